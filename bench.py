@@ -2,8 +2,9 @@
 """Headline benchmark: stylisation iterations/sec on the 200^3 smoke grid with 8 views
 (BASELINE.json metric; workload = configs[2], the configuration the metric is quoted on).
 
-  python bench.py --gpus N --steps K --warmup W        (N > 1 without WORLD_SIZE: re-executes itself under
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W        (N > 1 without WORLD_SIZE: starts itself as N ranks
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      with the environment
+                                                                                    torch.distributed.run gives a rank)
 
 One step at N = 1 = one stylisation iteration: advect -> smooth/clamp -> for all 8 views: rotate+render -> VGG-19
 conv1_1..conv5_1 -> Gram style loss -> full adjoint chain -> TF-Adam update of the 200^3 x 3 velocity field.  (The
@@ -31,6 +32,14 @@ Rank 0 prints ONE JSON line with the contract keys plus
   "cpu_baseline"  the CPU oracle timed on this box's host cores on a bounded sample (N=1 only),
   "parity"        gradient relative-L2 of the HIP path vs the oracle on a small case (N=1 only),
   "other_configs" short side measurements of BASELINE configs[0], [1], [3], [4] (N=1 only).
+
+--dump-outputs DIR (rank 0 writes; float32, at most 64 MB in all, an array larger than its share as a fixed seeded
+sample of its elements, see dump_outputs()):
+  views (N=1 and the default for N > 1)   loss.npy      the summed loss of the last timed step
+                                          density.npy   the smoothed density [G,G,G] that step rendered
+                                          velocity.npy  the velocity variable [G,G,G,3] after that step's Adam update
+  --scaling-by frames                     loss.npy      the per-frame losses of the last timed iteration
+                                          variable_f<t>.npy  the variable of every key frame t after it (all ranks')
 """
 from __future__ import annotations
 
@@ -78,22 +87,69 @@ def parse():
                     help="views 0..n-1 in the bounded CPU sample, besides view V-1 (so the default times two views)")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="BASELINE.md's protocol for the CPU baseline: 1 warm-up + median of 3 whole iterations (~20 min)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: ``arrays`` (name -> tensor) as out_dir/<name>.npy, float64 as it is, anything else as float32.
+    Every array gets an equal share of DUMP_BYTES; one larger than its share is written as a sample of that many
+    elements, at flat positions drawn without replacement from a fixed seed and sorted (the same positions in every run
+    with the same arguments)"""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 256                    # (room for the .npy header)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        k = share // t.element_size()
+        if t.numel() > k:
+            idx = np.sort(np.random.RandomState(0).choice(t.numel(), k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def relaunch(args):
-    """``python bench.py --gpus N`` outside a launcher: become N ranks (one per GPU) under torch.distributed.run"""
+    """``python bench.py --gpus N`` outside a launcher: run N ranks (one per GPU) as child processes with the environment
+    torch.distributed.run gives a rank, and exit when they have; the first rank to fail stops the others.  (No launcher
+    process: it would hold the GPU open beside the ranks.)"""
     import socket
+    import subprocess
     backend = os.environ.get("NFS_DIST_BACKEND", "nccl")
     if backend == "nccl" and torch.cuda.device_count() < args.gpus:
         raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible (one rank per GPU over RCCL); "
                          "NFS_DIST_BACKEND=gloo lets ranks share a GPU for a functional check"
                          % (args.gpus, torch.cuda.device_count()))
     s_ = socket.socket(); s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]; s_.close()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % args.gpus,
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    cmd = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(args.gpus),
+               LOCAL_WORLD_SIZE=str(args.gpus))
+    env.setdefault("OMP_NUM_THREADS", "1")                   # (as torch.distributed.run sets it for N > 1)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    procs, failed = [], None
+    try:
+        for r in range(args.gpus):
+            procs.append(subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r))))
+        while failed is None:
+            codes = [p.poll() for p in procs]                   # (every rank, every pass)
+            failed = next((r for r, c in enumerate(codes) if c), None)
+            if all(c is not None for c in codes):
+                break
+            time.sleep(0.1)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+            p.wait()
+    if failed is not None:
+        raise SystemExit("bench.py --gpus %d: rank %d exited with status %d" % (args.gpus, failed, procs[failed].returncode))
+    sys.exit(0)
 
 
 LIVE_BOX_FRAC = 1.0       # share of the volume inside the boxes the rotate adjoint accumulates (set from the mask in main())
@@ -1074,7 +1130,7 @@ def main():
         for _ in range(n):
             step()
 
-    def frames_run():
+    def frames_run(headline=False):
         """BASELINE configs[3] in weak scaling: world x frames_per_rank frames, sharded by frames"""
         F_ = world * args.frames_per_rank
         st = build_sequence(args, device, rank, world, F_, base, pg)
@@ -1084,6 +1140,10 @@ def main():
 
         settle(frames_step, 2)
         dt, last = time_steps(frames_step, barrier, args.warmup, args.steps, device, world)
+        if headline and args.dump_outputs:
+            allv = st.key_frame_variables()               # (a collective when the frames are sharded: every rank takes part)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, dict([("loss", last)] + [("variable_f%d" % t, allv[t]) for t in sorted(allv)]))
         res = dict(value=F_ * args.steps / dt, ms_per_step=1e3 * dt / args.steps, scaling="weak",
                    final_loss=float(last.sum()))
         cfg_ = dict(cfg_common, workload="smokegun %d^3 sequence of %d frames (%d per rank), %d rotated views per "
@@ -1102,6 +1162,10 @@ def main():
         settle(views_step)
         dt, last = time_steps(views_step, barrier, args.warmup, args.steps, device, world)
         out.update(value=args.steps / dt, ms_per_step=1e3 * dt / args.steps, scaling="strong", final_loss=float(last))
+        if args.dump_outputs:
+            velocity = gs.gather_variable()              # (a collective in the D-slab mode: every rank takes part)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, dict(loss=last, density=gs.d_s, velocity=velocity))
         # how the step was submitted: eagerly, or as a hipGraph replay -- the stylizer measures at its second step whether
         # the host can issue the ~80 launches faster than the GPU runs them (hosts of one pool differ by 2x)
         out["submission"] = {"hipgraph": bool(gs.use_graph),
@@ -1160,7 +1224,7 @@ def main():
             res, cfg_, _, _ = frames_run()
             out["frames_weak"] = dict(res, unit="frame-iters/s", workload=cfg_["workload"], parallelism=cfg_["parallelism"])
     else:
-        res, cfg_, step_fn, units = frames_run()
+        res, cfg_, step_fn, units = frames_run(headline=True)
         out.update(res)
         out["config"] = cfg_
         if gs is not None and world > 1:

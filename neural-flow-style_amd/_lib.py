@@ -180,7 +180,9 @@ ABI_VERSION = 151          # nfs_version() this table was written against (inclu
 
 def build(verbose=False):
     """Compile csrc/*.hip for gfx950 into libnfs_hip.so (in-tree)."""
-    r = subprocess.run(["make", "-C", CSRC_DIR, "-j", str(os.cpu_count() or 4)],
+    # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
+    jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
+    r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
                        capture_output=True, text=True)
     if verbose or r.returncode != 0:
         print(r.stdout[-4000:], r.stderr[-4000:])

@@ -254,6 +254,15 @@ class Styler(StylerBase):
         st.hist.append(losses)
         return losses
 
+    def key_frame_variables(self):
+        """the variable of every key frame as the loop has left it, {frame: tensor} on every rank (a collective when the
+        frames are sharded over ranks: every rank calls it)"""
+        st = self._st
+        if st.world > 1:
+            return parallel.exchange_frames(st.g_opt, set(st.keys), st.owner, st.work, group=self.pg,
+                                            need_by_rank=[set(st.keys)] * st.world)
+        return st.g_opt
+
     def finish(self):
         """frame interpolation (392-397) + final inference of every frame whose density this rank holds: all of them
         in an unsharded run (or a sharded one prepared with every frame), the rank's own frames after
@@ -261,8 +270,7 @@ class Styler(StylerBase):
         are"""
         st = self._st
         D, H, W_, _ = st.shape
-        allv = parallel.exchange_frames(st.g_opt, set(st.keys), st.owner, st.work, group=self.pg,
-                                        need_by_rank=[set(st.keys)] * st.world) if st.world > 1 else st.g_opt
+        allv = self.key_frame_variables()
         full = {t: allv[t] for t in st.keys}
         if self.interp > 1:
             w = np.linspace(0, 1, self.interp + 1)

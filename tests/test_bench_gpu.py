@@ -30,9 +30,16 @@ def _run(cmd, env=None):
     return json.loads(lines[0])
 
 
-def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory():
+def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory(tmp_path):
     args = ["--steps", "3", "--warmup", "1", "--grid", "64", "--no-cpu-baseline"]
-    one = _run([sys.executable, "bench.py"] + args)
+    one = _run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path)])
+    # --dump-outputs: the last timed step's loss (the line's final_loss), smoothed density and updated velocity, whole at 64^3
+    import numpy as np
+    dumped = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("loss", "density", "velocity")}
+    assert sorted(os.listdir(str(tmp_path))) == ["density.npy", "loss.npy", "velocity.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumped.values())
+    assert float(dumped["loss"]) == one["final_loss"]
+    assert dumped["density"].shape == (64, 64, 64) and dumped["velocity"].shape == (64, 64, 64, 3)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "kernels", "parity", "sustained", "other_configs",
               "scaling_by"):
@@ -79,38 +86,69 @@ def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory():
     assert v2["frames_weak"]["scaling"] == "weak" and v2["frames_weak"]["value"] > 0
     # frames as the headline on request; the same two-frame sequence on one rank: identical trajectory (frame sharding +
     # halo exchange are exact)
-    seq2 = _run([sys.executable, "bench.py", "--gpus", "2", "--scaling-by", "frames"] + fast, env=env)
+    seq2 = _run([sys.executable, "bench.py", "--gpus", "2", "--scaling-by", "frames"] + fast
+                + ["--dump-outputs", str(tmp_path / "seq2")], env=env)
     assert seq2["scaling"] == "weak" and seq2["scaling_by"] == "frames" and seq2["config"]["frames"] == 2
     assert abs(seq2["views_strong"]["final_loss"] - one["final_loss"]) <= 1e-5 * abs(one["final_loss"])
     assert abs(seq2["final_loss"] - v2["frames_weak"]["final_loss"]) <= 1e-5 * abs(seq2["final_loss"])
-    seq1 = _run([sys.executable, "bench.py", "--scaling-by", "frames", "--frames-per-rank", "2"] + fast)
+    seq1 = _run([sys.executable, "bench.py", "--scaling-by", "frames", "--frames-per-rank", "2"] + fast
+                + ["--dump-outputs", str(tmp_path / "seq1")])
     assert seq1["n_gpus"] == 1 and seq1["config"]["frames"] == 2
     assert abs(seq2["final_loss"] - seq1["final_loss"]) <= 1e-5 * abs(seq1["final_loss"])
+    # --dump-outputs in frames mode: every frame's variable, whichever rank owns it -- frame for frame the one-rank run's
+    names = ["loss.npy", "variable_f0.npy", "variable_f1.npy"]
+    assert sorted(os.listdir(str(tmp_path / "seq2"))) == names == sorted(os.listdir(str(tmp_path / "seq1")))
+    s1, s2 = ({n: np.load(str(tmp_path / d / n)) for n in names} for d in ("seq1", "seq2"))
+    np.testing.assert_allclose(s2["loss.npy"], s1["loss.npy"], rtol=1e-5)
+    assert float(s1["loss.npy"].sum()) == seq1["final_loss"]
+    for n in names[1:]:
+        assert s1[n].shape == (64, 64, 64, 3) and np.isfinite(s1[n]).all()
+        assert np.abs(s2[n] - s1[n]).max() <= 1e-4 * np.abs(s1[n]).max(), n
+
+
+_GLOO_ARGS = ["--steps", "3", "--warmup", "1", "--grid", "64", "--no-cpu-baseline", "--no-kernel-profile",
+              "--no-other-configs", "--no-sustained", "--no-split-limb"]
 
 
 def test_bench_gpus_4_and_8_over_gloo():
     """the rank counts of a SCALE run, functionally: ``bench.py --gpus 8`` (one view per rank, slabs of 64 / 8 planes)
-    and ``--gpus 4`` (two views per rank) as the driver launches them, the ranks sharing the one GPU over gloo.  Same
-    metric / workload as the one-rank line, the world size the ranks saw, and the trajectory of the one-rank run."""
-    args = ["--steps", "3", "--warmup", "1", "--grid", "64", "--no-cpu-baseline", "--no-kernel-profile",
-            "--no-other-configs", "--no-sustained", "--no-split-limb"]
-    one = _run([sys.executable, "bench.py"] + args)
+    and ``--gpus 4`` (two views per rank) as the driver launches them, the ranks sharing the visible GPUs over gloo.
+    Same metric / workload as the one-rank line, the world size the ranks saw, and the trajectory of the one-rank run."""
+    from tests.ranks import require_gpus_for
+    require_gpus_for(8)
+    one = _run([sys.executable, "bench.py"] + _GLOO_ARGS)
+    for n in (8, 4):
+        _check_gloo_ranks(n, one)
+
+
+def test_bench_gpus_4_over_gloo():
+    """``bench.py --gpus 4`` alone (two views per rank, slabs of 16 planes), the four ranks on one GPU where only one is
+    visible: the checks of test_bench_gpus_4_and_8_over_gloo at the rank count one GPU holds"""
+    from tests.ranks import require_gpus_for
+    require_gpus_for(4)
+    _check_gloo_ranks(4, _run([sys.executable, "bench.py"] + _GLOO_ARGS))
+
+
+def _check_gloo_ranks(n, one):
+    """``bench.py --gpus n`` over gloo against the one-rank line ``one`` of the same arguments"""
+    import torch
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         os.environ.pop(k, None)
-    for n in (8, 4):
-        r = _run([sys.executable, "bench.py", "--gpus", str(n)] + args, env={"NFS_DIST_BACKEND": "gloo"})
-        assert r["n_gpus"] == n and r["world_size_seen"] == n and r["collective_backend"] == "gloo"
-        assert r["config"]["views_per_rank"] == 8 // n and r["scaling"] == "strong"
-        assert r["metric"] == one["metric"] and r["config"]["workload"] == one["config"]["workload"]
-        assert abs(r["final_loss"] - one["final_loss"]) <= 1e-5 * abs(one["final_loss"]), (n, r["final_loss"])
-        assert r["config"]["field_work"].startswith("D-slab sharded"), r["config"]
-        # every rank's own record: backend, group size, device, the step's collectives timed on the device
-        assert len(r["ranks"]) == n and sorted(x["rank"] for x in r["ranks"]) == list(range(n))
-        for x in r["ranks"]:
-            assert x["backend"] == "gloo" and x["world_size"] == n and x["views_local"] == 8 // n
-            assert set(x["collectives"]) == {"reduce_scatter", "all_gather"}, x["collectives"]
-            assert all(c["calls_per_step"] == 1.0 and c["device_ms_per_step"] > 0 for c in x["collectives"].values())
-        assert r["collective_ms_per_step_max_over_ranks"] > 0 and r["distinct_devices"] == 1      # (one GPU shared here)
+    r = _run([sys.executable, "bench.py", "--gpus", str(n)] + _GLOO_ARGS, env={"NFS_DIST_BACKEND": "gloo"})
+    assert r["n_gpus"] == n and r["world_size_seen"] == n and r["collective_backend"] == "gloo"
+    assert r["config"]["views_per_rank"] == 8 // n and r["scaling"] == "strong"
+    assert r["metric"] == one["metric"] and r["config"]["workload"] == one["config"]["workload"]
+    assert abs(r["final_loss"] - one["final_loss"]) <= 1e-5 * abs(one["final_loss"]), (n, r["final_loss"])
+    assert r["config"]["field_work"].startswith("D-slab sharded"), r["config"]
+    # every rank's own record: backend, group size, device, the step's collectives timed on the device
+    assert len(r["ranks"]) == n and sorted(x["rank"] for x in r["ranks"]) == list(range(n))
+    for x in r["ranks"]:
+        assert x["backend"] == "gloo" and x["world_size"] == n and x["views_local"] == 8 // n
+        assert set(x["collectives"]) == {"reduce_scatter", "all_gather"}, x["collectives"]
+        assert all(c["calls_per_step"] == 1.0 and c["device_ms_per_step"] > 0 for c in x["collectives"].values())
+    # (rank r on GPU r mod the visible GPUs: one GPU shared by all of them on a one-GPU box)
+    assert r["collective_ms_per_step_max_over_ranks"] > 0
+    assert r["distinct_devices"] == min(n, torch.cuda.device_count())
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
