@@ -57,6 +57,20 @@ int nfs_gemm_timer(int enable);
  * The Gram gradient (mask / scale / symmetric operand) runs on the f32-input MFMA in both modes.
  * NFS_GEMM_MODE=0 presets 0. */
 int nfs_gemm_mode(int mode);
+/* Test hook (process-wide, off by default; nothing in the package calls it): run every following batched Winograd GEMM
+ * launch (conv products and the Gram gradient) on ONE kernel instance instead of the shape rule and the tile tuner -- no
+ * trial, no read or write of the tuner's cache.  variant -1: off.  0 LDS-B f32 (nbuf 1|2), 1 register-B f32,
+ * 2 16-row f32 (rb16), 3 16-row split-limb (rb16s; pre 0 float pack, 1 limb planes).  Returns NFS_EINVAL for a
+ * (variant, bm, bn, nbuf, pre) that names no instance.  Tiles: variants 0 / 1 bm, bn in {64, 128}; variants 2 / 3 bm in
+ * {48, 80, 112, 208}, bn in {64, 128, 256} (no 208 x 256); nbuf 0 outside variant 0, pre 0 outside variant 3.  Where
+ * the forced instance does not apply, the launch falls back as the dispatcher does (N % bn != 0 or a shape outside the
+ * 16-row form: the LDS-B kernel on the planner's tile; variant 3 on a masked / scaled / symmetric launch: variant 2;
+ * variant 1 there: variant 0; limb planes absent: pre 0).  The K parts stay the shape rule's (tests/test_gemm_instances_gpu.py). */
+int nfs_gemm_force(int variant, int bm, int bn, int nbuf, int pre);
+/* the instance the most recent batched GEMM launch ran, AFTER every applicability fallback, and its shape:
+ * out[0..10] = variant, bm, bn, nbuf, pre, ksplit, T, K, N, Z, trialled (1: the tuner timed candidates on it; the
+ * instance is then the last candidate launched, whose result the output holds).  variant -1: no launch yet. */
+int nfs_gemm_last(long long* out);
 int nfs_gemm_timer_read(double* ms_total, double* flops_total, long long* launches);
 /* the same for one kind of launch only (split_limb != 0: the bf16-MFMA split-limb launches; 0: the f32-input ones);
  * records of the other kind stay for a later read.  bytes_total (nullable): the summed algorithmic operand bytes of the

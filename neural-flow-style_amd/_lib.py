@@ -61,6 +61,8 @@ SIGNATURES = {
     "nfs_device_cus": [],
     "nfs_gemm_timer": [_I],
     "nfs_gemm_mode": [_I],
+    "nfs_gemm_force": [_I, _I, _I, _I, _I],
+    "nfs_gemm_last": [_P],
     "nfs_gemm_timer_read": [_P, _P, _P],
     "nfs_gemm_timer_read_kind": [_I, _P, _P, _P, _P],
     "nfs_warp3d_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -175,7 +177,7 @@ _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 151          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 152          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

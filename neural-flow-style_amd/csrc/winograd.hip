@@ -1557,11 +1557,13 @@ static void launch_gemm_rb16s_pre(const WgGemmArgs& a, hipStream_t s) {
     g_timer_recs.push_back(rec);
   }
 }
+// pre: -1 the row threshold above, 0 / 1 the float pack / the limb planes (nfs_gemm_force); returns the form launched
 template <int MT16, int NW16>
-static void launch_gemm_rb16s(const WgGemmArgs& a, hipStream_t s) {
+static int launch_gemm_rb16s(const WgGemmArgs& a, hipStream_t s, int pre = -1) {
   static const int64_t pre_rows = [] { const char* e = getenv("NFS_RB16S_PRE_ROWS"); return e ? atoll(e) : (int64_t)NFS_RB16S_PRE_ROWS; }();
-  if (NFS_RB16S_PRE && a.Ub16 && a.T >= pre_rows) launch_gemm_rb16s_pre<MT16, NW16, true>(a, s);
-  else launch_gemm_rb16s_pre<MT16, NW16, false>(a, s);
+  if (NFS_RB16S_PRE && a.Ub16 && (pre < 0 ? a.T >= pre_rows : pre == 1)) { launch_gemm_rb16s_pre<MT16, NW16, true>(a, s); return 1; }
+  launch_gemm_rb16s_pre<MT16, NW16, false>(a, s);
+  return 0;
 }
 
 // the register-B kernel takes the plain Winograd GEMMs (packed filters, no mask / scale) with 32-bit operand offsets
@@ -1603,10 +1605,20 @@ void winograd_pack_limbs16(const float* uq16, float* ub16, int K, int N, int Z, 
 
 static unsigned long long* g_gemm_prof = nullptr;        // NFS_ABLATE builds only (nfs_gemm_prof)
 
-static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s, int variant = 0) {
+// One kernel instance of the batched GEMM: variant 0 LDS-B f32 (nbuf 1 | 2), 1 register-B f32, 2 16-row f32 (rb16),
+// 3 16-row split-limb (rb16s; pre 0 the float pack split in registers, 1 the limb planes).  nbuf is 0 outside variant
+// 0, pre 0 outside variant 3.
+struct GemmInst { int variant, bm, bn, nbuf, pre; };
+
+// force_nbuf (1 | 2) / force_pre (0 | 1): nfs_gemm_force's choice instead of the rules below (0 / -1: the rules);
+// *ran (nullable): the instance launched, after the fallbacks of this function
+static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s, int variant = 0, GemmInst* ran = nullptr,
+                             int force_nbuf = 0, int force_pre = -1) {
   a.prof = g_gemm_prof;
   static const int nbuf_env = [] { const char* e = getenv("NFS_GEMM_NBUF"); return e ? atoi(e) : 0; }();
   const int nbuf = nbuf_env == 1 ? 1 : 2;
+  GemmInst dummy;
+  GemmInst& r = ran ? *ran : dummy;
   a.mt = (int)((a.T + bm - 1) / bm);
   a.nt = a.N / bn;
   a.Z = Z;
@@ -1623,10 +1635,12 @@ static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s,
     // the 16-row register-B form in split-limb arithmetic (mode 1): 64- or 128-column tiles
     a.mt = (int)((a.T + bm - 1) / bm);
     if (bn > 128 && bm == 208) { bn = 128; a.nt = a.N / 128; }
-    if (bm == 80) { if (bn == 256) launch_gemm_rb16s<5, 4>(a, s); else if (bn == 128) launch_gemm_rb16s<5, 2>(a, s); else launch_gemm_rb16s<5, 1>(a, s); }
-    else if (bm == 48) { if (bn == 256) launch_gemm_rb16s<3, 4>(a, s); else if (bn == 128) launch_gemm_rb16s<3, 2>(a, s); else launch_gemm_rb16s<3, 1>(a, s); }
-    else if (bm == 112) { if (bn == 256) launch_gemm_rb16s<7, 4>(a, s); else if (bn == 128) launch_gemm_rb16s<7, 2>(a, s); else launch_gemm_rb16s<7, 1>(a, s); }
-    else { if (bn == 128) launch_gemm_rb16s<13, 2>(a, s); else launch_gemm_rb16s<13, 1>(a, s); }
+    int p = force_pre;
+    if (bm == 80) { if (bn == 256) p = launch_gemm_rb16s<5, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<5, 2>(a, s, p); else p = launch_gemm_rb16s<5, 1>(a, s, p); }
+    else if (bm == 48) { if (bn == 256) p = launch_gemm_rb16s<3, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<3, 2>(a, s, p); else p = launch_gemm_rb16s<3, 1>(a, s, p); }
+    else if (bm == 112) { if (bn == 256) p = launch_gemm_rb16s<7, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<7, 2>(a, s, p); else p = launch_gemm_rb16s<7, 1>(a, s, p); }
+    else { if (bn == 128) p = launch_gemm_rb16s<13, 2>(a, s, p); else p = launch_gemm_rb16s<13, 1>(a, s, p); }
+    r = GemmInst{3, bm, bn == 256 || bn == 128 ? bn : 64, 0, p};
     return;
   }
   if (variant == 2 && gemm_rb16_applies(a) && rb16_rows_ok(bm) && a.N % bn == 0) {
@@ -1640,18 +1654,27 @@ static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s,
       if (bn == 256) { bn = 128; a.nt = a.N / 128; }          // (no 256-column instance of the 208-row form: 208 accumulators)
       if (bn == 128) launch_gemm_rb16<13, 2>(a, s); else launch_gemm_rb16<13, 1>(a, s);
     }
+    r = GemmInst{2, bm, bn == 256 || bn == 128 ? bn : 64, 0, 0};
     return;
   }
+  // (the 32-row kernels: 128- or 64-row, 128- or 64-column tiles, the grid counted for the tile that runs)
+  bm = bm == 128 ? 128 : 64;
+  bn = bn == 128 ? 128 : 64;
+  a.mt = (int)((a.T + bm - 1) / bm);
+  a.nt = a.N / bn;
   if (variant == 1 && gemm_rb_applies(a)) {
     if (bm == 128 && bn == 128) launch_gemm_rb<128, 128>(a, s);
     else if (bm == 128) launch_gemm_rb<128, 64>(a, s);
     else if (bn == 128) launch_gemm_rb<64, 128>(a, s);
     else launch_gemm_rb<64, 64>(a, s);
+    r = GemmInst{1, bm, bn, 0, 0};
     return;
   }
   // K = 64 (two chunks): nothing to double-buffer; a single LDS buffer doubles the co-resident blocks of this
   // bandwidth-bound shape (conv1_2: 0.103 -> 0.093 ms)
-  if (nbuf == 2 && (a.K > 64 || nbuf_env == 2)) {
+  const bool two = force_nbuf ? force_nbuf == 2 : nbuf == 2 && (a.K > 64 || nbuf_env == 2);
+  r = GemmInst{0, bm, bn, two ? 2 : 1, 0};
+  if (two) {
     if (bm == 128 && bn == 128) launch_gemm_variant<128, 128, 2>(a, s);
     else if (bm == 128) launch_gemm_variant<128, 64, 2>(a, s);
     else if (bn == 128) launch_gemm_variant<64, 128, 2>(a, s);
@@ -1678,6 +1701,17 @@ struct GemmKey {
 static std::map<GemmKey, std::tuple<int, int, int>> g_tile_cache;   // (BM, BN, kernel variant: 0 LDS-B, 1 register-B)
 static std::mutex g_tile_mu;
 
+// Test hook (nfs_gemm_force / nfs_gemm_last).  The forced instance, packed so that a launch reads it with one atomic
+// load: -1 off, else variant | bm << 4 | bn << 16 | nbuf << 28 | pre << 32.
+static std::atomic<long long> g_gemm_force{-1};
+// the most recent launch (under g_tile_mu): variant, bm, bn, nbuf, pre, ksplit, T, K, N, Z, trialled
+static long long g_gemm_last[11] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static void record_gemm_locked(const GemmInst& r, const WgGemmArgs& a, int Z, int trialled) {
+  const long long v[11] = {r.variant, r.bm, r.bn, r.nbuf, r.pre, r.variant >= 2 ? a.ksplit : 1, (long long)a.T, a.K, a.N,
+                           Z, trialled};
+  for (int i = 0; i < 11; ++i) g_gemm_last[i] = v[i];
+}
+
 int winograd_ksplit(int64_t T, int K) {
   static const int forced = [] { const char* e = getenv("NFS_GEMM_KSPLIT"); return e ? atoi(e) : 0; }();
   static const int tmax = [] { const char* e = getenv("NFS_GEMM_KSPLIT_T"); return e ? atoi(e) : 64; }();
@@ -1697,6 +1731,7 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
   static const int force_rb = [] { const char* e = getenv("NFS_GEMM_RB"); const int v = e ? atoi(e) : 0; return v == 2 ? 1 : v == 3 ? 2 : 0; }();
   int bm, bn, variant = force_rb;
   pick_gemm_tile(a.T, a.N, Z, cus, &bm, &bn);
+  const int bm32 = bm, bn32 = bn;
   // Which MFMA the GEMM runs on is decided by the shape alone (never by a measurement: the two instructions sum k in
   // different groupings, so their results differ in the last bit): the 16-row form wherever it executes no more rows
   // than the best 32-row tiling (NFS_GEMM_ROWS16_PCT, default 100: at equal rows it measured 3-5 % faster).  Within a family every candidate computes the identical result, and the tuner
@@ -1715,6 +1750,22 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
   // K parts (winograd_ksplit: by shape alone) only on the 16-row register-B form of a plain product (no mask / scale in
   // the epilogue: those apply to the complete sum)
   a.ksplit = (rows16 && !a.mask && !a.alpha_dev && a.alpha == 1.f && !a.symb) ? winograd_ksplit(a.T, a.K) : 1;
+  // nfs_gemm_force: one instance, no trial, the tuner's cache untouched.  The K parts stay the shape rule's (the conv
+  // workspace is sized by it).  Every instance stays inside M at any T: rows beyond T load as zeros (buffer descriptors /
+  // the LDS-B kernel's row guard) and are never stored (m < T in each epilogue); columns need N % bn == 0 -- where that
+  // or the 16-row form's applicability fails, the launch takes the 32-row LDS-B kernel on pick_gemm_tile's tile.
+  if (const long long f = g_gemm_force.load(std::memory_order_relaxed); f >= 0) {
+    int fv = (int)(f & 15), fbm = (int)((f >> 4) & 0xfff), fbn = (int)((f >> 16) & 0xfff), fnbuf = (int)((f >> 28) & 15);
+    const int fpre = (int)((f >> 32) & 1);
+    if (fv >= 2 && !(a.N % fbn == 0 && gemm_rb16_applies(a))) { fv = 0; fnbuf = 0; fbm = bm32; fbn = bn32; }
+    if (fv <= 1 && a.N % fbn) { fbm = bm32; fbn = bn32; }
+    if (fv != 2 && fv != 3) a.ksplit = 1;
+    GemmInst ran;
+    launch_gemm_tile(a, Z, fbm, fbn, s, fv, &ran, fnbuf, fv == 3 ? fpre : -1);
+    std::lock_guard<std::mutex> lk(g_tile_mu);
+    record_gemm_locked(ran, a, Z, 0);
+    return ran.variant >= 2 ? a.ksplit : 1;
+  }
   if (rows16 && !tune) { variant = v16; bm = bm16; bn = a.N % 128 == 0 ? 128 : 64; }
   if (force_rb == 2) {
     static const int fbm = [] { const char* e = getenv("NFS_GEMM_BM"); return e ? atoi(e) : 80; }();
@@ -1736,6 +1787,7 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
       hipEvent_t e0, e1;
       if (!capturing && !g_timer_on && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
         float best = 1e30f;
+        GemmInst ran;                                                   // (the last candidate launched: its result stays)
         auto trial = [&](int cbm, int cbn, int var) {
           launch_gemm_tile(a, Z, cbm, cbn, s, var);                     // warm (L2, instruction cache)
           // the fastest of three pairs: one pair alone mis-ranked candidates 5-10 % apart when something else (a
@@ -1743,7 +1795,7 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
           for (int rep = 0; rep < 3; ++rep) {
             (void)hipEventRecord(e0, s);
             launch_gemm_tile(a, Z, cbm, cbn, s, var);
-            launch_gemm_tile(a, Z, cbm, cbn, s, var);
+            launch_gemm_tile(a, Z, cbm, cbn, s, var, &ran);
             (void)hipEventRecord(e1, s);
             float ms = 1e30f;
             if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 1e30f;
@@ -1772,13 +1824,17 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
         if (log)
           fprintf(stderr, "gemm tuner: Z=%d T=%lld K=%d N=%d mask=%d ksplit=%d -> %d x %d (variant %d), %.1f us / launch\n",
                   Z, (long long)a.T, a.K, a.N, a.mask ? 1 : 0, a.ksplit, bm, bn, variant, 500.f * best);
+        record_gemm_locked(ran, a, Z, 1);
         return a.ksplit;                                              // the result is already in place
       }
     }
   }
   if (variant != 2 && variant != 3) a.ksplit = 1;                     // (only the rb16 kernels know about K parts)
-  launch_gemm_tile(a, Z, bm, bn, s, variant);
-  return a.ksplit;
+  GemmInst ran;
+  launch_gemm_tile(a, Z, bm, bn, s, variant, &ran);
+  std::lock_guard<std::mutex> lk(g_tile_mu);
+  record_gemm_locked(ran, a, Z, 0);
+  return ran.variant >= 2 ? a.ksplit : 1;
 }
 
 int winograd_launch_batched_gemm(const WgGemmArgs& a, int Z, int cus, hipStream_t s) { return launch_batched_gemm(a, Z, cus, s); }
@@ -1993,6 +2049,30 @@ int nfs_gemm_mode(int mode) {
   const int prev = nfs::g_gemm_mode.load();
   if (mode == 0 || mode == 1) nfs::g_gemm_mode.store(mode);
   return prev;
+}
+
+int nfs_gemm_force(int variant, int bm, int bn, int nbuf, int pre) {
+  if (variant == -1) { nfs::g_gemm_force.store(-1); return NFS_OK; }
+  const bool b32 = (bm == 64 || bm == 128) && (bn == 64 || bn == 128);
+  const bool b16 = nfs::rb16_rows_ok(bm) && (bn == 64 || bn == 128 || (bn == 256 && bm != 208));
+  const bool ok = (variant == 0 && b32 && (nbuf == 1 || nbuf == 2) && pre == 0) ||
+                  (variant == 1 && b32 && nbuf == 0 && pre == 0) || (variant == 2 && b16 && nbuf == 0 && pre == 0) ||
+                  (variant == 3 && b16 && nbuf == 0 && (pre == 0 || pre == 1));
+  if (!ok) {
+    nfs::set_error("nfs_gemm_force: (variant %d, bm %d, bn %d, nbuf %d, pre %d) names no GEMM instance", variant, bm, bn,
+                   nbuf, pre);
+    return NFS_EINVAL;
+  }
+  nfs::g_gemm_force.store((long long)variant | (long long)bm << 4 | (long long)bn << 16 | (long long)nbuf << 28 |
+                          (long long)pre << 32);
+  return NFS_OK;
+}
+
+int nfs_gemm_last(long long* out) {
+  if (!out) { nfs::set_error("nfs_gemm_last: null pointer"); return NFS_EINVAL; }
+  std::lock_guard<std::mutex> lk(nfs::g_tile_mu);
+  for (int i = 0; i < 11; ++i) out[i] = nfs::g_gemm_last[i];
+  return NFS_OK;
 }
 
 int nfs_gemm_timer(int enable) {
