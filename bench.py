@@ -16,22 +16,27 @@ N > 1 (``--scaling-by``):
   views (default)   the BASELINE metric: the 8 views of ONE frame sharded over the ranks (strong scaling); the exchange is
                     one all-reduce's worth of link traffic per iteration (reduce-scatter of the 32 MB density-field
                     gradient over D-slabs, slab-local field work, all-gather of the smoothed density).  Same metric,
-                    workload and unit as the N = 1 line.  The frame-sharded sequence is measured in the same run and
-                    reported under "frames_weak".
+                    workload and unit as the N = 1 line.  With --full the frame-sharded sequence is measured in the
+                    same run and reported under "frames_weak".
   frames            BASELINE configs[3] in weak scaling: N x ``--frames-per-rank`` frames of 200^3, every rank keeps
                     full 8-view batches for its own frames; one step = one iteration of the sequence loop (a
                     stylisation step per frame, halo exchange of the per-frame updates over RCCL point-to-point,
                     their temporal alignment by transport + Gaussian).  value = frame-iterations/s of the whole job;
-                    the view-sharded number rides along under "views_strong".
+                    with --full the view-sharded number rides along under "views_strong".
 
-Rank 0 prints ONE JSON line with the contract keys plus
+A plain run does what the headline needs and nothing else: it sets up, settles (lazy state, tile tuner, the
+eager-vs-hipGraph choice), warms up, times the K steps, writes --dump-outputs, and rank 0 prints ONE JSON line with the
+contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and how the step was configured and
+submitted.  --full adds everything else to the same line, measured after the headline timing:
   "roofline"      dominant kernel (the f32-MFMA Winograd GEMM) timed live with HIP events on its launch stream, in the
                   headline configuration,
   "kernels"       every C-ABI family the same way (HBM GB/s or TFLOP/s + fraction of peak; single-stream pass),
   "sustained"     >= 2 s of stepping in 20-step windows (median / min / max),
   "cpu_baseline"  the CPU oracle timed on this box's host cores on a bounded sample (N=1 only),
   "parity"        gradient relative-L2 of the HIP path vs the oracle on a small case (N=1 only),
-  "other_configs" short side measurements of BASELINE configs[0], [1], [3], [4] (N=1 only).
+  "other_configs" short side measurements of BASELINE configs[0], [1], [3], [4] (N=1 only),
+  "dead_region_skipping", "f32_mfma_gemm", "frames_weak" / "views_strong" (N>1), "ranks" (N>1): see main().
+The --no-* options leave parts of --full out.
 
 --dump-outputs DIR (rank 0 writes; float32, at most 64 MB in all, an array larger than its share as a fixed seeded
 sample of its elements, see dump_outputs()):
@@ -75,6 +80,10 @@ def parse():
                          "sequence of configs[3] in weak scaling; N=1 is the single-frame 8-view workload either way)")
     ap.add_argument("--frames-per-rank", type=int, default=1)
     ap.add_argument("--window-sigma", type=float, default=2.0, help="temporal filter of the sequence (config default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: kernel roofline, sustained rate, the "
+                         "other GEMM arithmetic, skipping controls, parity, CPU baseline, other configurations, the "
+                         "other sharding and the per-rank collectives (N>1); the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
@@ -84,9 +93,11 @@ def parse():
                     help="skip the dead-region-skipping controls (the same step with skipping off / on a dense density)")
     ap.add_argument("--no-split-limb", action="store_true", help="skip the secondary split-limb GEMM measurement")
     ap.add_argument("--cpu-views", type=int, default=1,
-                    help="views 0..n-1 in the bounded CPU sample, besides view V-1 (so the default times two views)")
+                    help="--full: views 0..n-1 in the bounded CPU sample, besides view V-1 (so the default times two "
+                         "views)")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="BASELINE.md's protocol for the CPU baseline: 1 warm-up + median of 3 whole iterations (~20 min)")
+                    help="--full: BASELINE.md's protocol for the CPU baseline: 1 warm-up + median of 3 whole iterations "
+                         "(~20 min)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
@@ -202,10 +213,9 @@ def live_box_fraction(gs):
     return float(m.mean()), vol / float(D * H * W), skipped / float(tiles)
 
 
-def build_problem(G, V, device, rank, world, dense=False):
-    from neural_flow_style_amd import engine, vgg
+def problem_data(G, V, dense=False):
+    """the synthetic inputs of the single-frame problem (seed 123): density, velocity, style image, view lattice"""
     from neural_flow_style_amd import synthetic as S
-    from neural_flow_style_amd import transform as T
     rng = np.random.RandomState(123)
     d0 = S.blob_density(G, rng)
     if dense:
@@ -215,6 +225,14 @@ def build_problem(G, V, device, rank, world, dense=False):
     vel = S.curl_velocity(G, rng, max_cells=2.0)
     simg = S.style_image(G, G, rng)
     mats = S.uniform_views(V)
+    return dict(d0=d0, vel=vel, simg=simg, mats=mats)
+
+
+def build_problem(G, V, device, rank, world, dense=False):
+    from neural_flow_style_amd import engine, vgg
+    from neural_flow_style_amd import transform as T
+    data = problem_data(G, V, dense)
+    d0, vel, simg, mats = data["d0"], data["vel"], data["simg"], data["mats"]
     net = vgg.VGG(vgg.synthetic_weights(123, upto="conv5_1"), device)
     loss = engine.RenderStyleLoss(net, STYLE_LAYERS, [1.0] * 5, 1.0, transmit=0.01)
     loss.set_style_image(simg)
@@ -225,7 +243,7 @@ def build_problem(G, V, device, rank, world, dense=False):
     gs = engine.GridStylizer(loss, torch.tensor(d0, device=device), k=3, target="v", lr=1e-3, process_group=pg)
     gs.var.copy_(torch.tensor(vel))
     rot_local = T.rot_to_device(mats[rank::world], device)
-    return gs, rot_local, dict(d0=d0, vel=vel, simg=simg, mats=mats)
+    return gs, rot_local, data
 
 
 # ---- algorithmic work per call ---------------------------------------
@@ -1098,11 +1116,11 @@ def main():
     # ---- the single-frame problem (N=1 headline; view-sharded strong scaling for N>1) ---------------------------------
     views_ok = V % world == 0
     gs = rot_local = None
-    if mode == "views" or views_ok:
+    if mode == "views" or (args.full and views_ok):
         assert mode != "views" or views_ok, "views must divide over ranks"
         gs, rot_local, base = build_problem(G, V, device, rank, world)
     else:
-        _, _, base = build_problem(G, V, device, 0, 1)
+        base = problem_data(G, V)
 
     from neural_flow_style_amd import ops as _ops
     gemm_mode0 = _ops.gemm_mode(None)          # the library's arithmetic for the Winograd GEMMs (1: split-limb, the default)
@@ -1182,7 +1200,7 @@ def main():
                              if gs.slab is not None else
                              ("replicated on every rank behind one all-reduce(sum)" if world > 1 else "one rank"))
         step_fn, units = views_step, 1
-        if gs._live_kw() and not args.no_skip_control:
+        if args.full and gs._live_kw() and not args.no_skip_control:
             # data dependence of the headline, made visible: the rotate adjoint skips what only feeds voxels whose
             # velocity gradient is an exact zero (empty space, plateaus).  (a) the same problem with skipping off,
             # (b) a dense density on which nothing can be skipped -- both NOT the headline
@@ -1219,7 +1237,7 @@ def main():
                 del gsd, rotd
                 torch.cuda.empty_cache()
             out["dead_region_skipping"] = ctl
-        if world > 1 and not args.no_other_configs:
+        if args.full and world > 1 and not args.no_other_configs:
             # the same box, the other sharding: a sequence with one frame per rank (weak scaling)
             res, cfg_, _, _ = frames_run()
             out["frames_weak"] = dict(res, unit="frame-iters/s", workload=cfg_["workload"], parallelism=cfg_["parallelism"])
@@ -1227,7 +1245,7 @@ def main():
         res, cfg_, step_fn, units = frames_run(headline=True)
         out.update(res)
         out["config"] = cfg_
-        if gs is not None and world > 1:
+        if args.full and gs is not None and world > 1:
             # the same box, the other sharding: the 8 views of ONE frame over the ranks (strong scaling)
             settle(views_step)
             dtv, lv = time_steps(views_step, barrier, args.warmup, args.steps, device, world)
@@ -1237,9 +1255,11 @@ def main():
                                                  % (4 * G ** 3 // 2 ** 20)}
     if world > 1:
         import torch.distributed as dist
-        from neural_flow_style_amd import parallel as _par
         out["collective_backend"] = dist.get_backend()
         out["world_size_seen"] = dist.get_world_size()
+    if args.full and world > 1:
+        import torch.distributed as dist
+        from neural_flow_style_amd import parallel as _par
         # what every rank saw: the backend (nccl = RCCL), the group size, its device, and the collectives of a step timed
         # on the device (event pair on the stream that waits for the collective) -- a SCALE run then shows that RCCL had N
         # ranks on N devices and how far the exchange is from the 0.05-0.37 ms DESIGN section 7 estimates for it
@@ -1262,11 +1282,11 @@ def main():
         out["collective_ms_per_step_max_over_ranks"] = max(r["collective_device_ms_per_step"] for r in allr)
         out["distinct_devices"] = len(set((r["device_uuid"] or r["device_index"]) for r in allr))
 
-    if not args.no_sustained:
+    if args.full and not args.no_sustained:
         out["sustained"] = dict(sustained(step_fn, barrier, units, device, world), unit=out["unit"])
 
     # ---- the same workload with the Winograd GEMMs in the OTHER arithmetic (see nfs_gemm_mode) ---------------------------
-    if gs is not None and mode == "views" and not args.no_split_limb:
+    if args.full and gs is not None and mode == "views" and not args.no_split_limb:
         from neural_flow_style_amd import ops
         other = 1 - gemm_mode0
         prev = ops.gemm_mode(other)
@@ -1285,7 +1305,7 @@ def main():
             ops.gemm_mode(prev)
 
     # ---- per-kernel live measurement (extra profiled steps, after the headline timing) -----------
-    if not args.no_kernel_profile and gs is not None:
+    if args.full and not args.no_kernel_profile and gs is not None:
         import ctypes
         psteps = max(2, min(args.steps, 5))
         gs.use_graph = False          # the per-call timers hook the C-ABI calls: a graph replay would bypass them
@@ -1425,7 +1445,7 @@ def main():
                                          "4VG^2) + the advect kernels as built, over the same measured time"}}
         out["kernels"] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_parity:
             try:
                 out["parity"] = small_parity(device)

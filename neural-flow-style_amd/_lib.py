@@ -224,7 +224,7 @@ def lib():
     return _lib
 
 
-# Optional live profiling (used by bench.py): when PROFILE is a dict, every call is bracketed by
+# Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
 # two events recorded on the SAME stream the kernel is enqueued on; entries are
 # name -> [(start_event, end_event, args)].  Costs two event records per call, so it is off by
 # default and the headline timing in bench.py is taken with it off.

@@ -25,8 +25,8 @@ def shard(items, rank=None, world=None, group=None):
     return list(items[rank::world])
 
 
-# Optional timing of the collectives (bench.py --gpus N): when TIMER is a dict every collective below is bracketed by an
-# event pair on the current stream (the stream the collective's result is waited on) and a host clock; entries are
+# Optional timing of the collectives (bench.py --full --gpus N): when TIMER is a dict every collective below is bracketed
+# by an event pair on the current stream (the stream the collective's result is waited on) and a host clock; entries are
 # name -> [(start_event, end_event, payload_bytes, host_seconds)].  Off by default: two event records per call.
 TIMER = None
 

@@ -1,5 +1,6 @@
-"""bench.py --dump-outputs and --steps without a GPU: the files dump_outputs() writes (float32 / float64, the 64 MB budget,
-the seeded sample of an array larger than its share) and the refusal of fewer than one timed step."""
+"""bench.py --dump-outputs, --steps and --full without a GPU: the files dump_outputs() writes (float32 / float64, the
+64 MB budget, the seeded sample of an array larger than its share), the refusal of fewer than one timed step, and --full
+off by default."""
 import os
 import sys
 
@@ -39,3 +40,11 @@ def test_steps_below_one_are_refused(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out"])
     a = bench.parse()
     assert a.steps == 7 and a.dump_outputs == "out"
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "10", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline

@@ -32,7 +32,7 @@ def _run(cmd, env=None):
 
 def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory(tmp_path):
     args = ["--steps", "3", "--warmup", "1", "--grid", "64", "--no-cpu-baseline"]
-    one = _run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path)])
+    one = _run([sys.executable, "bench.py", "--full"] + args + ["--dump-outputs", str(tmp_path)])
     # --dump-outputs: the last timed step's loss (the line's final_loss), smoothed density and updated velocity, whole at 64^3
     import numpy as np
     dumped = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("loss", "density", "velocity")}
@@ -78,7 +78,8 @@ def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory(tmp_p
     env = {"NFS_DIST_BACKEND": "gloo"}
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         os.environ.pop(k, None)
-    v2 = _run([sys.executable, "bench.py", "--gpus", "2"] + args + ["--no-kernel-profile", "--no-sustained"], env=env)
+    v2 = _run([sys.executable, "bench.py", "--gpus", "2", "--full"] + args + ["--no-kernel-profile", "--no-sustained"],
+              env=env)
     assert v2["n_gpus"] == 2 and v2["world_size_seen"] == 2 and v2["scaling"] == "strong" and v2["scaling_by"] == "views"
     assert v2["metric"] == one["metric"] and v2["unit"] == one["unit"]
     assert v2["config"]["workload"] == one["config"]["workload"] and v2["config"]["views_per_rank"] == 4
@@ -86,7 +87,7 @@ def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory(tmp_p
     assert v2["frames_weak"]["scaling"] == "weak" and v2["frames_weak"]["value"] > 0
     # frames as the headline on request; the same two-frame sequence on one rank: identical trajectory (frame sharding +
     # halo exchange are exact)
-    seq2 = _run([sys.executable, "bench.py", "--gpus", "2", "--scaling-by", "frames"] + fast
+    seq2 = _run([sys.executable, "bench.py", "--gpus", "2", "--scaling-by", "frames", "--full"] + fast
                 + ["--dump-outputs", str(tmp_path / "seq2")], env=env)
     assert seq2["scaling"] == "weak" and seq2["scaling_by"] == "frames" and seq2["config"]["frames"] == 2
     assert abs(seq2["views_strong"]["final_loss"] - one["final_loss"]) <= 1e-5 * abs(one["final_loss"])
@@ -106,7 +107,35 @@ def test_bench_line_and_sharded_ranks_reproduce_the_single_rank_trajectory(tmp_p
         assert np.abs(s2[n] - s1[n]).max() <= 1e-4 * np.abs(s1[n]).max(), n
 
 
-_GLOO_ARGS = ["--steps", "3", "--warmup", "1", "--grid", "64", "--no-cpu-baseline", "--no-kernel-profile",
+_MOVED_KEYS = ("roofline", "kernels", "render_advect_family", "sustained", "f32_mfma_gemm", "split_limb_gemm",
+               "dead_region_skipping", "parity", "cpu_baseline", "other_configs", "frames_weak", "views_strong", "ranks")
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """without --full the line carries the headline and how it was run, nothing measured beside it; its timed steps and
+    --dump-outputs are those of a --full run of the same arguments"""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--grid", "64"]
+    plain = _run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / "plain")])
+    full = _run([sys.executable, "bench.py", "--full"] + args + ["--no-cpu-baseline", "--no-other-configs",
+                                                                 "--dump-outputs", str(tmp_path / "full")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+              "scaling", "scaling_by", "vs_baseline", "data", "config", "submission", "final_loss"):
+        assert k in plain, k
+    assert not [k for k in _MOVED_KEYS if k in plain], plain.keys()
+    assert all(k in full for k in ("roofline", "kernels", "sustained", "f32_mfma_gemm", "dead_region_skipping", "parity"))
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and abs(plain["value"] * plain["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert abs(plain["final_loss"] - full["final_loss"]) <= 1e-5 * abs(full["final_loss"])
+    names = ["density.npy", "loss.npy", "velocity.npy"]
+    assert sorted(os.listdir(str(tmp_path / "plain"))) == names == sorted(os.listdir(str(tmp_path / "full")))
+    for n in names:
+        a, b = np.load(str(tmp_path / "plain" / n)), np.load(str(tmp_path / "full" / n))
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-4 * max(np.abs(b).max(), 1e-30), n
+
+
+_GLOO_ARGS = ["--steps", "3", "--warmup", "1", "--grid", "64", "--full", "--no-cpu-baseline", "--no-kernel-profile",
               "--no-other-configs", "--no-sustained", "--no-split-limb"]
 
 

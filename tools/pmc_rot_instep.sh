@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp
-BENCH="python $root/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-kernel-profile --no-parity --no-sustained --no-other-configs --no-split-limb"
+BENCH="python $root/bench.py --steps 6 --warmup 2"
 i=0
 for s in "SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS" "SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_VALU" "GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "SQ_BUSY_CU_CYCLES SQ_INSTS_SALU SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VMEM"; do
   rm -rf /tmp/pri$i

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence run for profiles/: kernel-trace stats, the two PMC passes (separate runs, kernel-trace only), and the
-# plain bench line.  Usage (on the GPU box, from the repo root):  bash tools/profile_round.sh r01_c
+# --full bench line.  Usage (on an MI355X, from the repo root):  bash tools/profile_round.sh r01_c
 # Writes gpurun_out/<tag>_*; copy what should be judged into profiles/.
 set -u
 tag=${1:-r01_x}
@@ -8,7 +8,7 @@ root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-BENCH="python $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-kernel-profile --no-parity --no-sustained --no-other-configs --no-split-limb --no-skip-control"
+BENCH="python $root/bench.py --steps 10 --warmup 2"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o b -- $BENCH > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/${tag}_pmc_fetch -o b -- $BENCH > /dev/null 2> $out/${tag}_pmc_fetch.err
@@ -24,7 +24,7 @@ python tools/pmc_traffic.py $(find $out/${tag}_pmc_fetch -name 'b_counter_collec
                             $out/${tag}_traffic.json > $out/${tag}_traffic.txt
 # the raw counter CSVs are large; keep only the summaries
 rm -rf $out/${tag}_pmc_fetch $out/${tag}_pmc_write $out/${tag}_stats
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 600 $out/${tag}_bench_under_rocprof.json; cat $out/${tag}_instep.txt
 python - <<EOF
 import csv
