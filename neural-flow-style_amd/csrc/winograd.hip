@@ -1430,19 +1430,18 @@ static std::atomic<bool> g_timer_on{false};
 static std::vector<GemmTimerRec> g_timer_recs;
 static std::mutex g_timer_mu;
 
-template <int BM, int BN, int NBUF>
-static void launch_gemm_variant(const WgGemmArgs& a, hipStream_t s) {
-  const size_t oper = NBUF * (BM + BN) * WG_LS, tile = BM * (BN + 4);
-  const size_t lds = (oper > tile ? oper : tile) * sizeof(float);
+// Every launch of a batched GEMM kernel: the LDS limit raised once per kernel instance whose tiles need more than 64 KB,
+// the grid rounded up to whole rounds of the XCD deal, and while nfs_gemm_timer is on an event pair around the launch
+// (rec: what its record counts).
+template <auto KERNEL, typename Args>
+static void launch_gemm_kernel(const Args& a, size_t lds, int blocks, GemmTimerRec rec, hipStream_t s) {
   static std::once_flag attr_once;   // (one set per kernel instance, safe from several host threads)
   if (lds > 65536) std::call_once(attr_once, [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_gemm_kernel<BM, BN, NBUF>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-  const int total = a.mt * a.nt * a.Z, grid = (total + WG_XCDS - 1) / WG_XCDS * WG_XCDS;
-  GemmTimerRec rec{nullptr, nullptr, 2.0 * a.Z * (double)a.T * a.K * a.N};
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+  const int grid = (blocks + WG_XCDS - 1) / WG_XCDS * WG_XCDS;
   const bool timed = g_timer_on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
   if (timed) (void)hipEventRecord(rec.e0, s);
-  hipLaunchKernelGGL((winograd_gemm_kernel<BM, BN, NBUF>), dim3(grid), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), lds, s, a);
   if (timed) {
     (void)hipEventRecord(rec.e1, s);
     std::lock_guard<std::mutex> lk(g_timer_mu);
@@ -1455,8 +1454,6 @@ static void launch_gemm_variant(const WgGemmArgs& a, hipStream_t s) {
 // ceil(left-over blocks / CUs)] x BM x BN, with M padded to BM: small T (deep layers, few views per GPU) wants
 // BM = 64, a grid that just misses a round boundary wants the other aspect ratio.
 static void pick_gemm_tile(int64_t T, int N, int Z, int cus, int* bm_out, int* bn_out) {
-  static const int force_bm = [] { const char* e = getenv("NFS_GEMM_BM"); return e ? atoi(e) : 0; }();
-  static const int force_bn = [] { const char* e = getenv("NFS_GEMM_BN"); return e ? atoi(e) : 0; }();
   double best = 1e300;
   *bm_out = 128; *bn_out = 64;
   const int bms[2] = {128, 64}, bns[2] = {64, 128};
@@ -1464,8 +1461,6 @@ static void pick_gemm_tile(int64_t T, int N, int Z, int cus, int* bm_out, int* b
     for (int ni = 0; ni < 2; ++ni) {
       const int bm = bms[bi], bn = bns[ni];
       if (N % bn) continue;
-      if (force_bm && bm != force_bm) continue;
-      if (force_bn && bn != force_bn && N % force_bn == 0) continue;
       const size_t oper = 2 * (bm + bn) * WG_LS, tile = (size_t)bm * (bn + 4);
       const size_t lds = (oper > tile ? oper : tile) * sizeof(float);
       int bpc = (int)(160 * 1024 / lds);
@@ -1483,48 +1478,6 @@ static void pick_gemm_tile(int64_t T, int N, int Z, int cus, int* bm_out, int* b
 // winograd_gemm_split_kernel).  Process-wide setting (nfs_gemm_mode); NFS_GEMM_MODE presets it.
 static std::atomic<int> g_gemm_mode{[] { const char* e = getenv("NFS_GEMM_MODE"); return e ? (atoi(e) == 0 ? 0 : 1) : 1; }()};
 
-template <int BM, int BN>
-static void launch_gemm_rb(const WgGemmArgs& a, hipStream_t s) {
-  const size_t oper = 2 * BM * WG_LS, tile = (BM / 2) * (BN + 4);
-  const size_t lds = (oper > tile ? oper : tile) * sizeof(float);
-  static std::once_flag attr_once;   // (one set per kernel instance, safe from several host threads)
-  if (lds > 65536) std::call_once(attr_once, [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_gemm_rb_kernel<BM, BN>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-  const int total = a.mt * a.nt * a.Z, grid = (total + WG_XCDS - 1) / WG_XCDS * WG_XCDS;
-  GemmTimerRec rec{nullptr, nullptr, 2.0 * a.Z * (double)a.T * a.K * a.N};
-  const bool timed = g_timer_on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
-  if (timed) (void)hipEventRecord(rec.e0, s);
-  hipLaunchKernelGGL((winograd_gemm_rb_kernel<BM, BN>), dim3(grid), dim3(256), lds, s, a);
-  if (timed) {
-    (void)hipEventRecord(rec.e1, s);
-    std::lock_guard<std::mutex> lk(g_timer_mu);
-    g_timer_recs.push_back(rec);
-  }
-}
-
-template <int MT16, int NW16>
-static void launch_gemm_rb16(const WgGemmArgs& a, hipStream_t s) {
-  constexpr int BM = 16 * MT16, BN = 64 * NW16, BMP = (BM + 31) / 32 * 32;
-  constexpr int EPMAX = NW16 >= 4 ? 2 : 5;
-  const size_t oper = 2 * BMP * WG_LS, tile = 16 * (MT16 < EPMAX ? MT16 : EPMAX) * (BN + 4);
-  const size_t lds = (oper > tile ? oper : tile) * sizeof(float);
-  static std::once_flag attr_once;
-  if (lds > 65536) std::call_once(attr_once, [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_gemm_rb16_kernel<MT16, NW16>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-  const int total = a.mt * a.nt * a.Z * a.ksplit, grid = (total + WG_XCDS - 1) / WG_XCDS * WG_XCDS;
-  GemmTimerRec rec{nullptr, nullptr, 2.0 * a.Z * (double)a.T * a.K * a.N};
-  const bool timed = g_timer_on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
-  if (timed) (void)hipEventRecord(rec.e0, s);
-  hipLaunchKernelGGL((winograd_gemm_rb16_kernel<MT16, NW16>), dim3(grid), dim3(256), lds, s, a);
-  if (timed) {
-    (void)hipEventRecord(rec.e1, s);
-    std::lock_guard<std::mutex> lk(g_timer_mu);
-    g_timer_recs.push_back(rec);
-  }
-}
-
 // Which form of B a launch reads: the limb planes (6 bytes per filter value, no split in the kernel) from NFS_RB16S_PRE_ROWS
 // rows on, the float32 fragment pack split in registers (4 bytes per value) below -- a launch of a few dozen rows (one or
 // two views per GPU) is bound by its filter stream, 51 MB at conv4_x, and the planes would make that 77 (one view 0.958 ->
@@ -1534,63 +1487,15 @@ static void launch_gemm_rb16(const WgGemmArgs& a, hipStream_t s) {
 #ifndef NFS_RB16S_PRE_ROWS
 #define NFS_RB16S_PRE_ROWS 128
 #endif
-template <int MT16, int NW16, bool PRE>
-static void launch_gemm_rb16s_pre(const WgGemmArgs& a, hipStream_t s) {
-  constexpr int BM = 16 * MT16, BN = 64 * NW16, BMP = (BM + 31) / 32 * 32;
-  constexpr int EPMAX = NW16 >= 4 ? 2 : 5;
-  const size_t oper = (size_t)2 * 3 * BMP * WS_RB, tile = (size_t)16 * (MT16 < EPMAX ? MT16 : EPMAX) * (BN + 4) * sizeof(float);
-  const size_t lds = oper > tile ? oper : tile;
-  static std::once_flag attr_once;
-  if (lds > 65536) std::call_once(attr_once, [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winograd_gemm_rb16s_kernel<MT16, NW16, PRE>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-  const int total = a.mt * a.nt * a.Z * a.ksplit, grid = (total + WG_XCDS - 1) / WG_XCDS * WG_XCDS;
-  GemmTimerRec rec{nullptr, nullptr, 2.0 * a.Z * (double)a.T * a.K * a.N};
-  const bool timed = g_timer_on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
-  if (timed) (void)hipEventRecord(rec.e0, s);
-  hipLaunchKernelGGL((winograd_gemm_rb16s_kernel<MT16, NW16, PRE>), dim3(grid), dim3(256), lds, s, a);
-  if (timed) {
-    rec.split = 1;
-    rec.bytes = a.Z * (4.0 * a.T * a.K + (PRE ? 6.0 : 4.0) * a.K * a.N + 4.0 * a.T * a.N * a.ksplit);   // V, filters, M
-    (void)hipEventRecord(rec.e1, s);
-    std::lock_guard<std::mutex> lk(g_timer_mu);
-    g_timer_recs.push_back(rec);
-  }
-}
-// pre: -1 the row threshold above, 0 / 1 the float pack / the limb planes (nfs_gemm_force); returns the form launched
-template <int MT16, int NW16>
-static int launch_gemm_rb16s(const WgGemmArgs& a, hipStream_t s, int pre = -1) {
-  static const int64_t pre_rows = [] { const char* e = getenv("NFS_RB16S_PRE_ROWS"); return e ? atoll(e) : (int64_t)NFS_RB16S_PRE_ROWS; }();
-  if (NFS_RB16S_PRE && a.Ub16 && (pre < 0 ? a.T >= pre_rows : pre == 1)) { launch_gemm_rb16s_pre<MT16, NW16, true>(a, s); return 1; }
-  launch_gemm_rb16s_pre<MT16, NW16, false>(a, s);
-  return 0;
-}
 
 // the register-B kernel takes the plain Winograd GEMMs (packed filters, no mask / scale) with 32-bit operand offsets
-// row tiles of the 16-row form: 80 (5 MFMA tiles), 48, 112, 208 (e.g. the 200 rows of an F(5x5) layer at 8 views)
-static const int kRb16Rows[4] = {80, 48, 112, 208};
-static bool rb16_rows_ok(int bm) { return bm == 80 || bm == 48 || bm == 112 || bm == 208; }
-// rows the 16-row form executes with row tile bm: the 80- and 48-row blocks run only the 16-row tiles that exist (their
-// last block is ragged), the taller ones keep whole zero-padded blocks
-static int64_t rb16_rows_executed(int64_t T, int bm) { return bm <= 80 ? (T + 15) / 16 * 16 : (T + bm - 1) / bm * bm; }
-static int64_t rb16_best_rows(int64_t T, int* bm_out) {
-  int64_t best = -1;
-  for (int i = 0; i < 4; ++i) {
-    const int64_t p = rb16_rows_executed(T, kRb16Rows[i]);
-    if (best < 0 || p < best) { best = p; if (bm_out) *bm_out = kRb16Rows[i]; }
-  }
-  return best;
+static bool gemm_rb_applies(const WgGemmArgs& a) {
+  return a.Uq && !a.mask && !a.alpha_dev && a.alpha == 1.f && a.T * a.K * 4 < ((int64_t)1 << 31) &&
+         (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
 }
-
 // ... the 16-row form also scales and masks (the Gram gradient runs on it, its symmetric D read in place)
 static bool gemm_rb16_applies(const WgGemmArgs& a) {
-  static const bool off = [] { const char* e = getenv("NFS_GEMM_RB"); return e && atoi(e) == 0; }();
-  return !off && a.Uq16 && a.T * a.K * 4 < ((int64_t)1 << 31) && (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
-}
-static bool gemm_rb_applies(const WgGemmArgs& a) {
-  static const bool off = [] { const char* e = getenv("NFS_GEMM_RB"); return e && atoi(e) == 0; }();
-  return !off && a.Uq && !a.mask && !a.alpha_dev && a.alpha == 1.f && a.T * a.K * 4 < ((int64_t)1 << 31) &&
-         (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
+  return a.Uq16 && a.T * a.K * 4 < ((int64_t)1 << 31) && (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
 }
 
 void winograd_pack_frag16(const float* up, float* uq, int K, int N, int64_t total, hipStream_t s) {
@@ -1603,26 +1508,130 @@ void winograd_pack_limbs16(const float* uq16, float* ub16, int K, int N, int Z, 
                      reinterpret_cast<const float4*>(uq16), reinterpret_cast<uint4*>(ub16), total);
 }
 
-static unsigned long long* g_gemm_prof = nullptr;        // NFS_ABLATE builds only (nfs_gemm_prof)
+#ifdef NFS_ABLATE
+static unsigned long long* g_gemm_prof = nullptr;        // (nfs_gemm_prof)
+#endif
 
 // One kernel instance of the batched GEMM: variant 0 LDS-B f32 (nbuf 1 | 2), 1 register-B f32, 2 16-row f32 (rb16),
 // 3 16-row split-limb (rb16s; pre 0 the float pack split in registers, 1 the limb planes).  nbuf is 0 outside variant
 // 0, pre 0 outside variant 3.
 struct GemmInst { int variant, bm, bn, nbuf, pre; };
 
-// force_nbuf (1 | 2) / force_pre (0 | 1): nfs_gemm_force's choice instead of the rules below (0 / -1: the rules);
-// *ran (nullable): the instance launched, after the fallbacks of this function
-static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s, int variant = 0, GemmInst* ran = nullptr,
-                             int force_nbuf = 0, int force_pre = -1) {
-  a.prof = g_gemm_prof;
-  static const int nbuf_env = [] { const char* e = getenv("NFS_GEMM_NBUF"); return e ? atoi(e) : 0; }();
-  const int nbuf = nbuf_env == 1 ? 1 : 2;
-  GemmInst dummy;
-  GemmInst& r = ran ? *ran : dummy;
-  a.mt = (int)((a.T + bm - 1) / bm);
-  a.nt = a.N / bn;
-  a.Z = Z;
+// LDS bytes of an instance: its staged operand buffers or the C tile its epilogue stages, whichever is larger.  The
+// 16-row forms stage their rows in whole 32-row passes (BMP), as float rows (rb16) or as three bf16 limb planes (rb16s),
+// and C in passes of at most 5 row tiles (2 at 256 columns).
+template <int V, int BM, int BN, int NBUF>
+constexpr size_t gemm_lds_bytes() {
+  constexpr int BMP = (BM + 31) / 32 * 32, EP = std::min(BM / 16, BN >= 256 ? 2 : 5);
+  const size_t oper = V == 0 ? NBUF * (BM + BN) * WG_LS * sizeof(float)
+                    : V == 1 ? 2 * BM * WG_LS * sizeof(float)
+                    : V == 2 ? 2 * BMP * WG_LS * sizeof(float)
+                             : (size_t)2 * 3 * BMP * WS_RB;
+  const size_t tile = (V == 0 ? BM : V == 1 ? BM / 2 : 16 * EP) * (BN + 4) * sizeof(float);
+  return std::max(oper, tile);
+}
+
+// launches instance (V, BM, BN, NBUF, PRE) over a.mt x a.nt x a.Z tiles (x a.ksplit K parts in the 16-row forms)
+template <int V, int BM, int BN, int NBUF, int PRE>
+static void launch_gemm_inst(const WgGemmArgs& a, hipStream_t s) {
+  constexpr size_t lds = gemm_lds_bytes<V, BM, BN, NBUF>();
+  GemmTimerRec rec{nullptr, nullptr, 2.0 * a.Z * (double)a.T * a.K * a.N};
+  const int blocks = a.mt * a.nt * a.Z;
+  if constexpr (V == 0) {
+    launch_gemm_kernel<winograd_gemm_kernel<BM, BN, NBUF>>(a, lds, blocks, rec, s);
+  } else if constexpr (V == 1) {
+    launch_gemm_kernel<winograd_gemm_rb_kernel<BM, BN>>(a, lds, blocks, rec, s);
+  } else if constexpr (V == 2) {
+    launch_gemm_kernel<winograd_gemm_rb16_kernel<BM / 16, BN / 64>>(a, lds, blocks * a.ksplit, rec, s);
+  } else {
+    rec.split = 1;
+    rec.bytes = a.Z * (4.0 * a.T * a.K + (PRE ? 6.0 : 4.0) * a.K * a.N + 4.0 * a.T * a.N * a.ksplit);   // V, filters, M
+    launch_gemm_kernel<winograd_gemm_rb16s_kernel<BM / 16, BN / 64, PRE>>(a, lds, blocks * a.ksplit, rec, s);
+  }
+}
+
+// The kernel instances of the batched GEMM, one row each.  This is the only list of them: launch_gemm_tile launches a
+// row, the tuner's candidates and the 16-row tile heights are read from it, and nfs_gemm_force accepts exactly its rows.
+// The forms of one tile (nbuf, pre) are adjacent rows, and within a variant the tiles stand in the tuner's trial order
+// (the order decides ties).
+struct GemmRow { GemmInst inst; void (*launch)(const WgGemmArgs&, hipStream_t); };
+template <int V, int BM, int BN, int NBUF, int PRE>
+constexpr GemmRow gemm_row() {
+  static_assert((V == 0) == (NBUF != 0) && (V == 3 || PRE == 0), "nbuf belongs to variant 0, pre to variant 3");
+  return {{V, BM, BN, NBUF, PRE}, launch_gemm_inst<V, BM, BN, NBUF, PRE>};
+}
+static const GemmRow kGemmInsts[] = {
+    // 16-row forms, split-limb (3) and f32 (2): row tiles of 80 (5 MFMA tiles), 48, 112 and 208 rows (e.g. the 200
+    // rows of an F(5x5) layer at 8 views).  256 columns: four times the MFMA work per block between its prologue and
+    // its epilogue, a tuner candidate where N % 256 == 0 (none for 208 rows: 208 accumulators).
+    gemm_row<3, 80, 256, 0, 0>(), gemm_row<3, 80, 256, 0, 1>(),
+    gemm_row<3, 80, 128, 0, 0>(), gemm_row<3, 80, 128, 0, 1>(),
+    gemm_row<3, 80, 64, 0, 0>(), gemm_row<3, 80, 64, 0, 1>(),
+    gemm_row<3, 48, 256, 0, 0>(), gemm_row<3, 48, 256, 0, 1>(),
+    gemm_row<3, 48, 128, 0, 0>(), gemm_row<3, 48, 128, 0, 1>(),
+    gemm_row<3, 48, 64, 0, 0>(), gemm_row<3, 48, 64, 0, 1>(),
+    gemm_row<3, 112, 256, 0, 0>(), gemm_row<3, 112, 256, 0, 1>(),
+    gemm_row<3, 112, 128, 0, 0>(), gemm_row<3, 112, 128, 0, 1>(),
+    gemm_row<3, 112, 64, 0, 0>(), gemm_row<3, 112, 64, 0, 1>(),
+    gemm_row<3, 208, 128, 0, 0>(), gemm_row<3, 208, 128, 0, 1>(),
+    gemm_row<3, 208, 64, 0, 0>(), gemm_row<3, 208, 64, 0, 1>(),
+    gemm_row<2, 80, 256, 0, 0>(), gemm_row<2, 80, 128, 0, 0>(), gemm_row<2, 80, 64, 0, 0>(),
+    gemm_row<2, 48, 256, 0, 0>(), gemm_row<2, 48, 128, 0, 0>(), gemm_row<2, 48, 64, 0, 0>(),
+    gemm_row<2, 112, 256, 0, 0>(), gemm_row<2, 112, 128, 0, 0>(), gemm_row<2, 112, 64, 0, 0>(),
+    gemm_row<2, 208, 128, 0, 0>(), gemm_row<2, 208, 64, 0, 0>(),
+    // 32-row forms: register-B (1) and LDS-B (0, single or double LDS buffer), 64- or 128-row, 64- or 128-column tiles
+    gemm_row<1, 64, 64, 0, 0>(), gemm_row<1, 64, 128, 0, 0>(), gemm_row<1, 128, 64, 0, 0>(), gemm_row<1, 128, 128, 0, 0>(),
+    gemm_row<0, 64, 64, 1, 0>(), gemm_row<0, 64, 64, 2, 0>(),
+    gemm_row<0, 64, 128, 1, 0>(), gemm_row<0, 64, 128, 2, 0>(),
+    gemm_row<0, 128, 64, 1, 0>(), gemm_row<0, 128, 64, 2, 0>(),
+    gemm_row<0, 128, 128, 1, 0>(), gemm_row<0, 128, 128, 2, 0>(),
+};
+
+// the row of instance g in kGemmInsts, -1 if g names no instance
+static int gemm_inst_index(const GemmInst& g) {
+  for (int i = 0; i < (int)std::size(kGemmInsts); ++i) {
+    const GemmInst& r = kGemmInsts[i].inst;
+    if (r.variant == g.variant && r.bm == g.bm && r.bn == g.bn && r.nbuf == g.nbuf && r.pre == g.pre) return i;
+  }
+  return -1;
+}
+
+// f(bm, bn) for every tile of `variant` in table order, once per tile whatever its nbuf / pre
+template <typename F>
+static void for_each_gemm_tile(int variant, F f) {
+  const GemmInst* prev = nullptr;
+  for (const GemmRow& row : kGemmInsts) {
+    const GemmInst& g = row.inst;
+    if (g.variant == variant && !(prev && prev->variant == variant && prev->bm == g.bm && prev->bn == g.bn)) f(g.bm, g.bn);
+    prev = &g;
+  }
+}
+
+static bool rb16_rows_ok(int bm) {
+  bool ok = false;
+  for_each_gemm_tile(2, [&](int tbm, int) { ok = ok || tbm == bm; });
+  return ok;
+}
+// rows the 16-row form executes with row tile bm: the 80- and 48-row blocks run only the 16-row tiles that exist (their
+// last block is ragged), the taller ones keep whole zero-padded blocks
+static int64_t rb16_rows_executed(int64_t T, int bm) { return bm <= 80 ? (T + 15) / 16 * 16 : (T + bm - 1) / bm * bm; }
+static int64_t rb16_best_rows(int64_t T, int* bm_out) {
+  int64_t best = -1;
+  for_each_gemm_tile(2, [&](int bm, int) {
+    const int64_t p = rb16_rows_executed(T, bm);
+    if (best < 0 || p < best) { best = p; *bm_out = bm; }
+  });
+  return best;
+}
+
+// Launches tile (bm, bn) of `variant` after the fallbacks below and returns the instance that ran (a row of kGemmInsts
+// for every bn of 64, 128 or 256).  force_nbuf (1 | 2) / force_pre (0 | 1): nfs_gemm_force's choice instead of the
+// rules below (0 / -1: the rules).
+static GemmInst launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s, int variant = 0, int force_nbuf = 0,
+                                 int force_pre = -1) {
+  static const int64_t pre_rows = [] { const char* e = getenv("NFS_RB16S_PRE_ROWS"); return e ? atoll(e) : (int64_t)NFS_RB16S_PRE_ROWS; }();
 #ifdef NFS_ABLATE
+  a.prof = g_gemm_prof;
   // timing-only ablations, -DNFS_ABLATE builds only (wrong results by construction): 1 no MFMA / operand reads, 2 no
   // stores of C, 4 no global loads after the first chunk, 8 no LDS staging, 16 no barrier in the K loop
   static const int dbg = getenv("NFS_GEMM_DBG") ? atoi(getenv("NFS_GEMM_DBG")) : 0;
@@ -1631,67 +1640,34 @@ static void launch_gemm_tile(WgGemmArgs a, int Z, int bm, int bn, hipStream_t s,
   // (a split-limb choice that meets a launch with a mask / scale / symmetric operand runs the same tile on the f32-input
   // MFMA: never the generic kernel with the 16-row form's tile height)
   if (variant == 3 && (a.mask || a.alpha_dev || a.alpha != 1.f || a.symb)) variant = 2;
-  if (variant == 3 && gemm_rb16_applies(a) && rb16_rows_ok(bm) && a.N % bn == 0) {
-    // the 16-row register-B form in split-limb arithmetic (mode 1): 64- or 128-column tiles
-    a.mt = (int)((a.T + bm - 1) / bm);
-    if (bn > 128 && bm == 208) { bn = 128; a.nt = a.N / 128; }
-    int p = force_pre;
-    if (bm == 80) { if (bn == 256) p = launch_gemm_rb16s<5, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<5, 2>(a, s, p); else p = launch_gemm_rb16s<5, 1>(a, s, p); }
-    else if (bm == 48) { if (bn == 256) p = launch_gemm_rb16s<3, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<3, 2>(a, s, p); else p = launch_gemm_rb16s<3, 1>(a, s, p); }
-    else if (bm == 112) { if (bn == 256) p = launch_gemm_rb16s<7, 4>(a, s, p); else if (bn == 128) p = launch_gemm_rb16s<7, 2>(a, s, p); else p = launch_gemm_rb16s<7, 1>(a, s, p); }
-    else { if (bn == 128) p = launch_gemm_rb16s<13, 2>(a, s, p); else p = launch_gemm_rb16s<13, 1>(a, s, p); }
-    r = GemmInst{3, bm, bn == 256 || bn == 128 ? bn : 64, 0, p};
-    return;
-  }
-  if (variant == 2 && gemm_rb16_applies(a) && rb16_rows_ok(bm) && a.N % bn == 0) {
-    a.mt = (int)((a.T + bm - 1) / bm);
-    // (256-column tiles for the 80- / 48- / 112-row forms: four times the MFMA work per block between its prologue
-    // and its epilogue; a tuner candidate where N % 256 == 0)
-    if (bm == 80) { if (bn == 256) launch_gemm_rb16<5, 4>(a, s); else if (bn == 128) launch_gemm_rb16<5, 2>(a, s); else launch_gemm_rb16<5, 1>(a, s); }
-    else if (bm == 48) { if (bn == 256) launch_gemm_rb16<3, 4>(a, s); else if (bn == 128) launch_gemm_rb16<3, 2>(a, s); else launch_gemm_rb16<3, 1>(a, s); }
-    else if (bm == 112) { if (bn == 256) launch_gemm_rb16<7, 4>(a, s); else if (bn == 128) launch_gemm_rb16<7, 2>(a, s); else launch_gemm_rb16<7, 1>(a, s); }
-    else {
-      if (bn == 256) { bn = 128; a.nt = a.N / 128; }          // (no 256-column instance of the 208-row form: 208 accumulators)
-      if (bn == 128) launch_gemm_rb16<13, 2>(a, s); else launch_gemm_rb16<13, 1>(a, s);
-    }
-    r = GemmInst{2, bm, bn == 256 || bn == 128 ? bn : 64, 0, 0};
-    return;
-  }
-  // (the 32-row kernels: 128- or 64-row, 128- or 64-column tiles, the grid counted for the tile that runs)
-  bm = bm == 128 ? 128 : 64;
-  bn = bn == 128 ? 128 : 64;
-  a.mt = (int)((a.T + bm - 1) / bm);
-  a.nt = a.N / bn;
-  if (variant == 1 && gemm_rb_applies(a)) {
-    if (bm == 128 && bn == 128) launch_gemm_rb<128, 128>(a, s);
-    else if (bm == 128) launch_gemm_rb<128, 64>(a, s);
-    else if (bn == 128) launch_gemm_rb<64, 128>(a, s);
-    else launch_gemm_rb<64, 64>(a, s);
-    r = GemmInst{1, bm, bn, 0, 0};
-    return;
-  }
-  // K = 64 (two chunks): nothing to double-buffer; a single LDS buffer doubles the co-resident blocks of this
-  // bandwidth-bound shape (conv1_2: 0.103 -> 0.093 ms)
-  const bool two = force_nbuf ? force_nbuf == 2 : nbuf == 2 && (a.K > 64 || nbuf_env == 2);
-  r = GemmInst{0, bm, bn, two ? 2 : 1, 0};
-  if (two) {
-    if (bm == 128 && bn == 128) launch_gemm_variant<128, 128, 2>(a, s);
-    else if (bm == 128) launch_gemm_variant<128, 64, 2>(a, s);
-    else if (bn == 128) launch_gemm_variant<64, 128, 2>(a, s);
-    else launch_gemm_variant<64, 64, 2>(a, s);
+  GemmInst r;
+  if (variant >= 2 && gemm_rb16_applies(a) && rb16_rows_ok(bm) && a.N % bn == 0) {
+    // the 16-row register-B form, f32 (2) or split-limb (3); B of the split-limb form as NFS_RB16S_PRE_ROWS (above) or
+    // nfs_gemm_force says
+    if (bm == 208 && bn == 256) bn = 128;          // (no 256-column instance of the 208-row form)
+    const bool pre = variant == 3 && NFS_RB16S_PRE && a.Ub16 && (force_pre < 0 ? a.T >= pre_rows : force_pre == 1);
+    r = GemmInst{variant, bm, bn, 0, pre ? 1 : 0};
   } else {
-    if (bm == 128 && bn == 128) launch_gemm_variant<128, 128, 1>(a, s);
-    else if (bm == 128) launch_gemm_variant<128, 64, 1>(a, s);
-    else if (bn == 128) launch_gemm_variant<64, 128, 1>(a, s);
-    else launch_gemm_variant<64, 64, 1>(a, s);
+    // (the 32-row kernels: 128- or 64-row, 128- or 64-column tiles, the grid counted for the tile that runs)
+    bm = bm == 128 ? 128 : 64;
+    bn = bn == 128 ? 128 : 64;
+    // K = 64 (two chunks): nothing to double-buffer; a single LDS buffer doubles the co-resident blocks of this
+    // bandwidth-bound shape (conv1_2: 0.103 -> 0.093 ms)
+    const bool two = force_nbuf ? force_nbuf == 2 : a.K > 64;
+    r = variant == 1 && gemm_rb_applies(a) ? GemmInst{1, bm, bn, 0, 0} : GemmInst{0, bm, bn, two ? 2 : 1, 0};
   }
+  a.mt = (int)((a.T + r.bm - 1) / r.bm);
+  a.nt = a.N / r.bn;
+  a.Z = Z;
+  kGemmInsts[gemm_inst_index(r)].launch(a, s);
+  return r;
 }
 
 // Tile shape per problem: the planner's model (pick_gemm_tile) misses by up to 15 % on single layers (it knows nothing
 // about L2 behaviour), so the first launch of every (T, K, N, Z, arithmetic) shape times the four candidates on the
 // device (two runs each, HIP events, the launch's own operands -- every candidate computes the identical result, the
 // k order does not depend on the tile shape) and the fastest is remembered for the process.  Not while a stream
-// capture is in progress, not while the GEMM timer brackets launches, and not with NFS_GEMM_BM / BN / NFS_GEMM_TUNE=0.
+// capture is in progress, not while the GEMM timer brackets launches, and not with NFS_GEMM_TUNE=0.
 struct GemmKey {
   int64_t T; int K, N, Z, mode;
   bool operator<(const GemmKey& o) const {
@@ -1701,9 +1677,8 @@ struct GemmKey {
 static std::map<GemmKey, std::tuple<int, int, int>> g_tile_cache;   // (BM, BN, kernel variant: 0 LDS-B, 1 register-B)
 static std::mutex g_tile_mu;
 
-// Test hook (nfs_gemm_force / nfs_gemm_last).  The forced instance, packed so that a launch reads it with one atomic
-// load: -1 off, else variant | bm << 4 | bn << 16 | nbuf << 28 | pre << 32.
-static std::atomic<long long> g_gemm_force{-1};
+// Test hook (nfs_gemm_force / nfs_gemm_last).  The forced instance: its row of kGemmInsts, -1 off.
+static std::atomic<int> g_gemm_force{-1};
 // the most recent launch (under g_tile_mu): variant, bm, bn, nbuf, pre, ksplit, T, K, N, Z, trialled
 static long long g_gemm_last[11] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static void record_gemm_locked(const GemmInst& r, const WgGemmArgs& a, int Z, int trialled) {
@@ -1713,70 +1688,49 @@ static void record_gemm_locked(const GemmInst& r, const WgGemmArgs& a, int Z, in
 }
 
 int winograd_ksplit(int64_t T, int K) {
-  static const int forced = [] { const char* e = getenv("NFS_GEMM_KSPLIT"); return e ? atoi(e) : 0; }();
-  static const int tmax = [] { const char* e = getenv("NFS_GEMM_KSPLIT_T"); return e ? atoi(e) : 64; }();
-  static const int kmin = [] { const char* e = getenv("NFS_GEMM_KSPLIT_K"); return e ? atoi(e) : 512; }();
-  int ks = forced > 0 ? (forced > 2 ? 2 : forced) : (T <= tmax && K >= kmin ? 2 : 1);    // (the output transforms sum 1 or 2)
-  while (ks > 1 && (K / WG_KC) % ks) ks >>= 1;
-  return ks < 1 ? 1 : ks;
+  return T <= 64 && K >= 512 && (K / WG_KC) % 2 == 0 ? 2 : 1;    // (the output transforms sum 1 or 2)
 }
 
 static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
-  static const bool tune = [] {
-    const char* e = getenv("NFS_GEMM_TUNE");
-    return !(e && atoi(e) == 0) && !getenv("NFS_GEMM_BM") && !getenv("NFS_GEMM_BN");
-  }();
-  // NFS_GEMM_RB=2 (with NFS_GEMM_BM / BN or NFS_GEMM_TUNE=0): always the register-B kernel where it applies (tests)
-  // NFS_GEMM_RB=3 NFS_GEMM_BM=80|48 NFS_GEMM_BN=128|64: always the 16-row form
-  static const int force_rb = [] { const char* e = getenv("NFS_GEMM_RB"); const int v = e ? atoi(e) : 0; return v == 2 ? 1 : v == 3 ? 2 : 0; }();
-  int bm, bn, variant = force_rb;
+  static const bool tune = [] { const char* e = getenv("NFS_GEMM_TUNE"); return !(e && atoi(e) == 0); }();
+  int bm, bn, variant = 0;
   pick_gemm_tile(a.T, a.N, Z, cus, &bm, &bn);
   const int bm32 = bm, bn32 = bn;
   // Which MFMA the GEMM runs on is decided by the shape alone (never by a measurement: the two instructions sum k in
   // different groupings, so their results differ in the last bit): the 16-row form wherever it executes no more rows
-  // than the best 32-row tiling (NFS_GEMM_ROWS16_PCT, default 100: at equal rows it measured 3-5 % faster).  Within a family every candidate computes the identical result, and the tuner
-  // measures.
-  static const int rows16_pct = [] { const char* e = getenv("NFS_GEMM_ROWS16_PCT"); return e ? atoi(e) : 100; }();
+  // than the best 32-row tiling (at equal rows it measured 3-5 % faster).  Within a family every candidate computes the
+  // identical result, and the tuner measures.
   int bm16 = 80;
   const int64_t pad32 = (a.T + 63) / 64 * 64, pad16 = rb16_best_rows(a.T, &bm16);
-  static const bool bm_forced = getenv("NFS_GEMM_BM") != nullptr;
   // mode 1: a plain product takes the split-limb instance of the 16-row form (variant 3); the Gram gradient (mask /
   // scale / symmetric B) stays on the f32-input MFMA
   const bool plain = !a.mask && !a.alpha_dev && a.alpha == 1.f && !a.symb;
   const int mode = g_gemm_mode;
   const int v16 = (mode == 1 && plain) ? 3 : 2;
-  const bool rows16 = gemm_rb16_applies(a) && force_rb != 1 && !bm_forced &&
-                      pad16 * 100 <= pad32 * rows16_pct;
+  const bool rows16 = gemm_rb16_applies(a) && pad16 <= pad32;
   // K parts (winograd_ksplit: by shape alone) only on the 16-row register-B form of a plain product (no mask / scale in
   // the epilogue: those apply to the complete sum)
-  a.ksplit = (rows16 && !a.mask && !a.alpha_dev && a.alpha == 1.f && !a.symb) ? winograd_ksplit(a.T, a.K) : 1;
+  a.ksplit = rows16 && plain ? winograd_ksplit(a.T, a.K) : 1;
   // nfs_gemm_force: one instance, no trial, the tuner's cache untouched.  The K parts stay the shape rule's (the conv
   // workspace is sized by it).  Every instance stays inside M at any T: rows beyond T load as zeros (buffer descriptors /
   // the LDS-B kernel's row guard) and are never stored (m < T in each epilogue); columns need N % bn == 0 -- where that
   // or the 16-row form's applicability fails, the launch takes the 32-row LDS-B kernel on pick_gemm_tile's tile.
-  if (const long long f = g_gemm_force.load(std::memory_order_relaxed); f >= 0) {
-    int fv = (int)(f & 15), fbm = (int)((f >> 4) & 0xfff), fbn = (int)((f >> 16) & 0xfff), fnbuf = (int)((f >> 28) & 15);
-    const int fpre = (int)((f >> 32) & 1);
+  if (const int f = g_gemm_force.load(std::memory_order_relaxed); f >= 0) {
+    const GemmInst& fi = kGemmInsts[f].inst;
+    int fv = fi.variant, fbm = fi.bm, fbn = fi.bn, fnbuf = fi.nbuf;
     if (fv >= 2 && !(a.N % fbn == 0 && gemm_rb16_applies(a))) { fv = 0; fnbuf = 0; fbm = bm32; fbn = bn32; }
     if (fv <= 1 && a.N % fbn) { fbm = bm32; fbn = bn32; }
-    if (fv != 2 && fv != 3) a.ksplit = 1;
-    GemmInst ran;
-    launch_gemm_tile(a, Z, fbm, fbn, s, fv, &ran, fnbuf, fv == 3 ? fpre : -1);
+    if (fv <= 1) a.ksplit = 1;
+    const GemmInst ran = launch_gemm_tile(a, Z, fbm, fbn, s, fv, fnbuf, fv == 3 ? fi.pre : -1);
     std::lock_guard<std::mutex> lk(g_tile_mu);
     record_gemm_locked(ran, a, Z, 0);
     return ran.variant >= 2 ? a.ksplit : 1;
   }
-  if (rows16 && !tune) { variant = v16; bm = bm16; bn = a.N % 128 == 0 ? 128 : 64; }
-  if (force_rb == 2) {
-    static const int fbm = [] { const char* e = getenv("NFS_GEMM_BM"); return e ? atoi(e) : 80; }();
-    static const int fbn = [] { const char* e = getenv("NFS_GEMM_BN"); return e ? atoi(e) : 128; }();
-    if (rb16_rows_ok(fbm) && a.N % fbn == 0 && gemm_rb16_applies(a)) { bm = fbm; bn = fbn; } else variant = 0;
-  }
+  if (rows16) { variant = v16; bm = bm16; bn = a.N % 128 == 0 ? 128 : 64; }   // (untuned, capture / timer: no trial)
   if (tune) {
     // (the arithmetic of a cached choice is part of the key: in mode 1 a plain product runs variant 3, a Gram gradient of
     // the same (T, K, N, Z) variant 2 -- one must never inherit the other's entry)
     const GemmKey key{a.T, a.K, a.N, Z, mode * 4 + (plain ? 2 : 0) + (a.mask ? 1 : 0)};
-    if (rows16) { variant = v16; bm = bm16; bn = a.N % 128 == 0 ? 128 : 64; }   // (capture / timer: no trial)
     std::unique_lock<std::mutex> lk(g_tile_mu);
     auto it = g_tile_cache.find(key);
     if (it != g_tile_cache.end()) {
@@ -1795,27 +1749,21 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
           for (int rep = 0; rep < 3; ++rep) {
             (void)hipEventRecord(e0, s);
             launch_gemm_tile(a, Z, cbm, cbn, s, var);
-            launch_gemm_tile(a, Z, cbm, cbn, s, var, &ran);
+            ran = launch_gemm_tile(a, Z, cbm, cbn, s, var);
             (void)hipEventRecord(e1, s);
             float ms = 1e30f;
             if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 1e30f;
             if (ms < best) { best = ms; bm = cbm; bn = cbn; variant = var; }
           }
         };
-        if (rows16) {                                                   // 16-row tiles: 80 / 48 rows x 128 / 64 columns
-          for (int i = 0; i < 4; ++i) {                                  // row tiles that pad no worse than 1.2 x the best
-            const int64_t p = rb16_rows_executed(a.T, kRb16Rows[i]);
-            if (p * 10 > pad16 * 12) continue;
-            static const bool bn256 = [] { const char* e = getenv("NFS_GEMM_BN256"); return !(e && atoi(e) == 0); }();
-            for (int cbn = bn256 ? 256 : 128; cbn >= 64; cbn /= 2)
-              if (a.N % cbn == 0 && !(cbn == 256 && kRb16Rows[i] == 208)) trial(kRb16Rows[i], cbn, v16);
-          }
+        if (rows16) {                                                   // 16-row tiles whose rows pad no worse than 1.2 x the best
+          for_each_gemm_tile(v16, [&](int cbm, int cbn) {
+            if (rb16_rows_executed(a.T, cbm) * 10 <= pad16 * 12 && a.N % cbn == 0) trial(cbm, cbn, v16);
+          });
         } else {
-          const int cand[4][2] = {{64, 64}, {64, 128}, {128, 64}, {128, 128}};
           const int nvar = (g_gemm_mode == 0 && gemm_rb_applies(a)) ? 2 : 1;
           for (int var = 0; var < nvar; ++var)
-            for (int c = 0; c < 4; ++c)
-              if (a.N % cand[c][1] == 0) trial(cand[c][0], cand[c][1], var);
+            for_each_gemm_tile(var, [&](int cbm, int cbn) { if (a.N % cbn == 0) trial(cbm, cbn, var); });
         }
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
@@ -1830,8 +1778,7 @@ static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
     }
   }
   if (variant != 2 && variant != 3) a.ksplit = 1;                     // (only the rb16 kernels know about K parts)
-  GemmInst ran;
-  launch_gemm_tile(a, Z, bm, bn, s, variant, &ran);
+  const GemmInst ran = launch_gemm_tile(a, Z, bm, bn, s, variant);
   std::lock_guard<std::mutex> lk(g_tile_mu);
   record_gemm_locked(ran, a, Z, 0);
   return ran.variant >= 2 ? a.ksplit : 1;
@@ -1879,18 +1826,8 @@ int gram_bwd_gemm_group(const float* const* F, const float* const* Dm, float* co
     flops += 2.0 * B * (double)a.T * a.K * a.N;
   }
   G.ustart[n] = ub;
-  constexpr int BMP = 96;
-  const size_t oper = 2 * BMP * WG_LS, tile = 16 * 5 * (64 + 4);
-  const size_t lds = (oper > tile ? oper : tile) * sizeof(float);
-  GemmTimerRec rec{nullptr, nullptr, flops};
-  const bool timed = g_timer_on && hipEventCreate(&rec.e0) == hipSuccess && hipEventCreate(&rec.e1) == hipSuccess;
-  if (timed) (void)hipEventRecord(rec.e0, s);
-  hipLaunchKernelGGL((winograd_gemm_rb16_group_kernel<5, 1>), dim3(ub), dim3(256), lds, s, G);
-  if (timed) {
-    (void)hipEventRecord(rec.e1, s);
-    std::lock_guard<std::mutex> lk(g_timer_mu);
-    g_timer_recs.push_back(rec);
-  }
+  launch_gemm_kernel<winograd_gemm_rb16_group_kernel<5, 1>>(G, gemm_lds_bytes<2, 80, 64, 0>(), ub,
+                                                            GemmTimerRec{nullptr, nullptr, flops}, s);
   return check_launch("gram_bwd_gemm_group");
 }
 
@@ -2053,18 +1990,13 @@ int nfs_gemm_mode(int mode) {
 
 int nfs_gemm_force(int variant, int bm, int bn, int nbuf, int pre) {
   if (variant == -1) { nfs::g_gemm_force.store(-1); return NFS_OK; }
-  const bool b32 = (bm == 64 || bm == 128) && (bn == 64 || bn == 128);
-  const bool b16 = nfs::rb16_rows_ok(bm) && (bn == 64 || bn == 128 || (bn == 256 && bm != 208));
-  const bool ok = (variant == 0 && b32 && (nbuf == 1 || nbuf == 2) && pre == 0) ||
-                  (variant == 1 && b32 && nbuf == 0 && pre == 0) || (variant == 2 && b16 && nbuf == 0 && pre == 0) ||
-                  (variant == 3 && b16 && nbuf == 0 && (pre == 0 || pre == 1));
-  if (!ok) {
+  const int i = nfs::gemm_inst_index({variant, bm, bn, nbuf, pre});
+  if (i < 0) {
     nfs::set_error("nfs_gemm_force: (variant %d, bm %d, bn %d, nbuf %d, pre %d) names no GEMM instance", variant, bm, bn,
                    nbuf, pre);
     return NFS_EINVAL;
   }
-  nfs::g_gemm_force.store((long long)variant | (long long)bm << 4 | (long long)bn << 16 | (long long)nbuf << 28 |
-                          (long long)pre << 32);
+  nfs::g_gemm_force.store(i);
   return NFS_OK;
 }
 

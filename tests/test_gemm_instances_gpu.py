@@ -342,31 +342,34 @@ def test_every_instance_was_launched():
 
 # ---- CPU checks ------------------------------------------------------------------------------------------------------
 
-def _launch_gemm_tile_source():
+def _instance_table():
+    """winograd.hip's source and the rows of its instance table kGemmInsts, in table order"""
     src = open(os.path.join(ROOT, "neural-flow-style_amd", "csrc", "winograd.hip")).read()
-    m = re.search(r"\nstatic void launch_gemm_tile\(.*?\n}\n", src, re.S)
-    assert m, "launch_gemm_tile not found"
-    return src, m.group(0)
+    m = re.search(r"\nstatic const GemmRow kGemmInsts\[\] = \{\n(.*?)\n\};\n", src, re.S)
+    assert m, "kGemmInsts not found"
+    rows = [tuple(int(v) for v in r) for r in re.findall(r"gemm_row<(\d+), (\d+), (\d+), (\d+), (\d+)>\(\)", m.group(1))]
+    return src, rows
 
 
-def test_instance_table_matches_the_dispatcher():
-    """the instances launch_gemm_tile instantiates are exactly INSTANCES: a new one cannot be added without coverage"""
-    src, body = _launch_gemm_tile_source()
-    found = set()
-    for mt, nw in re.findall(r"launch_gemm_rb16s<(\d+), (\d+)>", body):
-        found |= {(3, 16 * int(mt), 64 * int(nw), 0, pre) for pre in (0, 1)}
-    for mt, nw in re.findall(r"launch_gemm_rb16<(\d+), (\d+)>", body):
-        found.add((2, 16 * int(mt), 64 * int(nw), 0, 0))
-    for bm, bn in re.findall(r"launch_gemm_rb<(\d+), (\d+)>", body):
-        found.add((1, int(bm), int(bn), 0, 0))
-    for bm, bn, nbuf in re.findall(r"launch_gemm_variant<(\d+), (\d+), (\d+)>", body):
-        found.add((0, int(bm), int(bn), int(nbuf), 0))
-    assert found == set(INSTANCES), (sorted(found - set(INSTANCES)), sorted(set(INSTANCES) - found))
+def test_dispatch_table_rows_are_exactly_the_instances():
+    """the rows of the dispatcher's instance table (kGemmInsts: what launch_gemm_tile launches, the tuner tries and
+    nfs_gemm_force accepts) are exactly INSTANCES: a new one cannot be added without coverage"""
+    src, rows = _instance_table()
+    assert len(rows) == len(set(rows)), "an instance listed twice"
+    assert set(rows) == set(INSTANCES), (sorted(set(rows) - set(INSTANCES)), sorted(set(INSTANCES) - set(rows)))
     assert len(INSTANCES) == 45
     # both forms of B behind every split-limb tile
-    m = re.search(r"static int launch_gemm_rb16s\(.*?\n}\n", src, re.S)
-    assert m and "launch_gemm_rb16s_pre<MT16, NW16, true>" in m.group(0) and \
-        "launch_gemm_rb16s_pre<MT16, NW16, false>" in m.group(0)
+    for v, bm, bn, _, _ in rows:
+        if v == 3:
+            assert {(3, bm, bn, 0, 0), (3, bm, bn, 0, 1)} <= set(rows), (bm, bn)
+    # nothing launches an instance past the table: on the host side only launch_gemm_inst (a row's launcher) names the
+    # kernels of the instances
+    host = src[src.index("// ---- host side"):]
+    m = re.search(r"\nstatic void launch_gemm_inst\(.*?\n}\n", host, re.S)
+    assert m, "launch_gemm_inst not found"
+    for kernel in ("winograd_gemm_kernel<", "winograd_gemm_rb_kernel<", "winograd_gemm_rb16_kernel<",
+                   "winograd_gemm_rb16s_kernel<"):
+        assert host.count(kernel) == m.group(0).count(kernel) == 1, kernel
 
 
 def test_gemm_force_accepts_exactly_the_instances():

@@ -1,14 +1,18 @@
 """Time of the 16-row register-B GEMM against the number of tiles of a launch (batch sweep at a fixed problem per batch
-entry): the staircase tells the per-round fixed cost from the MFMA work.  Uses nfs_gram_bwd (symmetric B read in place).
-    NFS_GEMM_RB=3 NFS_GEMM_BM=80 NFS_GEMM_BN=64 python tools/gemm_staircase.py [T K]"""
+entry): the staircase tells the per-round fixed cost from the MFMA work.  Uses nfs_gram_bwd (symmetric B read in place)
+on the 16-row f32 instance (2, bm, bn, 0, 0), pinned with the nfs_gemm_force hook.
+    python tools/gemm_staircase.py [T=800 K=256 [bm=80 bn=64]]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import neural_flow_style_amd.ops as ops
+from neural_flow_style_amd import _lib
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 800
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-bm = int(os.environ.get("NFS_GEMM_BM", "80")); bn = int(os.environ.get("NFS_GEMM_BN", "64"))
+bm = int(sys.argv[3]) if len(sys.argv) > 3 else 80
+bn = int(sys.argv[4]) if len(sys.argv) > 4 else 64
+_lib.call("nfs_gemm_force", 2, bm, bn, 0, 0)
 for Z in (4, 8, 16, 24, 32, 40, 49, 56, 64, 80, 98, 128, 196):
     F = torch.randn(Z, T, K, device="cuda")
     D = torch.randn(Z, K, K, device="cuda"); D = D + D.transpose(1, 2)
