@@ -96,7 +96,9 @@ int nfs_warp3d_bwd(const float* imgs, const float* coords, const float* g_out,
  * output-stationary (a block owns a tile of g_d, accumulates in 64-bit fixed point in LDS, no
  * global atomics, bit-reproducible); otherwise it scatters with global float atomics.
  * `g_max` (device, nullable): max |g_out| as produced by nfs_render_bwd(gmax_out) -- the fixed-point scale
- * is derived from it; when NULL a streaming pre-pass over g_out computes it into the workspace.
+ * is derived from it; when NULL a streaming pre-pass over g_out computes it into the workspace.  The scale
+ * allows 4*max(D,H,W) summed weight per view on a voxel when R^T R = I (to 1e-4), D*H*W for any other
+ * matrix: the tiled sums are exact (no wrap) for every matrix, and rotations keep the finer scale.
  * `overwrite` != 0 (tiled adjoint only): g_d = sum over the views instead of +=; the tiles partition the volume, so
  * the caller needs no zero fill and the kernel no read of g_d. */
 int nfs_rotate_fwd(const float* d, const float* rot, float* out,

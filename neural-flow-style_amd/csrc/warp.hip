@@ -515,11 +515,13 @@ constexpr int RT_LZ = RT_TZ + 2, RT_LY = RT_TY + 2, RT_LX = RT_TX + 2;
 constexpr int RT_THREADS = NFS_RT_THREADS;
 constexpr int RT_GROUP = NFS_RT_GROUP;   // lanes that share one lattice row
 constexpr int RT_VMAX = 32;   // views per launch (host loops over chunks)
+static_assert(RT_THREADS / 2 >= RT_VMAX, "the per-view weight check runs on lanes RT_THREADS / 2 + v");
 
 struct ViewRows {             // per (block, view), in LDS
   // voxel-space sample coordinate of axis a at lattice point (oz,oy,ox): c + a0*oz + a1*oy + s*ox
   float a0[3], a1[3], s[3], inv_s[3], c[3];
   float lo[3], hi[3];         // catchment (padded) in voxel space
+  float wextra;               // weight bound of this view beyond the launcher's 4*nmax (0 for a rotation)
   int z_lo, y_lo, x_lo, x_hi, ey, rows;
   unsigned my;                // ceil(2^32 / ey)
 };
@@ -617,6 +619,22 @@ __device__ __forceinline__ void rotate_tile_catchment(const float* r, int D, int
   out->ey = ey;
   out->rows = hi[2] >= lo[2] ? ez * ey : 0;
   out->my = ey > 1 ? 0xFFFFFFFFu / (unsigned)ey + 1u : 0u;     // ceil(2^32 / ey), ey >= 2
+}
+
+// The launcher's fixed-point bound allows 4*nmax summed weight per view on one voxel, which holds for a rotation.  Any
+// other matrix may put more there (a scale clamps a whole corner region onto one voxel, a shrink stacks samples), up to
+// one unit per sample of the view: such a view adds D*H*W.  R^T R is formed from the floats the kernel reads.  (Run by
+// other lanes than the catchment's: inside rotate_tile_catchment it pushes that function into scratch.)
+__device__ __forceinline__ float rotate_view_extra_weight(const float* r, int D, int H, int W) {
+  bool rigid = true;
+#pragma unroll
+  for (int b = 0; b < 3; ++b)
+#pragma unroll
+    for (int c = b; c < 3; ++c) {
+      const double e = (double)r[b] * r[c] + (double)r[3 + b] * r[3 + c] + (double)r[6 + b] * r[6 + c];
+      rigid = rigid && fabs(e - (b == c ? 1.0 : 0.0)) <= 1e-4;
+    }
+  return rigid ? 0.f : (float)((double)D * H * W);
 }
 
 // ---- which tiles, and how much of each, a live-mask launch accumulates ------------------------------------------------
@@ -817,16 +835,22 @@ __global__ void __launch_bounds__(RT_THREADS, 8) rotate_bwd_tiled_kernel(const f
       }
     return;
   }
+  if (t < V) rotate_tile_catchment(rot + t * 9, D, H, W, z0, y0, x0, z1, y1, x1, &vrows[t]);
+  else if (t >= RT_THREADS / 2 && t < RT_THREADS / 2 + V)
+    vrows[t - RT_THREADS / 2].wextra = rotate_view_extra_weight(rot + (t - RT_THREADS / 2) * 9, D, H, W);
+  __syncthreads();
+
+  // bound on the summed weight of any voxel: the launcher's 4*nmax per view + 8, and more for a view that is no rotation
+  // (for rotations this is the launcher's float, so their scale and sums stay what they were)
+  float bf = bound_factor;
+  for (int v = 0; v < V; ++v) bf += vrows[v].wextra;
   int ebound;
-  frexpf(gmax * bound_factor, &ebound);           // gmax*bound_factor < 2^ebound
+  frexpf(gmax * bf, &ebound);                     // gmax*bf < 2^ebound
   const int kexp = 62 - ebound;
   // samples are scaled by 2^(k-32): the integer part of a product is the high word, the fraction the low word
   const int ks = kexp - 32;
   const float fscale = ldexpf(1.f, min(max(ks, -120), 120));
   const float fscale2 = ldexpf(1.f, ks - min(max(ks, -120), 120));  // split: 2^ks may exceed the float range
-
-  if (t < V) rotate_tile_catchment(rot + t * 9, D, H, W, z0, y0, x0, z1, y1, x1, &vrows[t]);
-  __syncthreads();
 
   const int grp = t / RT_GROUP, gl = t % RT_GROUP;
   constexpr int NGRP = RT_THREADS / RT_GROUP;
@@ -1018,8 +1042,9 @@ int nfs_rotate_bwd(const float* g_out, const float* rot, float* g_d_acc, int V, 
       hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, as_stream(stream), g_out, n, wb);
       gmax_bits = wb;
     }
-    // a voxel collects, per view, unit total weight from interior samples and at most ~max(D,H,W)
-    // clamped samples per face direction; 4*nmax per view is a safe bound on the summed weights
+    // a voxel collects, per rotation view, unit total weight from interior samples and at most ~max(D,H,W)
+    // clamped samples per face direction; 4*nmax per view is a safe bound on the summed weights (the kernel
+    // raises it for any view whose matrix is no rotation: rotate_view_extra_weight)
     const int nmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
     const float bound_factor = 4.f * (float)nmax * (float)V + 8.f;
     static const int order = [] { const char* e = getenv("NFS_RT_XCD"); return e ? atoi(e) : 0; }();
