@@ -162,11 +162,88 @@ __device__ __forceinline__ bool corners_differ(const F2u (&p)[4]) {
   return !(p[0].y == a && p[1].x == a && p[1].y == a && p[2].x == a && p[2].y == a && p[3].x == a && p[3].y == a);
 }
 
+struct __attribute__((packed, aligned(4))) F3u { float x, y, z; };
+
+// ---- the lean stencil (advect1_kernel, transport_step_kernel), every piece of it written once ---------------------
+// per-volume constants: (n-1)/2 per axis (velocity -> voxels), n-1 per axis (the clamp), row and plane strides
+struct LeanDims { float hz, hy, hx, nz1, ny1, nx1; unsigned uW, uHW; };
+__device__ __forceinline__ LeanDims lean_dims(int D, int H, int W) {
+  return {0.5f * (float)(D - 1), 0.5f * (float)(H - 1), 0.5f * (float)(W - 1),
+          (float)(D - 1), (float)(H - 1), (float)(W - 1), (unsigned)W, (unsigned)(H * W)};
+}
+
+// back-traced point of voxel (z, h, w): coordinate x = index - vel * (n-1)/2 by one FMA (un-clamped: the gradient asks
+// whether it lies inside), clamped to [0, n-1], base cell min(floor, n-2), weights in [0,1], linear offset of the base cell
+struct LeanCell { float xz, xy, xx, wz, wy, wx; unsigned o; };
+__device__ __forceinline__ LeanCell lean_cell(const F3u& v, int z, int h, int w, const LeanDims& s) {
+  LeanCell c;
+  c.xz = fmaf(-v.x, s.hz, (float)z); c.xy = fmaf(-v.y, s.hy, (float)h); c.xx = fmaf(-v.z, s.hx, (float)w);
+  const float cz = __builtin_amdgcn_fmed3f(c.xz, 0.f, s.nz1), cy = __builtin_amdgcn_fmed3f(c.xy, 0.f, s.ny1),
+              cx = __builtin_amdgcn_fmed3f(c.xx, 0.f, s.nx1);
+  const float bz = fminf(floorf(cz), s.nz1 - 1.f), by = fminf(floorf(cy), s.ny1 - 1.f), bx = fminf(floorf(cx), s.nx1 - 1.f);
+  c.wz = cz - bz; c.wy = cy - by; c.wx = cx - bx;
+  c.o = (unsigned)(int)bz * s.uHW + (unsigned)(int)by * s.uW + (unsigned)(int)bx;
+  return c;
+}
+
+// the four rows (z,y), (z,y+1), (z+1,y), (z+1,y+1) of the cell at offset o, each an (x, x+1) pair of T
+template <typename T>
+__device__ __forceinline__ void lean_gather(const T* d, unsigned o, const LeanDims& s, T (&lo)[4], T (&hi)[4]) {
+  const unsigned r[4] = {o, o + s.uW, o + s.uHW, o + s.uHW + s.uW};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { lo[k] = d[r[k]]; hi[k] = d[r[k] + 1]; }
+}
+// ... of a scalar field: one dword-aligned 8-byte load per row
+__device__ __forceinline__ void lean_gather(const float* d, unsigned o, const LeanDims& s, F2u (&p)[4]) {
+  p[0] = *reinterpret_cast<const F2u*>(d + o);
+  p[1] = *reinterpret_cast<const F2u*>(d + o + s.uW);
+  p[2] = *reinterpret_cast<const F2u*>(d + o + s.uHW);
+  p[3] = *reinterpret_cast<const F2u*>(d + o + s.uHW + s.uW);
+}
+
+// trilinear combine: x within each row (e: the row's difference, a: its value at wx), then y, then z
+__device__ __forceinline__ void lean_rows(const F2u (&p)[4], float wx, float (&e)[4], float (&a)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { e[k] = p[k].y - p[k].x; a[k] = fmaf(wx, e[k], p[k].x); }
+}
+__device__ __forceinline__ float lean_sample(const F2u (&p)[4], float wx, float wy, float wz) {
+  float e[4], a[4];
+  lean_rows(p, wx, e, a);
+  const float b0 = fmaf(wy, a[1] - a[0], a[0]), b1 = fmaf(wy, a[3] - a[2], a[2]);
+  return fmaf(wz, b1 - b0, b0);
+}
+
+// next voxel of this lane: 64 further on (clamped at the end of the volume; those results are not stored)
+__device__ __forceinline__ void walk64(int& w, int& h, int& z, int W, int H, int zlast) {
+  w += 64;
+  while (w >= W) { w -= W; if (++h == H) { h = 0; if (z < zlast) ++z; } }
+}
+
+// A wave owns NV x 64 consecutive voxels and lane l takes l, l + 64, ...: every streamed access (12-byte velocity /
+// moment vectors, g_out, out) is then one contiguous run per instruction.  (Consecutive voxels per lane with float4
+// accesses put the lanes 48 bytes apart: 24 cache lines per instruction, a third of each used.)
+// XCD_ORDER: contiguous z-slab per XCD (workgroups are dealt round-robin to the 8 XCDs; the grid is a multiple of 8): the
+// gathered planes of neighbouring rows then come through one L2 instead of being fetched into all eight.
+// Returns the lane's first voxel; the wave has none when first - lane >= n.  (block_threads: blockDim.x, read by the kernel
+// itself -- only there does the compiler fold it to the launch's uniform block size.)
+template <int NV, bool XCD_ORDER>
+__device__ __forceinline__ int lane_first(unsigned block_threads, int lane) {
+  const unsigned per_xcd = gridDim.x / 8;
+  const unsigned lb = XCD_ORDER ? (blockIdx.x % 8) * per_xcd + blockIdx.x / 8 : blockIdx.x;
+  return (lb * block_threads + (threadIdx.x - lane)) * NV + lane;
+}
+// ... and its position (z, h, w), clamped into the volume; walk64 steps on from there
+__device__ __forceinline__ void lane_start(int first, int n, int H, int W, int& w, int& h, int& z) {
+  const int f0 = min(first, n - 1);
+  w = f0 % W;
+  const int t2 = f0 / W;
+  h = t2 % H; z = t2 / H;
+}
+
+
 // MODE 0: forward; 1: velocity gradient -> out; 2: velocity gradient consumed on the spot by the TF-Adam update of
 // the velocity itself (vel, m, v updated in place: every thread reads and writes only its own 4 voxels of them;
 // the 96 MB gradient never goes to HBM)
-struct __attribute__((packed, aligned(4))) F3u { float x, y, z; };
-
 // Slab form (zoff, Dfull): vel / g_out / out / the moments hold only the D planes [zoff, zoff + D) of a volume of Dfull
 // planes, d is the WHOLE density (the back-traced points leave the slab); zoff = 0, Dfull = D is the whole volume.
 // EVER (MODE 2 + LIVE, volumes below 2^31 / 12 voxels): ad.ever is set and the streamed accesses are predicated per lane
@@ -176,18 +253,10 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
                                                       int D, int H, int W, AdamFused ad, int zoff, int Dfull) {
   constexpr bool BWD = MODE != 0;
   const int n = D * H * W;
-  // a wave owns 256 consecutive voxels and lane l takes l, l+64, l+128, l+192: every streamed access (the
-  // 12-byte velocity / moment vectors, g_out, out) is then one contiguous 768- or 256-byte run per instruction.
-  // (Four consecutive voxels per lane with float4 accesses put the lanes 48 bytes apart: 24 cache lines per
-  // instruction, a third of each used.)
-  const int lane = threadIdx.x & 63;
-  // contiguous z-slab per XCD (workgroups are dealt round-robin to the 8 XCDs): the gathered density planes of
-  // neighbouring rows then come through one L2 instead of being fetched into all eight
-  // (not for the fused Adam variant: it is dominated by the streamed moments, and eight distant streams measured
-  // slower than one front, 0.128 vs 0.112 ms)
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = MODE == 2 ? blockIdx.x : (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  const int first = (lb * blockDim.x + (threadIdx.x - lane)) * 4 + lane;
+  // a wave owns 256 consecutive voxels: lane l takes l, l+64, l+128, l+192 (768- or 256-byte runs per instruction).
+  // Per-XCD order not for the fused Adam variant: it is dominated by the streamed moments, and eight distant streams
+  // measured slower than one front, 0.128 vs 0.112 ms.
+  const int lane = threadIdx.x & 63, first = lane_first<4, MODE != 2>(blockDim.x, lane);
   if (first - lane >= n) return;
   [[maybe_unused]] unsigned long long ew[4] = {~0ull, ~0ull, ~0ull, ~0ull};
   if constexpr (MODE == 2 && LIVE) {
@@ -260,13 +329,10 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
       uu[j] = u3[ic];
     }
   }
-  const float hz = 0.5f * (float)(Dfull - 1), hy = 0.5f * (float)(H - 1), hx = 0.5f * (float)(W - 1);
-  const float nz1 = (float)(Dfull - 1), ny1 = (float)(H - 1), nx1 = (float)(W - 1);
-  const unsigned uW = (unsigned)W, uHW = (unsigned)(H * W);
-  const int f0 = min(first, n - 1);
-  int w = f0 % W;
-  const int t2 = f0 / W;
-  int h = t2 % H, z = t2 / H + zoff;
+  const LeanDims dm = lean_dims(Dfull, H, W);
+  int w, h, z;
+  lane_start(first, n, H, W, w, h, z);
+  z += zoff;
   const int zlast = zoff + D - 1;
   F2u p[4][4];
   float wz[4], wy[4], wx[4], mz[4], my[4], mx[4];
@@ -274,34 +340,21 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
   [[maybe_unused]] unsigned ob[4];                    // ... and the base cell of the first sample is remembered
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float xz = fmaf(-vv[j].x, hz, (float)z), xy = fmaf(-vv[j].y, hy, (float)h),
-                xx = fmaf(-vv[j].z, hx, (float)w);
-    const float cz = __builtin_amdgcn_fmed3f(xz, 0.f, nz1), cy = __builtin_amdgcn_fmed3f(xy, 0.f, ny1),
-                cx = __builtin_amdgcn_fmed3f(xx, 0.f, nx1);
-    const float bz = fminf(floorf(cz), nz1 - 1.f), by = fminf(floorf(cy), ny1 - 1.f), bx = fminf(floorf(cx), nx1 - 1.f);
-    wz[j] = cz - bz; wy[j] = cy - by; wx[j] = cx - bx;
+    const LeanCell c = lean_cell(vv[j], z, h, w, dm);
+    wz[j] = c.wz; wy[j] = c.wy; wx[j] = c.wx;
     if (BWD) {   // outside the volume both clipped corners coincide: no dependence on the coordinate
-      mz[j] = (xz >= 0.f && xz < nz1) ? hz : 0.f;
-      my[j] = (xy >= 0.f && xy < ny1) ? hy : 0.f;
-      mx[j] = (xx >= 0.f && xx < nx1) ? hx : 0.f;
+      mz[j] = (c.xz >= 0.f && c.xz < dm.nz1) ? dm.hz : 0.f;
+      my[j] = (c.xy >= 0.f && c.xy < dm.ny1) ? dm.hy : 0.f;
+      mx[j] = (c.xx >= 0.f && c.xx < dm.nx1) ? dm.hx : 0.f;
     }
-    const unsigned o = (unsigned)(int)bz * uHW + (unsigned)(int)by * uW + (unsigned)(int)bx;
-    if (MODE == 2) ob[j] = o;
-    p[j][0] = *reinterpret_cast<const F2u*>(d + o);
-    p[j][1] = *reinterpret_cast<const F2u*>(d + o + uW);
-    p[j][2] = *reinterpret_cast<const F2u*>(d + o + uHW);
-    p[j][3] = *reinterpret_cast<const F2u*>(d + o + uHW + uW);
-    // next voxel of this lane: 64 further on (clamped at the end of the volume; those results are not stored)
-    w += 64;
-    while (w >= W) { w -= W; if (++h == H) { h = 0; if (z < zlast) ++z; } }
+    if (MODE == 2) ob[j] = c.o;
+    lean_gather(d, c.o, dm, p[j]);
+    walk64(w, h, z, W, H, zlast);
   }
   if (!BWD) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float a00 = fmaf(wx[j], p[j][0].y - p[j][0].x, p[j][0].x), a01 = fmaf(wx[j], p[j][1].y - p[j][1].x, p[j][1].x);
-      const float a10 = fmaf(wx[j], p[j][2].y - p[j][2].x, p[j][2].x), a11 = fmaf(wx[j], p[j][3].y - p[j][3].x, p[j][3].x);
-      const float b0 = fmaf(wy[j], a01 - a00, a00), b1 = fmaf(wy[j], a11 - a10, a10);
-      if (ok[j]) out[first + 64 * j] = fmaf(wz[j], b1 - b0, b0);
+      if (ok[j]) out[first + 64 * j] = lean_sample(p[j], wx[j], wy[j], wz[j]);
       if constexpr (LIVE) {
         const unsigned long long lv = __ballot(ok[j] && corners_differ(p[j]));
         if (lane == 0 && first + 64 * j < n) ad.live[(first + 64 * j) >> 6] = lv;
@@ -310,16 +363,14 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float e00 = p[j][0].y - p[j][0].x, e01 = p[j][1].y - p[j][1].x, e10 = p[j][2].y - p[j][2].x,
-                  e11 = p[j][3].y - p[j][3].x;
-      const float a00 = fmaf(wx[j], e00, p[j][0].x), a01 = fmaf(wx[j], e01, p[j][1].x);
-      const float a10 = fmaf(wx[j], e10, p[j][2].x), a11 = fmaf(wx[j], e11, p[j][3].x);
+      float e[4], a[4];
+      lean_rows(p[j], wx[j], e, a);
       // d(sample)/d(coordinate) along each axis: difference of the two faces, interpolated in the other two
-      const float f0 = fmaf(wy[j], e01 - e00, e00), f1 = fmaf(wy[j], e11 - e10, e10);
+      const float f0 = fmaf(wy[j], e[1] - e[0], e[0]), f1 = fmaf(wy[j], e[3] - e[2], e[2]);
       const float dx = fmaf(wz[j], f1 - f0, f0);
-      const float g0 = a01 - a00, g1 = a11 - a10;
+      const float g0 = a[1] - a[0], g1 = a[3] - a[2];
       const float dy = fmaf(wz[j], g1 - g0, g0);
-      const float b0 = fmaf(wy[j], g0, a00), b1 = fmaf(wy[j], g1, a10);
+      const float b0 = fmaf(wy[j], g0, a[0]), b1 = fmaf(wy[j], g1, a[2]);
       const float dz = b1 - b0;
       // coordinate = index - vel * (n-1)/2  =>  d/dvel = -(n-1)/2 * d/dcoordinate (mz/my/mx carry the factor)
       const float gv[3] = {-gg[j] * dz * mz[j], -gg[j] * dy * my[j], -gg[j] * dx * mx[j]};
@@ -350,39 +401,27 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
       }
     }
     if (MODE == 2 && ad.adv_next) {
-      // the next iteration's forward sample from the updated velocity (the same lines as the MODE 0 body above; the
-      // voxel indices are walked again rather than kept: twelve registers more cost the kernel a wave per SIMD)
+      // the next iteration's forward sample from the updated velocity (MODE 0's on it; the voxel indices are walked
+      // again rather than kept: twelve registers more cost the kernel a wave per SIMD)
       w = w0; h = h0; z = z0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float xz = fmaf(-vv[j].x, hz, (float)z), xy = fmaf(-vv[j].y, hy, (float)h), xx = fmaf(-vv[j].z, hx, (float)w);
-        const float cz = __builtin_amdgcn_fmed3f(xz, 0.f, nz1), cy = __builtin_amdgcn_fmed3f(xy, 0.f, ny1),
-                    cx = __builtin_amdgcn_fmed3f(xx, 0.f, nx1);
-        const float bz = fminf(floorf(cz), nz1 - 1.f), by = fminf(floorf(cy), ny1 - 1.f), bx = fminf(floorf(cx), nx1 - 1.f);
-        wz[j] = cz - bz; wy[j] = cy - by; wx[j] = cx - bx;
-        const unsigned o = (unsigned)(int)bz * uHW + (unsigned)(int)by * uW + (unsigned)(int)bx;
+        const LeanCell c = lean_cell(vv[j], z, h, w, dm);
+        wz[j] = c.wz; wy[j] = c.wy; wx[j] = c.wx;
         // One Adam step moves the back-traced point by a fraction of a cell: its base cell is almost always the one the
         // adjoint just gathered, whose eight corners are still in registers -- only the weights change.  The second
         // gather (a further memory round trip in every wave's life: 0.128 -> 0.166 ms when it was unconditional) is
         // taken only by the lanes whose point crossed a cell face.
-        if (o != ob[j]) {
-          p[j][0] = *reinterpret_cast<const F2u*>(d + o);
-          p[j][1] = *reinterpret_cast<const F2u*>(d + o + uW);
-          p[j][2] = *reinterpret_cast<const F2u*>(d + o + uHW);
-          p[j][3] = *reinterpret_cast<const F2u*>(d + o + uHW + uW);
-        }
-        w += 64;
-        while (w >= W) { w -= W; if (++h == H) { h = 0; if (z < zlast) ++z; } }
+        if (c.o != ob[j]) lean_gather(d, c.o, dm, p[j]);
+        walk64(w, h, z, W, H, zlast);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float a00 = fmaf(wx[j], p[j][0].y - p[j][0].x, p[j][0].x), a01 = fmaf(wx[j], p[j][1].y - p[j][1].x, p[j][1].x);
-        const float a10 = fmaf(wx[j], p[j][2].y - p[j][2].x, p[j][2].x), a11 = fmaf(wx[j], p[j][3].y - p[j][3].x, p[j][3].x);
-        const float b0 = fmaf(wy[j], a01 - a00, a00), b1 = fmaf(wy[j], a11 - a10, a10);
+        const float s = lean_sample(p[j], wx[j], wy[j], wz[j]);
         if constexpr (EVER)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, fmaf(wz[j], b1 - b0, b0)), adv_rs,
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s), adv_rs,
                                                 act[j] ? (uint32_t)(first + 64 * j) * 4u : 0x80000000u, 0, 0);
-        else if (ok[j]) ad.adv_next[first + 64 * j] = fmaf(wz[j], b1 - b0, b0);
+        else if (ok[j]) ad.adv_next[first + 64 * j] = s;
         if constexpr (LIVE) {
           const unsigned long long lv = __ballot(ok[j] && (!EVER || act[j]) && corners_differ(p[j]));
           if (lane == 0 && first + 64 * j < n) ad.live[(first + 64 * j) >> 6] = lv;
@@ -408,10 +447,7 @@ __global__ void __launch_bounds__(256) transport_step_kernel(const float* __rest
                                                              int D, int H, int W, float scale, float w_g, float w_add) {
   constexpr int NV = 2;
   const int n = D * H * W;
-  const int lane = threadIdx.x & 63;
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;     // contiguous z-slab per XCD (shared planes)
-  const int first = (lb * blockDim.x + (threadIdx.x - lane)) * NV + lane;
+  const int lane = threadIdx.x & 63, first = lane_first<NV, true>(blockDim.x, lane);
   if (first - lane >= n) return;
   const F3u* u3 = reinterpret_cast<const F3u*>(u);
   const Vec<C>* gC = reinterpret_cast<const Vec<C>*>(g);
@@ -426,36 +462,25 @@ __global__ void __launch_bounds__(256) transport_step_kernel(const float* __rest
     vv[j] = u3[ic];
     if (addend) add[j] = reinterpret_cast<const Vec<C>*>(addend)[ic];
   }
-  const float hz = 0.5f * (float)(D - 1) * scale, hy = 0.5f * (float)(H - 1) * scale, hx = 0.5f * (float)(W - 1) * scale;
-  const float nz1 = (float)(D - 1), ny1 = (float)(H - 1), nx1 = (float)(W - 1);
-  const unsigned uW = (unsigned)W, uHW = (unsigned)(H * W);
-  const int f0 = min(first, n - 1);
-  int w = f0 % W;
-  const int t2 = f0 / W;
-  int h = t2 % H, z = t2 / H;
+  LeanDims dm = lean_dims(D, H, W);
+  dm.hz *= scale; dm.hy *= scale; dm.hx *= scale;     // the back-trace runs along scale * u
+  int w, h, z;
+  lane_start(first, n, H, W, w, h, z);
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
-    const float xz = fmaf(-vv[j].x, hz, (float)z), xy = fmaf(-vv[j].y, hy, (float)h), xx = fmaf(-vv[j].z, hx, (float)w);
-    const float cz = __builtin_amdgcn_fmed3f(xz, 0.f, nz1), cy = __builtin_amdgcn_fmed3f(xy, 0.f, ny1),
-                cx = __builtin_amdgcn_fmed3f(xx, 0.f, nx1);
-    const float bz = fminf(floorf(cz), nz1 - 1.f), by = fminf(floorf(cy), ny1 - 1.f), bx = fminf(floorf(cx), nx1 - 1.f);
-    const float wz = cz - bz, wy = cy - by, wx = cx - bx;
-    const unsigned o = (unsigned)(int)bz * uHW + (unsigned)(int)by * uW + (unsigned)(int)bx;
-    const Vec<C> p00a = gC[o], p00b = gC[o + 1], p01a = gC[o + uW], p01b = gC[o + uW + 1];
-    const Vec<C> p10a = gC[o + uHW], p10b = gC[o + uHW + 1], p11a = gC[o + uHW + uW], p11b = gC[o + uHW + uW + 1];
+    const LeanCell cell = lean_cell(vv[j], z, h, w, dm);
+    Vec<C> lo[4], hi[4];
+    lean_gather(gC, cell.o, dm, lo, hi);
     Vec<C> r;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const float a00 = fmaf(wx, p00b.v[c] - p00a.v[c], p00a.v[c]), a01 = fmaf(wx, p01b.v[c] - p01a.v[c], p01a.v[c]);
-      const float a10 = fmaf(wx, p10b.v[c] - p10a.v[c], p10a.v[c]), a11 = fmaf(wx, p11b.v[c] - p11a.v[c], p11a.v[c]);
-      const float b0 = fmaf(wy, a01 - a00, a00), b1 = fmaf(wy, a11 - a10, a10);
-      float s = w_g * fmaf(wz, b1 - b0, b0);
+      const F2u p[4] = {{lo[0].v[c], hi[0].v[c]}, {lo[1].v[c], hi[1].v[c]}, {lo[2].v[c], hi[2].v[c]}, {lo[3].v[c], hi[3].v[c]}};
+      float s = w_g * lean_sample(p, cell.wx, cell.wy, cell.wz);
       if (addend) s = fmaf(w_add, add[j].v[c], s);
       r.v[c] = s;
     }
     if (ok[j]) reinterpret_cast<Vec<C>*>(out)[first + 64 * j] = r;
-    w += 64;
-    while (w >= W) { w -= W; if (++h == H) { h = 0; if (z < D - 1) ++z; } }
+    walk64(w, h, z, W, H, D - 1);
   }
 }
 
@@ -990,6 +1015,68 @@ static int check_dims(int B, int X, int Y, int Z, int C) {
   return NFS_OK;
 }
 
+// ---- the one launch path of rotate_bwd_tiled_kernel -------------------------------------------------------------------
+// src: g_out [V,D,H,W], or with COEF (ab set: per-(view, segment, ray) coefficients) the render's u volume; scale_bits:
+// max |sample gradient| (COEF: nbounds per-block bounds on it); live + lws (COEF, nullable): the tiles' live boxes are
+// formed first and the blocks take the tiles by that order
+static void rotate_bwd_tiled_launch(const float* src, const float* rot, float* g_d, const unsigned* scale_bits, int V,
+                                    int D, int H, int W, int overwrite, const float2* ab, int nseg, int seg_len,
+                                    int nbounds, const unsigned long long* live, int dilate, int* lws, hipStream_t s) {
+  const int tz = (D + RT_TZ - 1) / RT_TZ, ty = (H + RT_TY - 1) / RT_TY, tx = (W + RT_TX - 1) / RT_TX;
+  // a voxel collects, per rotation view, unit total weight from interior samples and at most ~max(D,H,W)
+  // clamped samples per face direction; 4*nmax per view is a safe bound on the summed weights (the kernel
+  // raises it for any view whose matrix is no rotation: rotate_view_extra_weight)
+  const int nmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
+  const float bound_factor = 4.f * (float)nmax * (float)V + 8.f;
+  static const int order = [] { const char* e = getenv("NFS_RT_XCD"); return e ? atoi(e) : 0; }();
+  const int grid = (live || order == 0) ? tz * ty * tx : 8 * ((tz * ty + 7) / 8) * tx;
+  if (live) {
+    hipLaunchKernelGGL(rotate_live_boxes_kernel, dim3((tz * ty * tx + LB_WAVES - 1) / LB_WAVES), dim3(LB_THREADS), 0, s,
+                       live, D, H, W, ty, tx, dilate, tz * ty * tx, lws);
+    hipLaunchKernelGGL(rotate_live_order_kernel, dim3(1), dim3(LB_THREADS), 0, s, tz * ty * tx, lws);
+  }
+  const auto kernel = ab ? rotate_bwd_tiled_kernel<true> : rotate_bwd_tiled_kernel<false>;
+  for (int v0 = 0; v0 < V; v0 += RT_VMAX) {
+    const int vn = V - v0 < RT_VMAX ? V - v0 : RT_VMAX;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_THREADS), 0, s, src + (int64_t)v0 * D * H * W, rot + v0 * 9, g_d,
+                       scale_bits, bound_factor, vn, D, H, W, ty, tx, (overwrite && v0 == 0) ? 1 : 0, order,
+                       ab ? ab + (int64_t)v0 * nseg * H * W : ab, nseg, seg_len, nbounds, live ? (const int*)lws : nullptr);
+  }
+}
+
+// ---- the one launch path of advect1_kernel -----------------------------------------------------------------------------
+// the shapes it takes: nz planes of a [D,H,W] volume (nz = D: all of it)
+static bool advect1_takes(int D, int H, int W, int nz) {
+  return W >= 2 && H >= 2 && D >= 2 && (int64_t)nz * H * W % 4 == 0 && (int64_t)D * H * W < ((int64_t)1 << 30);
+}
+
+// mode: advect1_kernel's MODE; LIVE follows ad.live, EVER ad.ever (and NFS_EVER_LANES); the planes [z0, z0 + nz) of the
+// volume (vel / g_out / out / the moments hold those only; z0 = 0, nz = D: the whole-volume forms).  The callers have
+// checked their pointers for null.
+static int advect1_launch(const char* who, int mode, const float* d, const float* vel, const float* g_out, float* out,
+                          int D, int H, int W, int z0, int nz, const AdamFused& ad, nfs_stream_t stream) {
+  NFS_REQUIRE(!ad.adv_next || (ad.adv_next != d && ad.adv_next != g_out), "%s: adv_next must not alias d or g_out", who);
+  if (int e = check_dims(1, D, H, W, 1)) return e;
+  NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "%s: slab outside the volume", who);
+  NFS_REQUIRE(advect1_takes(D, H, W, nz),
+              "%s: needs D, H, W >= 2, D*H*W < 2^30 and a multiple of 4 voxels (nz*H*W for a slab)", who);
+  const int64_t n = (int64_t)nz * H * W;
+  auto kernel = ad.live ? advect1_kernel<0, true> : advect1_kernel<0>;
+  if (mode == 1) {
+    kernel = advect1_kernel<1>;
+  } else if (mode == 2 && !ad.live) {
+    kernel = advect1_kernel<2>;
+  } else if (mode == 2) {
+    // (per-lane predication goes through buffer descriptors: 32-bit byte offsets, 12 n < 2^31; larger volumes skip by waves only)
+    static const bool lanes = [] { const char* e = getenv("NFS_EVER_LANES"); return !(e && atoi(e) == 0); }();
+    kernel = (ad.ever && lanes && n * 12 < ((int64_t)1 << 31)) ? advect1_kernel<2, true, true> : advect1_kernel<2, true>;
+  }
+  // 256 threads x 4 voxels; whole rounds of the 8 XCDs
+  hipLaunchKernelGGL(kernel, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out, out,
+                     nz, H, W, ad, z0, D);
+  return check_launch(who);
+}
+
 }  // namespace nfs
 
 using namespace nfs;
@@ -1033,7 +1120,6 @@ int nfs_rotate_bwd(const float* g_out, const float* rot, float* g_d_acc, int V, 
   NFS_REQUIRE(g_out && rot && g_d_acc, "nfs_rotate_bwd: null pointer");
   if (int e = check_dims(V, D, H, W, C)) return e;
   if (C == 1 && workspace) {
-    const int tz = (D + RT_TZ - 1) / RT_TZ, ty = (H + RT_TY - 1) / RT_TY, tx = (W + RT_TX - 1) / RT_TX;
     const unsigned* gmax_bits = reinterpret_cast<const unsigned*>(g_max);
     if (!gmax_bits) {                       // no max |g_out| supplied: streaming pre-pass
       unsigned* wb = reinterpret_cast<unsigned*>(workspace);
@@ -1042,20 +1128,8 @@ int nfs_rotate_bwd(const float* g_out, const float* rot, float* g_d_acc, int V, 
       hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, as_stream(stream), g_out, n, wb);
       gmax_bits = wb;
     }
-    // a voxel collects, per rotation view, unit total weight from interior samples and at most ~max(D,H,W)
-    // clamped samples per face direction; 4*nmax per view is a safe bound on the summed weights (the kernel
-    // raises it for any view whose matrix is no rotation: rotate_view_extra_weight)
-    const int nmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
-    const float bound_factor = 4.f * (float)nmax * (float)V + 8.f;
-    static const int order = [] { const char* e = getenv("NFS_RT_XCD"); return e ? atoi(e) : 0; }();
-    const int grid = order == 0 ? tz * ty * tx : 8 * ((tz * ty + 7) / 8) * tx;
-    for (int v0 = 0; v0 < V; v0 += RT_VMAX) {
-      const int vn = V - v0 < RT_VMAX ? V - v0 : RT_VMAX;
-      hipLaunchKernelGGL(rotate_bwd_tiled_kernel<false>, dim3(grid), dim3(RT_THREADS), 0, as_stream(stream),
-                         g_out + (int64_t)v0 * D * H * W, rot + v0 * 9, g_d_acc, gmax_bits, bound_factor, vn, D, H, W,
-                         ty, tx, (overwrite && v0 == 0) ? 1 : 0, order, (const float2*)nullptr, 1, D, 0,
-                         (const int*)nullptr);
-    }
+    rotate_bwd_tiled_launch(g_out, rot, g_d_acc, gmax_bits, V, D, H, W, overwrite, nullptr, 1, D, 0, nullptr, 0, nullptr,
+                            as_stream(stream));
     return check_launch("nfs_rotate_bwd(tiled)");
   }
   NFS_REQUIRE(!overwrite, "nfs_rotate_bwd: overwrite needs the tiled adjoint (C == 1 and a workspace)");
@@ -1077,24 +1151,8 @@ static int rotate_bwd_coef_impl(const char* who, const float* u_rot, const float
   if (int e = check_dims(V, D, H, W, 1)) return e;
   NFS_REQUIRE(nseg > 0 && seg_len > 0 && (int64_t)nseg * seg_len >= D, "nfs_rotate_bwd_coef: the segments do not cover D");
   NFS_REQUIRE(!live || (dilate >= 0 && RT_TX + 2 * dilate <= 63), "nfs_rotate_bwd_coef_live: dilate out of range");
-  const int tz = (D + RT_TZ - 1) / RT_TZ, ty = (H + RT_TY - 1) / RT_TY, tx = (W + RT_TX - 1) / RT_TX;
-  const int nmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
-  const float bound_factor = 4.f * (float)nmax * (float)V + 8.f;
-  static const int order = [] { const char* e = getenv("NFS_RT_XCD"); return e ? atoi(e) : 0; }();
-  const int grid = (live || order == 0) ? tz * ty * tx : 8 * ((tz * ty + 7) / 8) * tx;
-  if (live)
-    hipLaunchKernelGGL(rotate_live_boxes_kernel, dim3((tz * ty * tx + LB_WAVES - 1) / LB_WAVES), dim3(LB_THREADS), 0,
-                       as_stream(stream), live, D, H, W, ty, tx, dilate, tz * ty * tx, lws);
-  if (live)
-    hipLaunchKernelGGL(rotate_live_order_kernel, dim3(1), dim3(LB_THREADS), 0, as_stream(stream), tz * ty * tx, lws);
-  for (int v0 = 0; v0 < V; v0 += RT_VMAX) {
-    const int vn = V - v0 < RT_VMAX ? V - v0 : RT_VMAX;
-    hipLaunchKernelGGL(rotate_bwd_tiled_kernel<true>, dim3(grid), dim3(RT_THREADS), 0, as_stream(stream),
-                       u_rot + (int64_t)v0 * D * H * W, rot + v0 * 9, g_d_acc, reinterpret_cast<const unsigned*>(bounds),
-                       bound_factor, vn, D, H, W, ty, tx, (overwrite && v0 == 0) ? 1 : 0, order,
-                       reinterpret_cast<const float2*>(ab) + (int64_t)v0 * nseg * H * W, nseg, seg_len, nbounds,
-                       live ? (const int*)lws : (const int*)nullptr);
-  }
+  rotate_bwd_tiled_launch(u_rot, rot, g_d_acc, reinterpret_cast<const unsigned*>(bounds), V, D, H, W, overwrite,
+                          reinterpret_cast<const float2*>(ab), nseg, seg_len, nbounds, live, dilate, lws, as_stream(stream));
   return check_launch(who);
 }
 
@@ -1135,13 +1193,10 @@ int nfs_live_mask_words(int D, int H, int W) {
 int nfs_advect_fwd(const float* d, const float* vel, float* out, int D, int H, int W, int C, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && out, "nfs_advect_fwd: null pointer");
   if (int e = check_dims(1, D, H, W, C)) return e;
+  if (C == 1 && advect1_takes(D, H, W, D))
+    return advect1_launch("nfs_advect_fwd(x4)", 0, d, vel, nullptr, out, D, H, W, 0, D, AdamFused{}, stream);
   WarpArgs a{d, vel, 1, D, H, W, C, 0};
   const int64_t n = (int64_t)D * H * W;
-  if (C == 1 && W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30)) {
-    hipLaunchKernelGGL(advect1_kernel<0>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel,
-                       (const float*)nullptr, out, D, H, W, AdamFused{}, 0, D);
-    return check_launch("nfs_advect_fwd(x4)");
-  }
   hipLaunchKernelGGL(warp_fwd_kernel<COORD_ADVECT>, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), a, out);
   return check_launch("nfs_advect_fwd");
 }
@@ -1151,15 +1206,9 @@ int nfs_advect_fwd(const float* d, const float* vel, float* out, int D, int H, i
 int nfs_advect_fwd_live(const float* d, const float* vel, float* out, unsigned long long* live, int D, int H, int W,
                         nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && out && live, "nfs_advect_fwd_live: null pointer");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  const int64_t n = (int64_t)D * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30),
-              "nfs_advect_fwd_live: needs D, H, W >= 2 and D*H*W %% 4 == 0");
   AdamFused ad{};
   ad.live = live;
-  hipLaunchKernelGGL((advect1_kernel<0, true>), dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel,
-                     (const float*)nullptr, out, D, H, W, ad, 0, D);
-  return check_launch("nfs_advect_fwd_live");
+  return advect1_launch("nfs_advect_fwd_live", 0, d, vel, nullptr, out, D, H, W, 0, D, ad, stream);
 }
 
 int nfs_advect_bwd(const float* d, const float* vel, const float* g_out, float* g_d_acc, float* g_vel, int D, int H,
@@ -1168,43 +1217,30 @@ int nfs_advect_bwd(const float* d, const float* vel, const float* g_out, float* 
   NFS_REQUIRE(!g_vel || d, "nfs_advect_bwd: g_vel needs d");
   NFS_REQUIRE(g_d_acc || g_vel, "nfs_advect_bwd: nothing to compute");
   if (int e = check_dims(1, D, H, W, C)) return e;
+  if (C == 1 && !g_d_acc && advect1_takes(D, H, W, D))   // velocity gradient only: no atomics
+    return advect1_launch("nfs_advect_bwd(x4)", 1, d, vel, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream);
   WarpArgs a{d, vel, 1, D, H, W, C, 0};
   const int64_t n = (int64_t)D * H * W;
-  if (C == 1 && !g_d_acc && W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30)) {   // velocity gradient only: no atomics
-    hipLaunchKernelGGL(advect1_kernel<1>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel,
-                       g_out, g_vel, D, H, W, AdamFused{}, 0, D);
-    return check_launch("nfs_advect_bwd(x4)");
-  }
   hipLaunchKernelGGL(warp_bwd_kernel<COORD_ADVECT>, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), a,
                      g_out, g_d_acc, g_vel);
   return check_launch("nfs_advect_bwd");
 }
 
-// velocity gradient of advect + TF ApplyAdam on the velocity in one pass (scalar field, C = 1)
+// velocity gradient of advect + TF ApplyAdam on the velocity in one pass (scalar field, C = 1; the shapes the four-voxel
+// kernel does not take: nfs_advect_bwd + nfs_adam_tf_step)
 int nfs_advect_bwd_adam(const float* d, float* vel, const float* g_out, float* m, float* v, int D, int H, int W,
                         float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v, "nfs_advect_bwd_adam: null pointer");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  const int64_t n = (int64_t)D * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam: needs D, H, W >= 2 and D*H*W %% 4 == 0 (use nfs_advect_bwd + nfs_adam_tf_step)");
-  hipLaunchKernelGGL(advect1_kernel<2>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out, vel,
-                     D, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps}, 0, D);
-  return check_launch("nfs_advect_bwd_adam");
+  return advect1_launch("nfs_advect_bwd_adam", 2, d, vel, g_out, vel, D, H, W, 0, D,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps}, stream);
 }
 
 // ... and the NEXT iteration's forward advect of the updated velocity in the same pass (adv_next [D,H,W], see AdamFused)
 int nfs_advect_bwd_adam_fwd(const float* d, float* vel, const float* g_out, float* m, float* v, float* adv_next, int D, int H,
                             int W, float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v && adv_next, "nfs_advect_bwd_adam_fwd: null pointer");
-  NFS_REQUIRE(adv_next != d && adv_next != g_out, "nfs_advect_bwd_adam_fwd: adv_next must not alias d or g_out");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  const int64_t n = (int64_t)D * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam_fwd: needs D, H, W >= 2 and D*H*W %% 4 == 0");
-  hipLaunchKernelGGL(advect1_kernel<2>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out, vel,
-                     D, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next}, 0, D);
-  return check_launch("nfs_advect_bwd_adam_fwd");
+  return advect1_launch("nfs_advect_bwd_adam_fwd", 2, d, vel, g_out, vel, D, H, W, 0, D,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next}, stream);
 }
 
 // ... and the live mask of that next forward sample (for the next iteration's nfs_rotate_bwd_coef_live)
@@ -1212,14 +1248,8 @@ int nfs_advect_bwd_adam_fwd_live(const float* d, float* vel, const float* g_out,
                                  unsigned long long* live_next, int D, int H, int W, float lr_t, float beta1, float beta2,
                                  float eps, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v && adv_next && live_next, "nfs_advect_bwd_adam_fwd_live: null pointer");
-  NFS_REQUIRE(adv_next != d && adv_next != g_out, "nfs_advect_bwd_adam_fwd_live: adv_next must not alias d or g_out");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  const int64_t n = (int64_t)D * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam_fwd_live: needs D, H, W >= 2 and D*H*W %% 4 == 0");
-  hipLaunchKernelGGL((advect1_kernel<2, true>), dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out, vel,
-                     D, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next, live_next}, 0, D);
-  return check_launch("nfs_advect_bwd_adam_fwd_live");
+  return advect1_launch("nfs_advect_bwd_adam_fwd_live", 2, d, vel, g_out, vel, D, H, W, 0, D,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next, live_next}, stream);
 }
 
 // ... skipping the waves whose voxels have never been live (see `ever` in advect1_kernel): `live` holds the mask of the
@@ -1230,20 +1260,8 @@ int nfs_advect_bwd_adam_fwd_live_ever(const float* d, float* vel, const float* g
                                       unsigned long long* live, unsigned long long* ever, int D, int H, int W, float lr_t,
                                       float beta1, float beta2, float eps, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v && adv_next && live && ever, "nfs_advect_bwd_adam_fwd_live_ever: null pointer");
-  NFS_REQUIRE(adv_next != d && adv_next != g_out, "nfs_advect_bwd_adam_fwd_live_ever: adv_next must not alias d or g_out");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  const int64_t n = (int64_t)D * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && n < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam_fwd_live_ever: needs D, H, W >= 2 and D*H*W %% 4 == 0");
-  // (per-lane predication goes through buffer descriptors: 32-bit byte offsets, 12 n < 2^31; larger volumes skip by waves only)
-  static const bool lanes = [] { const char* e = getenv("NFS_EVER_LANES"); return !(e && atoi(e) == 0); }();
-  if (lanes && n * 12 < ((int64_t)1 << 31))
-    hipLaunchKernelGGL((advect1_kernel<2, true, true>), dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel,
-                       g_out, vel, D, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next, live, ever}, 0, D);
-  else
-    hipLaunchKernelGGL((advect1_kernel<2, true>), dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out,
-                       vel, D, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next, live, ever}, 0, D);
-  return check_launch("nfs_advect_bwd_adam_fwd_live_ever");
+  return advect1_launch("nfs_advect_bwd_adam_fwd_live_ever", 2, d, vel, g_out, vel, D, H, W, 0, D,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next, live, ever}, stream);
 }
 
 // Slab forms (view-sharded runs shard the replicated field work over D-slabs, engine.GridStylizer): d is the whole
@@ -1252,42 +1270,22 @@ int nfs_advect_bwd_adam_fwd_live_ever(const float* d, float* vel, const float* g
 int nfs_advect_fwd_slab(const float* d, const float* vel, float* out, int D, int H, int W, int z0, int nz,
                         nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && out, "nfs_advect_fwd_slab: null pointer");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "nfs_advect_fwd_slab: slab outside the volume");
-  const int64_t n = (int64_t)nz * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && (int64_t)D * H * W < ((int64_t)1 << 30),
-              "nfs_advect_fwd_slab: needs D, H, W >= 2 and nz*H*W %% 4 == 0");
-  hipLaunchKernelGGL(advect1_kernel<0>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel,
-                     (const float*)nullptr, out, nz, H, W, AdamFused{}, z0, D);
-  return check_launch("nfs_advect_fwd_slab");
+  return advect1_launch("nfs_advect_fwd_slab", 0, d, vel, nullptr, out, D, H, W, z0, nz, AdamFused{}, stream);
 }
 
 int nfs_advect_bwd_adam_slab(const float* d, float* vel, const float* g_out, float* m, float* v, int D, int H, int W,
                              int z0, int nz, float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v, "nfs_advect_bwd_adam_slab: null pointer");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "nfs_advect_bwd_adam_slab: slab outside the volume");
-  const int64_t n = (int64_t)nz * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && (int64_t)D * H * W < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam_slab: needs D, H, W >= 2 and nz*H*W %% 4 == 0");
-  hipLaunchKernelGGL(advect1_kernel<2>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out,
-                     vel, nz, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps}, z0, D);
-  return check_launch("nfs_advect_bwd_adam_slab");
+  return advect1_launch("nfs_advect_bwd_adam_slab", 2, d, vel, g_out, vel, D, H, W, z0, nz,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps}, stream);
 }
 
 int nfs_advect_bwd_adam_fwd_slab(const float* d, float* vel, const float* g_out, float* m, float* v, float* adv_next, int D,
                                  int H, int W, int z0, int nz, float lr_t, float beta1, float beta2, float eps,
                                  nfs_stream_t stream) {
   NFS_REQUIRE(d && vel && g_out && m && v && adv_next, "nfs_advect_bwd_adam_fwd_slab: null pointer");
-  NFS_REQUIRE(adv_next != d && adv_next != g_out, "nfs_advect_bwd_adam_fwd_slab: adv_next must not alias d or g_out");
-  if (int e = check_dims(1, D, H, W, 1)) return e;
-  NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "nfs_advect_bwd_adam_fwd_slab: slab outside the volume");
-  const int64_t n = (int64_t)nz * H * W;
-  NFS_REQUIRE(W >= 2 && H >= 2 && D >= 2 && n % 4 == 0 && (int64_t)D * H * W < ((int64_t)1 << 30),
-              "nfs_advect_bwd_adam_fwd_slab: needs D, H, W >= 2 and nz*H*W %% 4 == 0");
-  hipLaunchKernelGGL(advect1_kernel<2>, dim3((blocks_for(n, 1024) + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, vel, g_out,
-                     vel, nz, H, W, AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next}, z0, D);
-  return check_launch("nfs_advect_bwd_adam_fwd_slab");
+  return advect1_launch("nfs_advect_bwd_adam_fwd_slab", 2, d, vel, g_out, vel, D, H, W, z0, nz,
+                        AdamFused{m, v, lr_t, beta1, beta2, eps, adv_next}, stream);
 }
 
 // one step of StylerBase._transport (styler_base.py:59-89) with the temporal filter's weighted accumulation fused in

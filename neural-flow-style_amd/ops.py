@@ -144,23 +144,21 @@ def advect_bwd_adam(d, vel, g_out, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8,
     were zeroed -- waves of voxels that never were live are left out altogether (ApplyAdam is an exact no-op there)"""
     D, H, W, Cn = d.shape
     assert Cn == 1
-    if adv_next is not None and live_next is not None and ever is not None:
-        assert adv_next.is_contiguous() and adv_next.numel() == D * H * W and ever.numel() == live_next.numel()
-        _lib.call("nfs_advect_bwd_adam_fwd_live_ever", _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), _ptr(adv_next),
-                  _ptr(live_next), _ptr(ever), D, H, W, float(lr_t), float(beta1), float(beta2), float(eps), _stream())
-        _written(live_next, ever)
-    elif adv_next is not None and live_next is not None:
+    # each optional buffer that is present (in this order; one that is absent ends the list) adds its pointer after v and
+    # its suffix to the entry point's name
+    name, extra = "nfs_advect_bwd_adam", []
+    for suffix, t in (("_fwd", adv_next), ("_live", live_next), ("_ever", ever)):
+        if t is None:
+            break
+        name += suffix
+        extra.append(t)
+    if extra:
         assert adv_next.is_contiguous() and adv_next.numel() == D * H * W
-        _lib.call("nfs_advect_bwd_adam_fwd_live", _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), _ptr(adv_next),
-                  _ptr(live_next), D, H, W, float(lr_t), float(beta1), float(beta2), float(eps), _stream())
-        _written(live_next)
-    elif adv_next is None:
-        _lib.call("nfs_advect_bwd_adam", _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), D, H, W, float(lr_t),
-                  float(beta1), float(beta2), float(eps), _stream())
-    else:
-        assert adv_next.is_contiguous() and adv_next.numel() == D * H * W
-        _lib.call("nfs_advect_bwd_adam_fwd", _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), _ptr(adv_next), D, H, W,
-                  float(lr_t), float(beta1), float(beta2), float(eps), _stream())
+    if len(extra) == 3:
+        assert ever.numel() == live_next.numel()
+    _lib.call(name, _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), *map(_ptr, extra), D, H, W, float(lr_t),
+              float(beta1), float(beta2), float(eps), _stream())
+    _written(*extra[1:])
     _written(vel, m, v, adv_next)
 
 
@@ -179,13 +177,12 @@ def advect_bwd_adam_slab(d, vel_slab, g_slab, m_slab, v_slab, z0, lr_t, beta1=0.
     d is the whole density [D,H,W]; ``adv_next`` [nz,H,W] (optional) as in advect_bwd_adam"""
     D, H, W = d.shape
     nz = vel_slab.shape[0]
-    if adv_next is None:
-        _lib.call("nfs_advect_bwd_adam_slab", _ptr(d), _ptr(vel_slab), _ptr(g_slab), _ptr(m_slab), _ptr(v_slab), D, H, W,
-                  int(z0), nz, float(lr_t), float(beta1), float(beta2), float(eps), _stream())
-    else:
+    extra = [] if adv_next is None else [adv_next]
+    if extra:
         assert adv_next.is_contiguous() and adv_next.numel() == nz * H * W
-        _lib.call("nfs_advect_bwd_adam_fwd_slab", _ptr(d), _ptr(vel_slab), _ptr(g_slab), _ptr(m_slab), _ptr(v_slab),
-                  _ptr(adv_next), D, H, W, int(z0), nz, float(lr_t), float(beta1), float(beta2), float(eps), _stream())
+    _lib.call("nfs_advect_bwd_adam_fwd_slab" if extra else "nfs_advect_bwd_adam_slab", _ptr(d), _ptr(vel_slab), _ptr(g_slab),
+              _ptr(m_slab), _ptr(v_slab), *map(_ptr, extra), D, H, W, int(z0), nz, float(lr_t), float(beta1), float(beta2),
+              float(eps), _stream())
     _written(vel_slab, m_slab, v_slab, adv_next)
 
 

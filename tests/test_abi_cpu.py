@@ -43,6 +43,58 @@ def test_argument_errors_do_not_need_a_gpu():
     assert _lib.lib().nfs_conv3x3_packed_floats(64, 128, 0) == (9 + 36 + 36 + 36 + 54 + 36) * 64 * 128
 
 
+# the eight entry points that run only on the four-voxel advect kernel: name -> (number of pointer arguments before D, H, W
+# (d is the first, g_out the third); of them the index of adv_next, or None; takes a slab (z0, nz) after D, H, W)
+_ADVECT_X4 = {
+    "nfs_advect_fwd_live": (4, None, False),
+    "nfs_advect_bwd_adam": (5, None, False),
+    "nfs_advect_bwd_adam_fwd": (6, 5, False),
+    "nfs_advect_bwd_adam_fwd_live": (7, 5, False),
+    "nfs_advect_bwd_adam_fwd_live_ever": (8, 5, False),
+    "nfs_advect_fwd_slab": (3, None, True),
+    "nfs_advect_bwd_adam_slab": (5, None, True),
+    "nfs_advect_bwd_adam_fwd_slab": (6, 5, True),
+}
+
+
+# (the pointers below are host memory that must never reach a kernel: with a device present a bug in the code under test
+# would turn a failed assertion into a launch)
+@pytest.mark.skipif(torch.cuda.is_available(), reason="passes dummy host pointers: only where nothing can be launched")
+@pytest.mark.parametrize("name", sorted(_ADVECT_X4))
+def test_four_voxel_advect_entry_points_refuse_before_any_launch(name):
+    """shapes the four-voxel kernel does not take, a slab outside the volume and an adv_next that aliases d come back as
+    NFS_EINVAL with a text that names the entry point and the requirement"""
+    import ctypes
+    _lib = _ensure_built()
+    nptr, adv, slab = _ADVECT_X4[name]
+    bufs = [ctypes.create_string_buffer(64) for _ in range(nptr)]           # distinct, non-null, never dereferenced
+    ptrs = [ctypes.addressof(b) for b in bufs]
+    adam = () if "adam" not in name else (1e-3, 0.9, 0.999, 1e-8)
+
+    def refused(ptrs, D, H, W, z0, nz, text):
+        with pytest.raises(_lib.NfsError) as e:
+            _lib.call(name, *ptrs, D, H, W, *((z0, nz) if slab else ()), *adam, None)
+        assert e.value.code == _lib.NFS_EINVAL
+        msg = _lib.lib().nfs_last_error().decode()
+        assert msg.startswith(name + ":") and text in msg, msg
+
+    refused(ptrs, 3, 3, 3, 0, 3, "needs D, H, W >= 2")                        # 27 voxels: no multiple of 4
+    for shape in ((1, 4, 4), (4, 1, 4), (4, 4, 1)):
+        refused(ptrs, *shape, 0, shape[0], "needs D, H, W >= 2")
+    if slab:
+        refused(ptrs, 4, 4, 4, 2, 3, "slab outside the volume")
+        refused(ptrs, 4, 4, 4, -1, 2, "slab outside the volume")
+        refused(ptrs, 4, 4, 4, 0, 0, "slab outside the volume")
+        refused(ptrs, 4, 3, 3, 1, 1, "needs D, H, W >= 2")                     # 36 voxels, but a slab of 9
+    if adv is not None:
+        refused(ptrs[:adv] + [ptrs[0]] + ptrs[adv + 1:], 4, 4, 4, 0, 4, "adv_next must not alias d or g_out")
+        refused(ptrs[:adv] + [ptrs[2]] + ptrs[adv + 1:], 4, 4, 4, 0, 4, "adv_next must not alias d or g_out")
+        # the alias check comes before the shape check
+        refused(ptrs[:adv] + [ptrs[0]] + ptrs[adv + 1:], 3, 3, 3, 0, 3, "adv_next must not alias d or g_out")
+    for i in range(nptr):
+        refused(ptrs[:i] + [None] + ptrs[i + 1:], 4, 4, 4, 0, 4, "null pointer")
+
+
 def test_no_cpu_fallback():
     import neural_flow_style_amd.ops as ops
     with pytest.raises(ValueError):
