@@ -157,12 +157,18 @@ __global__ void __launch_bounds__(256) p2g_fwd_kernel(SplatDev s, const float* _
 // float accumulation keeps), and the integer sums do not depend on the order of the adds.
 constexpr int SPL_LDS = 8192;      // 64-bit LDS accumulators (64 KB: two blocks per CU)
 
+// The magnitude is converted and the integer negated: floor(c) and fract(c) of a NEGATIVE c with |c| < 1 are -1 and
+// 1 - |c|, and the latter keeps 24 bits below 1 -- 2^8 quanta lost per contribution, which the cells that receive only
+// small contributions of a block with large ones showed (tests/test_splat_gpu.py, attributes 1e-12 .. 1).  fract of a
+// non-negative float is exact, so every contribution is now truncated toward zero by less than one quantum.
 __device__ __forceinline__ unsigned long long splat_fix64(float c) {     // c = contribution * 2^(k - 32), |c| < 2^31
+  const float a = fabsf(c);
   unsigned hi, lo;
-  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(hi) : "v"(c));
-  const float fr = __builtin_amdgcn_fractf(c) * 4294967296.f;
+  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(hi) : "v"(a));
+  const float fr = __builtin_amdgcn_fractf(a) * 4294967296.f;
   asm("v_cvt_u32_f32 %0, %1" : "=v"(lo) : "v"(fr));
-  return ((unsigned long long)hi << 32) | lo;
+  const unsigned long long m = ((unsigned long long)hi << 32) | lo;
+  return c < 0.f ? 0ull - m : m;
 }
 
 // One particle per thread, 256 per block.  A block whose box does not fit (15 % of the blocks of the 5e5-particle set:

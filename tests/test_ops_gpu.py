@@ -485,7 +485,9 @@ def test_p2g_density(ops, nd):
     g = torch.randn_like(ref)
     (gp,) = torch.autograd.grad(ref, p, g)
     gp_h, _, _ = ops.p2g_bwd(dev(p[0]), cfg, dev(g[0]))
-    assert rel(gp_h, gp[0]) < 5e-4
+    # the per-particle bound of tests/splat_ref.py gives 5e-5 in relative L2 for both cases (its position term, the
+    # rounding of v and of the cell centre, carries 4e-5 of it): inside TOL
+    assert rel(gp_h, gp[0]) < TOL
 
 
 @pytest.mark.parametrize("mode", ["density", "wavg"])
@@ -540,6 +542,9 @@ def test_p2g_cell_ordered_particles_accumulate_in_lds_and_agree_with_the_scatter
     if mode == "density":
         pt_ = torch.tensor(p)[None].requires_grad_()
         (gref,) = torch.autograd.grad(O.p2g(pt_, dom, res, 0.5, 1000., 1, is_2d=False, clip=False), pt_, g[None])
+        # not TOL: the bound of tests/splat_ref.py allows 1.4e-4 in relative L2 here, 1.3e-4 of it the position term
+        # 'r' (one rounding of v = p dom and two of the cell centre, ~ 3 x 2^-24 x 48 against h = 2); the cell-by-cell
+        # check is tests/test_splat_gpu.py
         assert rel(grads[0][0], gref[0]) < 5e-4
 
 
@@ -577,6 +582,8 @@ def test_p2g_wavg_3d(ops):
     g_xs, g_ws = ops.p2g_wavg_finish_bwd(xs, ws, dev(g[0]))
     gp_h, gx_h, _ = ops.p2g_bwd(dev(p[0]), cfg, g_xs, attr=dev(x[0]), g_wsum=g_ws, need_p=True, need_attr=True)
     assert rel(gx_h, gx[0]) < TOL
+    # not TOL: the bound of tests/splat_ref.py allows 1.6e-4 in relative L2 here (position term 'r' 1.1e-4, the
+    # arithmetic of q and dW 5e-5: the gradient of an average is a difference of terms that nearly cancel)
     assert rel(gp_h, gp[0]) < 5e-4
 
 
