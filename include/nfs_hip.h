@@ -208,9 +208,32 @@ int nfs_advect2d_bwd(const float* d, const float* vel, const float* g_out, float
  *   d_bwd = advect(d_fwd, -vel);  d_adv = d_fwd + (d - d_bwd)/2;  where d_adv leaves the range of d over the corners
  *   of the back-traced interpolation cell, d_fwd is kept (the reference's "soft clamp").  The reference's own limiter
  *   is broken (tf.to_int32 of [-1,1] coordinates; d_max[grids]); this is the scheme it transcribes, done as intended.
- * d, d_fwd, out [D,H,W,C] (2-D: D = 1), vel [D,H,W,nd], nd = 2 | 3.  Forward only (as its uses: transport of results). */
+ * d, d_fwd, out [D,H,W,C] (2-D: D = 1), vel [D,H,W,nd], nd = 2 | 3.  Forward only (as its uses: transport of results);
+ * to differentiate through the scheme use the _keep form and its adjoint below. */
 int nfs_advect_maccormack(const float* d, const float* vel, const float* d_fwd, float* out,
                           int D, int H, int W, int C, int nd, nfs_stream_t stream);
+/* The differentiable form (transform.py:570-582, 590-607; config.py:41 adv_order = 2).
+ * nfs_advect_maccormack_keep: nfs_advect_maccormack (out bit-identical) + keep [nfs_maccormack_mask_words(D,H,W,C) 64-bit
+ *   words, all written]: bit e of the mask = the limiter fired for element e = voxel * C + channel of out, i.e. out = d_fwd
+ *   there and d_adv elsewhere.
+ * nfs_advect_maccormack_bwd: with F = d_fwd, B = advect(F, -vel), A = F + (d - B)/2, out = keep ? F : A and g = g_out:
+ *     gA = keep ? 0 : g;  gB = -gA/2;  gF = g + scatter(gB; x + vel);
+ *     g_d_acc (nullable) += gA/2 + scatter(gF; x - vel);
+ *     g_vel (nullable, overwritten) = +(n-1)/2 gB grad F(x + vel) - (n-1)/2 gF grad d(x - vel)
+ *   (the limiter is a comparison: no gradient through it).  keep and d_fwd are the forward's own: nothing is decided or
+ *   sampled again, so forward and adjoint agree on every element.  g_vel is bit-reproducible from call to call and does
+ *   not depend on g_d_acc being asked for: gF is summed in 64-bit fixed point (scale from max|g_out|, found on the
+ *   device; no element count or velocity field can overflow it); g_d_acc takes float atomics as nfs_advect_bwd's does.
+ *   Each half differentiates the stencil the forward sampled with (d_fwd as nfs_advect_fwd / nfs_advect2d_fwd formed
+ *   it).  workspace: nfs_advect_maccormack_bwd_workspace_floats(D,H,W,C,nd) floats (-1 for unsupported arguments),
+ *   8-byte aligned, contents irrelevant on entry.  Shapes: all nfs_advect_maccormack takes. */
+int nfs_maccormack_mask_words(int D, int H, int W, int C);
+int nfs_advect_maccormack_keep(const float* d, const float* vel, const float* d_fwd, float* out, unsigned long long* keep,
+                               int D, int H, int W, int C, int nd, nfs_stream_t stream);
+int64_t nfs_advect_maccormack_bwd_workspace_floats(int D, int H, int W, int C, int nd);
+int nfs_advect_maccormack_bwd(const float* d, const float* vel, const float* d_fwd, const unsigned long long* keep,
+                              const float* g_out, float* g_d_acc, float* g_vel, float* workspace, int64_t workspace_floats,
+                              int D, int H, int W, int C, int nd, nfs_stream_t stream);
 
 /* ---- curl of a stream function (transform.py:517-555) -------------------------------------------
  * nd = 2: s [H,W] -> out [H,W,2] = (ds/dy, -ds/dx);  nd = 3: s [D,H,W,3] -> out [D,H,W,3] (forward differences, last

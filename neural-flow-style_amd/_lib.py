@@ -81,6 +81,10 @@ SIGNATURES = {
     "nfs_advect2d_fwd": [_P, _P, _P, _I, _I, _I, _P],
     "nfs_advect2d_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "nfs_advect_maccormack": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "nfs_maccormack_mask_words": [_I, _I, _I, _I],
+    "nfs_advect_maccormack_keep": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "nfs_advect_maccormack_bwd_workspace_floats": [_I, _I, _I, _I, _I],
+    "nfs_advect_maccormack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "nfs_curl_fwd": [_P, _P, _I, _I, _I, _I, _P],
     "nfs_curl_bwd": [_P, _P, _I, _I, _I, _I, _P],
     "nfs_lap_down": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -173,11 +177,12 @@ SIGNATURES = {
 _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64,
             "nfs_conv3x3_workspace_floats": C.c_int64, "nfs_gram_workspace_floats": C.c_int64,
             "nfs_conv3x3_relu_bits_words": C.c_int64, "nfs_gram_style_group_workspace_floats": C.c_int64, "nfs_hist_loss_wide_workspace_floats": C.c_int64,
+            "nfs_advect_maccormack_bwd_workspace_floats": C.c_int64,
             "nfs_conv3x3_executed_flops": C.c_double, "nfs_conv2d_packed_floats": C.c_int64,
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 152          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 153          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

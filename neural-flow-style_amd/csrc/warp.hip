@@ -213,6 +213,19 @@ __device__ __forceinline__ float lean_sample(const F2u (&p)[4], float wx, float 
   return fmaf(wz, b1 - b0, b0);
 }
 
+// gradient of that sample along (z, y, x), in cells: difference of the two faces, interpolated in the other two axes
+// (the arithmetic of advect1_kernel's adjoint branch)
+__device__ __forceinline__ void lean_grad(const F2u (&p)[4], float wx, float wy, float wz, float& dz, float& dy, float& dx) {
+  float e[4], a[4];
+  lean_rows(p, wx, e, a);
+  const float f0 = fmaf(wy, e[1] - e[0], e[0]), f1 = fmaf(wy, e[3] - e[2], e[2]);
+  dx = fmaf(wz, f1 - f0, f0);
+  const float g0 = a[1] - a[0], g1 = a[3] - a[2];
+  dy = fmaf(wz, g1 - g0, g0);
+  const float b0 = fmaf(wy, g0, a[0]), b1 = fmaf(wy, g1, a[2]);
+  dz = b1 - b0;
+}
+
 // next voxel of this lane: 64 further on (clamped at the end of the volume; those results are not stored)
 __device__ __forceinline__ void walk64(int& w, int& h, int& z, int W, int H, int zlast) {
   w += 64;
@@ -1009,6 +1022,280 @@ __global__ void __launch_bounds__(RT_THREADS, 8) rotate_bwd_tiled_kernel(const f
   }
 }
 
+// ---- adjoint of MacCormack advection (nfs_advect_maccormack_bwd) ----------------------------------------------------------
+// The scheme (warp2d.hip, maccormack_kernel): F = SL(d, x - v), B = SL(F, x + v), A = F + (d - B)/2, out = keep ? F : A with
+// keep the limiter's decision, a comparison (no gradient through it).  Given g = dL/d out and the forward's own keep mask:
+//   gA = keep ? 0 : g,  gB = -gA/2,  gF = g + SL^T(gB; x + v),  g_d = gA/2 + SL^T(gF; x - v),
+//   g_vel = +(n-1)/2 gB grad F(x + v) - (n-1)/2 gF grad d(x - v)
+// i.e. the order-1 adjoint twice: pass 1 on (F, -v, gB), pass 2 on (d, v, gF).  gF is a scattered sum that g_vel depends
+// on, and g_vel has to come out the same bits in every run (view-sharded ranks apply "the identical step"), so pass 1
+// scatters into 64-bit fixed-point accumulators (integer adds are associative), one per element of the field.  Scale
+// 2^k from max|g| (absmax_kernel, on the device): every element may trace into one cell, so an accumulator holds at most
+// max|g|/2 * D H W C in magnitude; k is the largest power with that bound below 2^62 (a quantum of ~2^-39 max|g| at
+// 200^3).  A clamped axis (trace outside the volume: both clipped corners coincide) scatters with weight 1 onto the one
+// cell it sampled -- the real-number adjoint of (1 - w) f + w f -- so every weight lies in [0, 1] whatever the velocity.
+__device__ __forceinline__ double mc_fixed_scale(const unsigned* gmax_bits, float nelem) {
+  const float m = fminf(__uint_as_float(*gmax_bits) * 0.5f * nelem, 3.0e38f);     // > any accumulator's |sum|
+  if (!(m > 0.f)) return 1.0;
+  int e;
+  frexpf(m, &e);                                                                     // m < 2^e
+  return ldexp(1.0, 62 - e);
+}
+__device__ __forceinline__ void mc_fixed_add(long long* acc, int64_t o, double scaled) {
+  atomicAdd(reinterpret_cast<unsigned long long*>(acc) + o, (unsigned long long)__double2ll_rn(scaled));
+}
+
+// one axis of the stencil tri_setup builds, corners merged where they coincide
+struct McAxis { int i[2]; float w[2]; };
+__device__ __forceinline__ McAxis mc_axis(float c, int n) {
+  const Axis a = axis_setup(c, n);
+  const bool two = a.i0 != a.i1;
+  return {{a.i0, a.i1}, {two ? 1.f - a.w1 : 1.f, two ? a.w1 : 0.f}};
+}
+// gradient of the trilinear sample along (z, y, x) in cells: difference of the two faces, interpolated in the other two
+// axes (f[a*4 + b*2 + c]: corner (z_a, y_b, x_c))
+__device__ __forceinline__ void mc_grad(const float (&f)[8], const McAxis& az, const McAxis& ay, const McAxis& ax, float& dz,
+                                        float& dy, float& dx) {
+  dz = ay.w[0] * (ax.w[0] * (f[4] - f[0]) + ax.w[1] * (f[5] - f[1])) + ay.w[1] * (ax.w[0] * (f[6] - f[2]) + ax.w[1] * (f[7] - f[3]));
+  dy = az.w[0] * (ax.w[0] * (f[2] - f[0]) + ax.w[1] * (f[3] - f[1])) + az.w[1] * (ax.w[0] * (f[6] - f[4]) + ax.w[1] * (f[7] - f[5]));
+  dx = az.w[0] * (ay.w[0] * (f[1] - f[0]) + ay.w[1] * (f[3] - f[2])) + az.w[1] * (ay.w[0] * (f[5] - f[4]) + ay.w[1] * (f[7] - f[6]));
+}
+
+// pass 1, one thread per voxel (any C, 2-D as D == 1): gB from g and the keep mask; g_vel (nullable) = the B half;
+// g_d_acc (nullable) += gA/2 on the element itself; acc += SL^T(gB; x + v) in fixed point.  Stencil: tri_setup at x + v,
+// as maccormack_kernel sampled d_fwd.
+__global__ void __launch_bounds__(256) maccormack_bwd1_kernel(const float* __restrict__ g_out, const float* __restrict__ vel,
+                                                              const float* __restrict__ d_fwd,
+                                                              const unsigned long long* __restrict__ keep,
+                                                              float* __restrict__ g_vel, float* __restrict__ g_d_acc,
+                                                              long long* acc, const unsigned* __restrict__ gmax_bits, int D,
+                                                              int H, int W, int C, int nd) {
+  const int64_t n = (int64_t)D * H * W;
+  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vox >= n) return;
+  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
+  const float* v = vel + vox * nd;
+  const float vz = nd == 3 ? v[0] : 0.f, vy = v[nd - 2], vx = v[nd - 1];
+  const McAxis az = mc_axis(lin_coord(z, D) + vz, D), ay = mc_axis(lin_coord(y, H) + vy, H),
+               ax = mc_axis(lin_coord(x, W) + vx, W);
+  const double scale = mc_fixed_scale(gmax_bits, (float)n * (float)C);
+  float sz = 0.f, sy = 0.f, sx = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const int64_t e = vox * C + c;
+    const float g = g_out[e];
+    const float gA = ((keep[e >> 6] >> (e & 63)) & 1ull) ? 0.f : g, gB = -0.5f * gA;
+    if (gA == 0.f) continue;
+    if (g_d_acc) g_d_acc[e] += 0.5f * gA;
+    int64_t o[8];
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      o[k] = (((int64_t)az.i[k >> 2] * H + ay.i[(k >> 1) & 1]) * W + ax.i[k & 1]) * C + c;
+      f[k] = d_fwd[o[k]];
+    }
+    if (g_vel) {
+      float dz, dy, dx;
+      mc_grad(f, az, ay, ax, dz, dy, dx);
+      sz += gB * dz; sy += gB * dy; sx += gB * dx;
+    }
+    const double gs = (double)gB * scale;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const double w = (double)az.w[k >> 2] * (double)ay.w[(k >> 1) & 1] * (double)ax.w[k & 1];
+      if (w != 0.0) mc_fixed_add(acc, o[k], w * gs);
+    }
+  }
+  if (g_vel) {   // coordinate = index + vel (n-1)/2
+    float* gv = g_vel + vox * nd;
+    if (nd == 3) gv[0] = sz * (0.5f * (float)(D - 1));
+    gv[nd - 2] = sy * (0.5f * (float)(H - 1));
+    gv[nd - 1] = sx * (0.5f * (float)(W - 1));
+  }
+}
+
+// pass 1 for the scalar 3-D field: a block owns MT_Z x MT_Y x MT_X voxels and sums what their traces scatter in LDS, in
+// the same 64-bit fixed point, over the tile and a halo of MT_R cells (a trace of up to MT_R - 1 cells per axis stays
+// inside); the few contributions that land further away go to the global accumulator directly.  The tile is then added
+// to the global accumulators row by row (contiguous 8-byte atomics, zeros skipped): about 3.6 global atomics per voxel in
+// runs instead of 8 scattered ones (global atomics bound the one-thread-per-voxel form: 0.52 ms at 200^3 for 32 B of
+// streamed traffic per cell; this form 0.16 ms, profiles/maccormack_adjoint.txt).  Integer adds in LDS and in memory: the
+// sums do not depend on the order.
+constexpr int MT_Z = 8, MT_Y = 8, MT_X = 32, MT_R = 3, MT_THREADS = 512;
+constexpr int MT_LZ = MT_Z + 2 * MT_R, MT_LY = MT_Y + 2 * MT_R, MT_LX = MT_X + 2 * MT_R, MT_CELLS = MT_LZ * MT_LY * MT_LX;
+static_assert(MT_CELLS * 8 <= 64 * 1024, "the tile's accumulators fit the LDS a launch gets without an opt-in");
+__global__ void __launch_bounds__(MT_THREADS) maccormack_bwd1_tiled_kernel(const float* __restrict__ g_out,
+                                                                           const float* __restrict__ vel,
+                                                                           const float* __restrict__ d_fwd,
+                                                                           const unsigned long long* __restrict__ keep,
+                                                                           float* __restrict__ g_vel, float* __restrict__ g_d_acc,
+                                                                           long long* acc, const unsigned* __restrict__ gmax_bits,
+                                                                           int D, int H, int W, int ntx, int nty) {
+  __shared__ unsigned long long tile[MT_CELLS];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < MT_CELLS; i += MT_THREADS) tile[i] = 0ull;
+  const int bx = blockIdx.x % ntx, by = (blockIdx.x / ntx) % nty, bz = blockIdx.x / (ntx * nty);
+  const int z0 = bz * MT_Z, y0 = by * MT_Y, x0 = bx * MT_X;
+  const double scale = mc_fixed_scale(gmax_bits, (float)D * (float)H * (float)W);
+  __syncthreads();
+  for (int l = tid; l < MT_Z * MT_Y * MT_X; l += MT_THREADS) {
+    const int x = x0 + l % MT_X, y = y0 + (l / MT_X) % MT_Y, z = z0 + l / (MT_X * MT_Y);
+    if (x >= W || y >= H || z >= D) continue;
+    const int64_t vox = ((int64_t)z * H + y) * W + x;
+    const F3u v = reinterpret_cast<const F3u*>(vel)[vox];
+    const float g = g_out[vox];
+    const float gA = ((keep[vox >> 6] >> (vox & 63)) & 1ull) ? 0.f : g, gB = -0.5f * gA;
+    if (gA == 0.f) {
+      if (g_vel) reinterpret_cast<F3u*>(g_vel)[vox] = F3u{0.f, 0.f, 0.f};
+      continue;
+    }
+    if (g_d_acc) g_d_acc[vox] += 0.5f * gA;
+    const McAxis az = mc_axis(lin_coord(z, D) + v.x, D), ay = mc_axis(lin_coord(y, H) + v.y, H),
+                 ax = mc_axis(lin_coord(x, W) + v.z, W);
+    if (g_vel) {
+      float f[8];
+      tri_gather_pairs(d_fwd, H, W, Axis{az.i[0], az.i[1], 0.f}, Axis{ay.i[0], ay.i[1], 0.f}, Axis{ax.i[0], ax.i[1], 0.f}, f);
+      float dz, dy, dx;
+      mc_grad(f, az, ay, ax, dz, dy, dx);      // coordinate = index + vel (n-1)/2
+      reinterpret_cast<F3u*>(g_vel)[vox] = F3u{gB * dz * (0.5f * (float)(D - 1)), gB * dy * (0.5f * (float)(H - 1)),
+                                               gB * dx * (0.5f * (float)(W - 1))};
+    }
+    const double gs = (double)gB * scale;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const double wk = (double)az.w[k >> 2] * (double)ay.w[(k >> 1) & 1] * (double)ax.w[k & 1];
+      if (wk == 0.0) continue;
+      const int cz = az.i[k >> 2], cy = ay.i[(k >> 1) & 1], cx = ax.i[k & 1];
+      const unsigned rz = (unsigned)(cz - z0 + MT_R), ry = (unsigned)(cy - y0 + MT_R), rx = (unsigned)(cx - x0 + MT_R);
+      const unsigned long long q = (unsigned long long)__double2ll_rn(wk * gs);
+      if (rz < (unsigned)MT_LZ && ry < (unsigned)MT_LY && rx < (unsigned)MT_LX)
+        atomicAdd(&tile[(rz * MT_LY + ry) * MT_LX + rx], q);
+      else
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc) + ((int64_t)cz * H + cy) * W + cx, q);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < MT_CELLS; i += MT_THREADS) {
+    const unsigned long long q = tile[i];
+    if (q == 0ull) continue;     // (only cells inside the volume ever receive anything)
+    const int cx = x0 - MT_R + i % MT_LX, cy = y0 - MT_R + (i / MT_LX) % MT_LY, cz = z0 - MT_R + i / (MT_LX * MT_LY);
+    atomicAdd(reinterpret_cast<unsigned long long*>(acc) + ((int64_t)cz * H + cy) * W + cx, q);
+  }
+}
+
+// pass 2: gF = g + acc / scale; g_vel (nullable, holds pass 1's half) -= (n-1)/2 gF grad d(x - v); g_d_acc (nullable) +=
+// SL^T(gF; x - v) (float atomics, as nfs_advect_bwd).  Stencil: the one d_fwd was sampled with.
+// Scalar 3-D fields the four-voxel forward takes (advect1_takes): the lean stencil in advect1_kernel's layout -- a wave
+// owns 256 consecutive voxels, lane l takes l, l + 64, ...; g, the accumulators, the velocity and pass 1's half of g_vel
+// are streamed in contiguous runs, all requested before the gathers; per-XCD z-slabs.
+__global__ void __launch_bounds__(256) maccormack_bwd2x4_kernel(const float* __restrict__ d, const float* __restrict__ vel,
+                                                                const float* __restrict__ g_out,
+                                                                const long long* __restrict__ acc,
+                                                                const unsigned* __restrict__ gmax_bits, float* g_vel,
+                                                                float* g_d_acc, int D, int H, int W) {
+  const int n = D * H * W;
+  const int lane = threadIdx.x & 63, first = lane_first<4, true>(blockDim.x, lane);
+  if (first - lane >= n) return;
+  const double inv = 1.0 / mc_fixed_scale(gmax_bits, (float)n);
+  const F3u* v3 = reinterpret_cast<const F3u*>(vel);
+  F3u* gv3 = reinterpret_cast<F3u*>(g_vel);
+  F3u vv[4], hh[4];
+  float gg[4];
+  long long aa[4];
+  bool ok[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int idx = first + 64 * j;
+    ok[j] = idx < n;
+    const int ic = ok[j] ? idx : n - 1;
+    vv[j] = v3[ic];
+    gg[j] = g_out[ic];
+    aa[j] = acc[ic];
+    if (g_vel) hh[j] = gv3[ic];
+  }
+  const LeanDims dm = lean_dims(D, H, W);
+  int w, h, z;
+  lane_start(first, n, H, W, w, h, z);
+  F2u p[4][4];
+  float wz[4], wy[4], wx[4], mz[4], my[4], mx[4];
+  unsigned ob[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const LeanCell c = lean_cell(vv[j], z, h, w, dm);
+    wz[j] = c.wz; wy[j] = c.wy; wx[j] = c.wx; ob[j] = c.o;
+    // outside the volume both clipped corners coincide: no dependence on the coordinate
+    mz[j] = (c.xz >= 0.f && c.xz < dm.nz1) ? dm.hz : 0.f;
+    my[j] = (c.xy >= 0.f && c.xy < dm.ny1) ? dm.hy : 0.f;
+    mx[j] = (c.xx >= 0.f && c.xx < dm.nx1) ? dm.hx : 0.f;
+    lean_gather(d, c.o, dm, p[j]);
+    walk64(w, h, z, W, H, D - 1);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!ok[j]) continue;
+    const float gF = (float)((double)gg[j] + (double)aa[j] * inv);
+    if (g_vel) {
+      float dz, dy, dx;
+      lean_grad(p[j], wx[j], wy[j], wz[j], dz, dy, dx);
+      gv3[first + 64 * j] = F3u{hh[j].x - gF * dz * mz[j], hh[j].y - gF * dy * my[j], hh[j].z - gF * dx * mx[j]};
+    }
+    if (g_d_acc && gF != 0.f) {
+      const float cz[2] = {1.f - wz[j], wz[j]}, cy[2] = {1.f - wy[j], wy[j]}, cx[2] = {1.f - wx[j], wx[j]};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float contrib = cz[k >> 2] * cy[(k >> 1) & 1] * cx[k & 1] * gF;
+        if (contrib != 0.f) atomicAdd(g_d_acc + ob[j] + (k >> 2) * dm.uHW + ((k >> 1) & 1) * dm.uW + (k & 1), contrib);
+      }
+    }
+  }
+}
+
+// ... and every other shape (any C, 2-D as D == 1, thin sides), one thread per voxel: tri_setup at x - v
+__global__ void __launch_bounds__(256) maccormack_bwd2_kernel(const float* __restrict__ d, const float* __restrict__ vel,
+                                                              const float* __restrict__ g_out, const long long* __restrict__ acc,
+                                                              const unsigned* __restrict__ gmax_bits, float* __restrict__ g_vel,
+                                                              float* __restrict__ g_d_acc, int D, int H, int W, int C, int nd) {
+  const int64_t n = (int64_t)D * H * W;
+  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vox >= n) return;
+  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
+  const double inv = 1.0 / mc_fixed_scale(gmax_bits, (float)n * (float)C);
+  const float* v = vel + vox * nd;
+  const float vz = nd == 3 ? v[0] : 0.f, vy = v[nd - 2], vx = v[nd - 1];
+  const McAxis az = mc_axis(lin_coord(z, D) - vz, D), ay = mc_axis(lin_coord(y, H) - vy, H),
+               ax = mc_axis(lin_coord(x, W) - vx, W);
+  float sz = 0.f, sy = 0.f, sx = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const int64_t e = vox * C + c;
+    const float gF = (float)((double)g_out[e] + (double)acc[e] * inv);
+    if (gF == 0.f) continue;
+    int64_t o[8];
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      o[k] = (((int64_t)az.i[k >> 2] * H + ay.i[(k >> 1) & 1]) * W + ax.i[k & 1]) * C + c;
+      if (g_vel) f[k] = d[o[k]];
+    }
+    if (g_vel) {
+      float dz, dy, dx;
+      mc_grad(f, az, ay, ax, dz, dy, dx);
+      sz += gF * dz; sy += gF * dy; sx += gF * dx;
+    }
+    if (g_d_acc) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float contrib = az.w[k >> 2] * ay.w[(k >> 1) & 1] * ax.w[k & 1] * gF;
+        if (contrib != 0.f) atomicAdd(g_d_acc + o[k], contrib);
+      }
+    }
+  }
+  if (g_vel) {   // coordinate = index - vel (n-1)/2
+    float* gv = g_vel + vox * nd;
+    if (nd == 3) gv[0] -= sz * (0.5f * (float)(D - 1));
+    gv[nd - 2] -= sy * (0.5f * (float)(H - 1));
+    gv[nd - 1] -= sx * (0.5f * (float)(W - 1));
+  }
+}
+
 static int check_dims(int B, int X, int Y, int Z, int C) {
   NFS_REQUIRE(B > 0 && X > 0 && Y > 0 && Z > 0 && C > 0, "warp: non-positive dimension");
   NFS_REQUIRE((int64_t)B * X * Y * Z * C < (int64_t)1 << 40, "warp: tensor too large");
@@ -1224,6 +1511,54 @@ int nfs_advect_bwd(const float* d, const float* vel, const float* g_out, float* 
   hipLaunchKernelGGL(warp_bwd_kernel<COORD_ADVECT>, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), a,
                      g_out, g_d_acc, g_vel);
   return check_launch("nfs_advect_bwd");
+}
+
+// ---- adjoint of nfs_advect_maccormack_keep (transform.py:570-582, 590-607; the kernels above) ----------------------------
+static bool mc_dims_ok(int D, int H, int W, int C, int nd) {
+  return D > 0 && H > 0 && W > 0 && C > 0 && (nd == 2 || nd == 3) && (nd == 3 || D == 1) &&
+         (int64_t)D * H * W * C < ((int64_t)1 << 40);
+}
+// workspace: the 64-bit accumulators (one per element), then 64 floats whose first word holds max|g_out|
+int64_t nfs_advect_maccormack_bwd_workspace_floats(int D, int H, int W, int C, int nd) {
+  return mc_dims_ok(D, H, W, C, nd) ? 2 * (int64_t)D * H * W * C + 64 : -1;
+}
+
+int nfs_advect_maccormack_bwd(const float* d, const float* vel, const float* d_fwd, const unsigned long long* keep,
+                              const float* g_out, float* g_d_acc, float* g_vel, float* workspace, int64_t workspace_floats,
+                              int D, int H, int W, int C, int nd, nfs_stream_t stream) {
+  NFS_REQUIRE(d && vel && d_fwd && keep && g_out && workspace, "nfs_advect_maccormack_bwd: null pointer");
+  NFS_REQUIRE(g_d_acc || g_vel, "nfs_advect_maccormack_bwd: nothing to compute");
+  NFS_REQUIRE(mc_dims_ok(D, H, W, C, nd),
+              "nfs_advect_maccormack_bwd: needs positive dimensions, nd 2 (with D == 1) or 3, fewer than 2^40 elements");
+  const int64_t ne = (int64_t)D * H * W * C, nv = (int64_t)D * H * W;
+  NFS_REQUIRE(workspace_floats >= 2 * ne + 64 && ((uintptr_t)workspace & 7) == 0,
+              "nfs_advect_maccormack_bwd: workspace smaller than nfs_advect_maccormack_bwd_workspace_floats() or not 8-byte "
+              "aligned");
+  NFS_REQUIRE(g_vel != g_out && g_d_acc != g_out, "nfs_advect_maccormack_bwd: the gradients must not alias g_out");
+  hipStream_t s = as_stream(stream);
+  long long* acc = reinterpret_cast<long long*>(workspace);
+  unsigned* gmax = reinterpret_cast<unsigned*>(workspace + 2 * ne);
+  zero_words(workspace, 2 * ne + 64, s);
+  const unsigned mb = blocks_for(ne, 1024);
+  hipLaunchKernelGGL(absmax_kernel, dim3(mb < 2048 ? mb : 2048), dim3(256), 0, s, g_out, ne, gmax);
+  // the scalar 3-D fields the four-voxel forward takes (nfs_advect_fwd's choice of stencil for d_fwd) have kernels of
+  // their own in both passes
+  const bool hot = C == 1 && nd == 3 && advect1_takes(D, H, W, D);
+  if (hot) {
+    const int ntx = (W + MT_X - 1) / MT_X, nty = (H + MT_Y - 1) / MT_Y, ntz = (D + MT_Z - 1) / MT_Z;
+    hipLaunchKernelGGL(maccormack_bwd1_tiled_kernel, dim3(ntx * nty * ntz), dim3(MT_THREADS), 0, s, g_out, vel, d_fwd, keep,
+                       g_vel, g_d_acc, acc, gmax, D, H, W, ntx, nty);
+  } else {
+    hipLaunchKernelGGL(maccormack_bwd1_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, s, g_out, vel, d_fwd, keep, g_vel,
+                       g_d_acc, acc, gmax, D, H, W, C, nd);
+  }
+  if (hot)                                                    // 256 threads x 4 voxels; whole rounds of the 8 XCDs
+    hipLaunchKernelGGL(maccormack_bwd2x4_kernel, dim3((blocks_for(nv, 1024) + 7) / 8 * 8), dim3(256), 0, s, d, vel, g_out,
+                       acc, gmax, g_vel, g_d_acc, D, H, W);
+  else
+    hipLaunchKernelGGL(maccormack_bwd2_kernel, dim3(blocks_for(nv, 256)), dim3(256), 0, s, d, vel, g_out, acc, gmax, g_vel,
+                       g_d_acc, D, H, W, C, nd);
+  return check_launch("nfs_advect_maccormack_bwd");
 }
 
 // velocity gradient of advect + TF ApplyAdam on the velocity in one pass (scalar field, C = 1; the shapes the four-voxel

@@ -112,9 +112,15 @@ __global__ void __launch_bounds__(256) warp2d_bwd_kernel(Warp2Args a, const floa
 //   limiter: d_min / d_max = extrema of d over the corners of the back-traced interpolation stencil (what the
 //   reference's 2x2(x2) max-pool sampled at the back-traced cell means); where d_adv leaves [d_min, d_max] the
 //   first-order value d_fwd is kept ("soft clamp", transform.py:578-582 / 604-607).
+// keep (nullable): bit e of the mask = the limiter fired for element e = vox * C + c of out (what the adjoint reads
+// instead of deciding again).  C == 1: a wave's lanes hold 64 consecutive elements, one ballot = one word; else bits are
+// OR-ed into the zero-filled mask.  ONE kernel serves nfs_advect_maccormack and nfs_advect_maccormack_keep, and the sums
+// are written as explicit FMAs: the compiler contracted `bwd += w * f` in the unrolled channel pairs and not in the
+// remainder, so two instances of this body differed in the last bit for C > 1.
 __global__ void __launch_bounds__(256) maccormack_kernel(const float* __restrict__ d, const float* __restrict__ vel,
                                                          const float* __restrict__ d_fwd, float* __restrict__ out,
-                                                         int D, int H, int W, int C, int nd) {
+                                                         int D, int H, int W, int C, int nd,
+                                                         unsigned long long* __restrict__ keep) {
   const int64_t n = (int64_t)D * H * W;
   const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (vox >= n) return;
@@ -133,11 +139,21 @@ __global__ void __launch_bounds__(256) maccormack_kernel(const float* __restrict
       const float dv = d[tb.o[k] * C + c];
       lo = fminf(lo, dv);
       hi = fmaxf(hi, dv);
-      bwd += tf.w[k] * d_fwd[tf.o[k] * C + c];
+      bwd = fmaf(tf.w[k], d_fwd[tf.o[k] * C + c], bwd);
     }
     const float f = d_fwd[vox * C + c];
-    const float adv = f + (d[vox * C + c] - bwd) * 0.5f;
-    out[vox * C + c] = (adv > hi || lo > adv) ? f : adv;
+    const float adv = fmaf(d[vox * C + c] - bwd, 0.5f, f);
+    const bool kp = adv > hi || lo > adv;
+    out[vox * C + c] = kp ? f : adv;
+    if (keep) {
+      const int64_t e = vox * C + c;
+      if (C == 1) {
+        const unsigned long long word = __ballot(kp);
+        if ((threadIdx.x & 63) == 0) keep[e >> 6] = word;
+      } else if (kp) {
+        atomicOr(keep + (e >> 6), 1ull << (e & 63));
+      }
+    }
   }
 }
 
@@ -272,9 +288,32 @@ int nfs_advect_maccormack(const float* d, const float* vel, const float* d_fwd, 
   NFS_REQUIRE(nd == 3 || D == 1, "nfs_advect_maccormack: a 2-D field has D == 1");
   NFS_REQUIRE(out != d_fwd && out != d, "nfs_advect_maccormack: out must not alias d or d_fwd");
   if (int e = check_dims2(D, H, W, C)) return e;
-  hipLaunchKernelGGL(maccormack_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), d, vel,
-                     d_fwd, out, D, H, W, C, nd);
+  hipLaunchKernelGGL(maccormack_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), d,
+                     vel, d_fwd, out, D, H, W, C, nd, (unsigned long long*)nullptr);
   return check_launch("nfs_advect_maccormack");
+}
+
+// 64-bit words of the keep mask of a [D,H,W,C] field: one bit per element, rounded up to whole blocks of 256 elements
+int nfs_maccormack_mask_words(int D, int H, int W, int C) {
+  const int64_t n = (int64_t)D * H * W * C;
+  return (D > 0 && H > 0 && W > 0 && C > 0 && n < ((int64_t)1 << 36)) ? (int)((n + 255) / 256 * 4) : 0;
+}
+
+// nfs_advect_maccormack + the limiter's decisions (keep [nfs_maccormack_mask_words]): the same kernel body, so out is
+// bit-identical; the mask is what nfs_advect_maccormack_bwd differentiates by
+int nfs_advect_maccormack_keep(const float* d, const float* vel, const float* d_fwd, float* out, unsigned long long* keep,
+                               int D, int H, int W, int C, int nd, nfs_stream_t stream) {
+  NFS_REQUIRE(d && vel && d_fwd && out && keep, "nfs_advect_maccormack_keep: null pointer");
+  NFS_REQUIRE(nd == 2 || nd == 3, "nfs_advect_maccormack_keep: nd must be 2 or 3");
+  NFS_REQUIRE(nd == 3 || D == 1, "nfs_advect_maccormack_keep: a 2-D field has D == 1");
+  NFS_REQUIRE(out != d_fwd && out != d, "nfs_advect_maccormack_keep: out must not alias d or d_fwd");
+  if (int e = check_dims2(D, H, W, C)) return e;
+  const int words = nfs_maccormack_mask_words(D, H, W, C);
+  NFS_REQUIRE(words > 0, "nfs_advect_maccormack_keep: field too large for a mask");
+  zero_words(keep, 2 * (long long)words, as_stream(stream));
+  hipLaunchKernelGGL(maccormack_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), d,
+                     vel, d_fwd, out, D, H, W, C, nd, keep);
+  return check_launch("nfs_advect_maccormack_keep");
 }
 
 int nfs_curl_fwd(const float* s, float* out, int D, int H, int W, int nd, nfs_stream_t stream) {

@@ -779,9 +779,14 @@ class GridStylizer(object):
     adjoint, advect adjoint + ApplyAdam, advect, smooth -> all-gather of the smoothed density (see
     ``_slab_setup``).  Otherwise the gradient is all-reduced and every rank applies the identical step.
     ``bind`` swaps the frame (density, variable, Adam state) under the same
-    stylizer: the frame loop of a sequence (styler_grid.py) re-uses one instance."""
+    stylizer: the frame loop of a sequence (styler_grid.py) re-uses one instance.
+    ``adv_order`` (config.py adv_order; velocity variable): 1 = semi-Lagrangian advect, 2 = MacCormack with the extrema
+    limiter, forward and adjoint (``ops.advect_maccormack`` / ``advect_maccormack_bwd``).  Order 2 takes the unfused
+    update (adjoint, then the optimiser's step) and, over ranks, the all-reduce mode: every rank repeats the field work
+    on the summed density gradient and, the adjoint being bit-reproducible, arrives at the identical variable.  With
+    ``target='d'`` there is no advect: ``adv_order`` is accepted and has no effect."""
 
-    def __init__(self, loss, d0, k=3, target="v", lr=0.1, process_group=None, graph=None, optimizer="adam"):
+    def __init__(self, loss, d0, k=3, target="v", lr=0.1, process_group=None, graph=None, optimizer="adam", adv_order=1):
         self.loss = loss
         self.d0 = d0.contiguous()
         self.k = float(k)
@@ -791,6 +796,15 @@ class GridStylizer(object):
         self.adam = make_optimizer(optimizer)        # (named after the reference's optimiser; L-BFGS on request)
         # the advect adjoint consumed inside the Adam kernel: only when the optimiser IS Adam
         self.fuse_adam = os.environ.get("NFS_FUSE_ADAM", "1") != "0" and isinstance(self.adam, TFAdamState)
+        assert int(adv_order) in (1, 2), "adv_order is 1 (semi-Lagrangian) or 2 (MacCormack)"
+        self.adv_order = int(adv_order)
+        if self.adv_order == 2 and target == "v":
+            # the fused kernels (adjoint + Adam + next forward, slab forms, live mask) are those of the order-1 stencil
+            self.fuse_adam = False
+        # order 2: the first-order sample and the limiter's decisions of the CURRENT forward, which the adjoint reads (fixed
+        # buffers: a captured forward writes them at every replay, the adjoint outside the capture reads what it wrote)
+        self._mc_fwd = None
+        self._mc_keep = None
         # hipGraph replay of the forward + adjoint (about 130 launches a step; the host needs 1.25 ms to issue
         # them one by one, which is the whole step at one view per rank)
         # (measured: 200^3 x 8 views 3.98 -> 3.90 ms, 200^3 x 1 view 1.35 -> 1.41 ms, 100^3 x 1 view 1.20 -> 1.06 ms:
@@ -1026,6 +1040,8 @@ class GridStylizer(object):
     def _advect_now(self):
         """d_adv = advect(d0, var) -- from the previous step's Adam kernel when it is still current, else computed here
         (into the same buffer: a captured graph reads it by address)"""
+        if self.adv_order == 2:
+            return self._advect_now_order2()
         sl = self.slab
         buf = self._adv_target()
         live = self._live_target()
@@ -1039,6 +1055,14 @@ class GridStylizer(object):
         if buf is not None:
             self._adv_mark(live=live is not None)
         return out
+
+    def _advect_now_order2(self):
+        """d_adv = MacCormack(d0, var); d_fwd and the keep mask stay on the stylizer for ``variable_gradient``"""
+        d4 = self.d0.unsqueeze(-1)
+        if self._mc_fwd is None or self._mc_fwd.shape != d4.shape:
+            self._mc_fwd = torch.empty_like(d4)
+            self._mc_keep = ops.maccormack_mask(d4.shape, d4)
+        return ops.advect_maccormack(d4, self.var, keep=self._mc_keep, d_fwd=self._mc_fwd).squeeze(-1)
 
     def forward_field(self):
         if self.slab is not None:
@@ -1077,6 +1101,10 @@ class GridStylizer(object):
         """adjoint of smooth+max and advect: dL/d variable from dL/d d_s (deterministic kernels: every
         rank computes the identical result from the all-reduced g_ds)"""
         g_adv = ops.smooth3d_relu_bwd(self.d_s, g_ds, self.k)
+        if self.target == "v" and self.adv_order == 2:
+            _, g_var = ops.advect_maccormack_bwd(self.d0.unsqueeze(-1), self.var, self._mc_fwd, self._mc_keep,
+                                                 g_adv.unsqueeze(-1), need_d=False, need_vel=True)
+            return g_var
         if self.target == "v":
             _, g_var = ops.advect_bwd(self.d0.unsqueeze(-1), self.var, g_adv.unsqueeze(-1), need_d=False,
                                       need_vel=True)

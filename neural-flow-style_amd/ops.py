@@ -219,19 +219,62 @@ def advect2d_bwd(d, vel, g_out, need_d=True, need_vel=True):
     return g_d, g_vel
 
 
-def advect_maccormack(d, vel):
+def maccormack_mask(shape, like):
+    """buffer for the limiter's keep mask of a field of ``shape`` = [D,H,W,C] or [H,W,C]: nfs_maccormack_mask_words 64-bit
+    words, bit e = element e of the advected field kept its first-order value; float32 storage like ``live_mask``"""
+    D, H, W, Cn = (1,) * (4 - len(shape)) + tuple(shape)
+    return torch.zeros(2 * int(_lib.lib().nfs_maccormack_mask_words(D, H, W, Cn)), dtype=torch.float32, device=like.device)
+
+
+def advect_maccormack(d, vel, keep=None, d_fwd=None):
     """order-2 (MacCormack) advection with the extrema limiter (transform.py:570-582, 590-607 as intended);
-    d [D,H,W,C] + vel [D,H,W,3], or d [H,W,C] + vel [H,W,2].  Forward only."""
+    d [D,H,W,C] + vel [D,H,W,3], or d [H,W,C] + vel [H,W,2].  ``keep`` (optional, ``maccormack_mask``): also write the
+    limiter's decisions; ``d_fwd`` (optional, shaped like d): receives the first-order sample the scheme starts from --
+    the two things ``advect_maccormack_bwd`` differentiates by.  The result is the same bits with and without them."""
+    nd = vel.shape[-1]
+    if d_fwd is not None:
+        assert d_fwd.shape == d.shape and d_fwd.is_contiguous()
+    if nd == 3:
+        D, H, W, Cn = d.shape
+        d_fwd = advect_fwd(d, vel, out=d_fwd)
+    else:
+        (H, W, Cn), D = d.shape, 1
+        if d_fwd is None:
+            d_fwd = advect2d_fwd(d, vel)
+        else:
+            _lib.call("nfs_advect2d_fwd", _ptr(d), _ptr(vel), _ptr(d_fwd), H, W, Cn, _stream())
+    out = _empty(d.shape, d)
+    if keep is None:
+        _lib.call("nfs_advect_maccormack", _ptr(d), _ptr(vel), _ptr(d_fwd), _ptr(out), D, H, W, Cn, nd, _stream())
+    else:
+        assert keep.numel() == 2 * int(_lib.lib().nfs_maccormack_mask_words(D, H, W, Cn))
+        _lib.call("nfs_advect_maccormack_keep", _ptr(d), _ptr(vel), _ptr(d_fwd), _ptr(out), _ptr(keep), D, H, W, Cn, nd,
+                  _stream())
+        _written(keep)
+    return out
+
+
+def advect_maccormack_bwd(d, vel, d_fwd, keep, g_out, need_d=True, need_vel=True, g_d_acc=None, g_vel=None):
+    """adjoint of ``advect_maccormack`` on the forward's own ``d_fwd`` and ``keep``: (g_d, g_vel) in the style of
+    ``advect_bwd`` (g_d_acc is accumulated into, g_vel overwritten).  g_vel is bit-identical from call to call and with
+    ``need_d`` on or off (fixed-point sums; include/nfs_hip.h)."""
     nd = vel.shape[-1]
     if nd == 3:
         D, H, W, Cn = d.shape
-        d_fwd = advect_fwd(d, vel)
     else:
         (H, W, Cn), D = d.shape, 1
-        d_fwd = advect2d_fwd(d, vel)
-    out = _empty(d.shape, d)
-    _lib.call("nfs_advect_maccormack", _ptr(d), _ptr(vel), _ptr(d_fwd), _ptr(out), D, H, W, Cn, nd, _stream())
-    return out
+    if need_d and g_d_acc is None:
+        g_d_acc = _zeros(d.shape, d)
+    if need_vel and g_vel is None:
+        g_vel = _empty(vel.shape, d)
+    nws = int(_lib.lib().nfs_advect_maccormack_bwd_workspace_floats(D, H, W, Cn, nd))
+    if nws < 0:
+        raise ValueError("advect_maccormack_bwd: unsupported shape %s / %s" % (tuple(d.shape), tuple(vel.shape)))
+    ws = _empty((nws,), d)
+    _lib.call("nfs_advect_maccormack_bwd", _ptr(d), _ptr(vel), _ptr(d_fwd), _ptr(keep), _ptr(g_out),
+              _ptr(g_d_acc if need_d else None), _ptr(g_vel if need_vel else None), _ptr(ws), nws, D, H, W, Cn, nd,
+              _stream())
+    return (g_d_acc if need_d else None), (g_vel if need_vel else None)
 
 
 def curl_fwd(s):

@@ -48,6 +48,7 @@ class Styler(StylerBase):
         assert self.batch_size == 1, "batch_size > 1 is not supported (styler_3p module docstring)"
         self.target = getattr(self, "grid_variable", "") or "v"
         assert self.target in ("v", "d")
+        self.adv_order = int(getattr(self, "adv_order", 1) or 1)       # config.py adv_order: 1 = SL, 2 = MacCormack
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -203,7 +204,7 @@ class Styler(StylerBase):
         first = st.d[st.mine[0]] if st.mine else (next(iter(st.d.values())) if st.d else
                                                   torch.zeros(tuple(self.resolution), device=self.device))
         st.gs = engine.GridStylizer(self.loss, first, k=self.k, target=self.target, lr=st.lr,
-                                    optimizer=getattr(self, "optimizer", "adam"))
+                                    optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
         st.opt_ = {}
         st.hist = []
         return st
@@ -285,7 +286,9 @@ class Styler(StylerBase):
             if var is None:                                        # trailing frames past the last key frame
                 var = self._initial(t)
             if self.target == "v":
-                d_adv = ops.advect_fwd(st.d[t].unsqueeze(-1), var).squeeze(-1)
+                # (the order the loop optimised through)
+                advect = ops.advect_maccormack if self.adv_order == 2 else ops.advect_fwd
+                d_adv = advect(st.d[t].unsqueeze(-1), var).squeeze(-1)
             else:
                 d_adv = var.reshape(D, H, W_)
             d_out = ops.smooth3d_relu_fwd(d_adv.contiguous(), float(self.k))

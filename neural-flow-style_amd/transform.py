@@ -229,16 +229,36 @@ class _Advect2d(torch.autograd.Function):
         return (None if gd is None else gd.unsqueeze(0)), (None if gv is None else gv.unsqueeze(0))
 
 
+class _AdvectMacCormack(torch.autograd.Function):
+    """order 2, 3-D and 2-D: the forward keeps its first-order sample and the limiter's decisions for the adjoint"""
+
+    @staticmethod
+    def forward(ctx, d, vel):
+        d = d.contiguous(); vel = vel.contiguous()
+        keep = ops.maccormack_mask(d.shape[1:], d)
+        d_fwd = torch.empty_like(d[0])
+        out = ops.advect_maccormack(d[0], vel[0], keep=keep, d_fwd=d_fwd)
+        ctx.save_for_backward(d, vel, d_fwd, keep)
+        return out.unsqueeze(0)
+
+    @staticmethod
+    def backward(ctx, g):
+        d, vel, d_fwd, keep = ctx.saved_tensors
+        gd, gv = ops.advect_maccormack_bwd(d[0], vel[0], d_fwd, keep, g.contiguous()[0], need_d=ctx.needs_input_grad[0],
+                                           need_vel=ctx.needs_input_grad[1])
+        return (None if gd is None else gd.unsqueeze(0)), (None if gv is None else gv.unsqueeze(0))
+
+
 def advect(d, vel, order=1, is_3d=False):
     """semi-Lagrangian step d(x - v) (transform.py:557-609): 3-D d [1,D,H,W,C] + vel [1,D,H,W,3], or 2-D d [1,H,W,C]
-    + vel [1,H,W,2] (``is_3d=False``, the reference's default).  order 1 is differentiable in d and vel; order 2 is
-    the MacCormack scheme with its extrema limiter done as intended (the reference's limiter lines do not run,
-    transform.py:577,598-601), forward only."""
+    + vel [1,H,W,2] (``is_3d=False``, the reference's default).  order 2 is the MacCormack scheme with its extrema
+    limiter done as intended (the reference's limiter lines do not run, transform.py:577,598-601).  Both orders are
+    differentiable in d and vel; the limiter's decision is a comparison and carries no gradient."""
     assert d.shape[0] == 1
     is_3d = bool(is_3d) or d.dim() == 5
     if order == 1:
         return _Advect.apply(d, vel) if is_3d else _Advect2d.apply(d, vel)
-    return ops.advect_maccormack(d.detach()[0].contiguous(), vel.detach()[0].contiguous()).unsqueeze(0)
+    return _AdvectMacCormack.apply(d, vel)
 
 
 class _Warp2d(torch.autograd.Function):
