@@ -626,14 +626,19 @@ int nfs_p2g_wavg_finish(const float* xsum, const float* wsum, float* out, int64_
 /* nfs_p2g_wavg_finish_bwd + nfs_p2g_bwd (mode 2) in ONE launch (round 4): the adjoint of p2g_wavg (transform.py:1577-1704)
  * from g_out [cells,C] = dL/d(finished average), the raw accumulators xsum [cells,C] / wsum [cells] of the forward and
  * the particles: the gradients wrt the accumulators are formed per cell while a block stages its box of the grid, not
- * in a five-array pass over the whole grid.  g_p [N,nd] / g_attr [N,C] overwritten (each nullable).  NFS_EINVAL for
- * (nd, nsize) without a compile-time neighbourhood: use the two-step path then. */
+ * in a five-array pass over the whole grid.  g_p [N,nd] / g_attr [N,C] overwritten (each nullable).  NFS_EINVAL where
+ * nfs_p2g_has_instance answers 0: use the two-step path then. */
 int nfs_p2g_wavg_bwd(const float* p, const float* attr, const float* xsum, const float* wsum, const float* g_out,
                      float* g_p, float* g_attr, int N, int C, float eps, const nfs_splat_cfg* cfg_host,
                      nfs_stream_t stream);
 int nfs_p2g_wavg_finish_bwd(const float* xsum, const float* wsum, const float* g_out,
                             float* g_xsum, float* g_wsum, int64_t n, int C, float eps,
                             nfs_stream_t stream);
+/* 1 when the adjoint of this configuration runs with a compile-time neighbourhood and the block's box of the grid
+ * gradient staged in LDS -- the form nfs_p2g_wavg_bwd needs -- else 0: (nd, nsize) is in splat.hip's one list of
+ * instances, the grid has fewer than 2^31 cells and NFS_SPLAT_LDS is not 0 (read once per process).  Launches
+ * nothing; NFS_EINVAL for a bad configuration. */
+int nfs_p2g_has_instance(const nfs_splat_cfg* cfg_host);
 
 /* ---- g2p_linear / g2p_cubic (transform.py:771-1231) ----------------------
  * g [X,Y,(Z),C] cell-centred grid, p [N,nd] in [0,1] (axis order = array order), out [N,C].

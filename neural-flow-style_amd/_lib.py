@@ -163,6 +163,7 @@ SIGNATURES = {
     "nfs_p2g_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(SplatCfg), _P],
     "nfs_p2g_wavg_finish": [_P, _P, _P, _L, _I, _F, _P],
     "nfs_p2g_wavg_finish_bwd": [_P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "nfs_p2g_has_instance": [C.POINTER(SplatCfg)],
     "nfs_p2g_wavg_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, C.POINTER(SplatCfg), _P],
     "nfs_g2p_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P],
     "nfs_adam_tf_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P],
@@ -182,7 +183,7 @@ _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 153          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 154          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

@@ -1,14 +1,22 @@
 // A8: SPH particle -> grid splat (transform.py:1233-1267 W, 1310-1453 p2g, 1577-1704
 // p2g_wavg) and its adjoint.  The reference issues (2*nsize+1)^d separate ScatterNd ops
-// with N x (d+1) index tensors each; here one thread owns a particle, evaluates the whole
-// neighbourhood in registers and scatters with float atomics (forward) / gathers
-// (backward, no atomics).  HBM-bound: N*(4*nd+4*C) B of particle data + the touched cells.
+// with N x (d+1) index tensors each; here one thread owns a particle and evaluates the whole
+// neighbourhood in registers.  Forward: the (nd, nsize) listed in with_instance have compile-time
+// neighbourhoods and accumulate the cells of a block's 256 particles in 64-bit fixed-point LDS, one
+// global float atomic per touched cell (p2g_fwd_lds_kernel); everything else scatters per cell with
+// global float atomics (p2g_fwd_kernel).  Backward: a gather, no atomics -- from the block's box of
+// the grid gradient staged in LDS for the instances (p2g_bwd_box_kernel), from global memory
+// otherwise (p2g_bwd_kernel).  HBM-bound: N*(4*nd+4*C) B of particle data + the touched cells.
 #include "common.h"
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace nfs {
 
+// nfs_splat_cfg as the kernels read it: the kernel constants (support h, normalisation sigma, particle mass) worked out
+// once on the host (make_dev_cfg)
 struct SplatDev {
   int nd, mode, nsize, clip;
   int res[3];
@@ -69,10 +77,19 @@ __device__ __forceinline__ int64_t cell_index(const SplatDev& s, const int* c) {
   return lin;
 }
 
+// coefficient of a particle's weights: mass (density), mass / density (colour), 1 (raw sums); pdv = the density a colour
+// particle is divided by (the adjoint needs it again), 1 otherwise
+__device__ __forceinline__ float mode_coef(const SplatDev& s, const float* __restrict__ pd, int64_t a, float& pdv) {
+  pdv = (s.mode == 1) ? (pd ? pd[a] : s.rest_density) : 1.f;
+  float coef = 1.f;
+  if (s.mode == 0) coef = s.mass;
+  if (s.mode == 1) coef = s.mass / pdv;
+  return coef;
+}
 
 // The (2 nsize + 1)^nd neighbourhood of a particle with compile-time extents: the per-axis offsets r - n cell and their
-// squares are formed once (3 x SP values instead of 3 per cell), the loops unroll, no integer division (the generic
-// loops below spend ~120 instructions per cell on o / span, o % span with a run-time span).  f(i0, i1, i2, d2) with
+// squares are formed once (3 x SP values instead of 3 per cell), the loops unroll, no integer division (hood_each
+// below spends ~120 instructions per cell on o / span, o % span with a run-time span).  f(i0, i1, i2, d2) with
 // i_k = n_k + NS in [0, SP); rr[k][i_k] = r_k - n_k cell.
 template <int ND, int NS>
 struct Hood {
@@ -103,6 +120,30 @@ struct Hood {
   }
 };
 
+// The same neighbourhood with run-time nd / nsize, for every (nd, nsize) without an instance and for grids of >= 2^31
+// cells: f(c, rr, d2) with c the cell, rr[k] = r_k - n_k cell.  No early-out on d2: the callers form q = sqrtf(d2) / h.
+template <class F>
+__device__ __forceinline__ void hood_each(const SplatDev& s, const Particle& P, F&& f) {
+  const int span = 2 * s.nsize + 1;
+  const int total = s.nd == 2 ? span * span : span * span * span;
+  for (int o = 0; o < total; ++o) {
+    int n[3] = {0, 0, 0};
+    if (s.nd == 2) { n[0] = o / span - s.nsize; n[1] = o % span - s.nsize; }
+    else { n[0] = o / (span * span) - s.nsize; n[1] = (o / span) % span - s.nsize; n[2] = o % span - s.nsize; }
+    float d2 = 0.f, rr[3] = {0.f, 0.f, 0.f};
+    int c[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < s.nd) {
+        rr[k] = P.r[k] - (float)n[k] * s.cell;
+        d2 += rr[k] * rr[k];
+        c[k] = P.idx[k] + n[k];
+      }
+    f(c, rr, d2);
+  }
+}
+
+// The scatter with per-cell global atomics: any nd / nsize, 64-bit cell indices.
 __global__ void __launch_bounds__(256) p2g_fwd_kernel(SplatDev s, const float* __restrict__ p,
                                                       const float* __restrict__ attr, const float* __restrict__ pd,
                                                       float* __restrict__ grid, float* __restrict__ wsum, int N,
@@ -111,34 +152,75 @@ __global__ void __launch_bounds__(256) p2g_fwd_kernel(SplatDev s, const float* _
   if (a >= N) return;
   const Particle P = load_particle(s, p, a);
   if (!P.valid) return;
-  const int span = 2 * s.nsize + 1;
-  const int total = s.nd == 2 ? span * span : span * span * span;
-  float coef = 1.f;
-  if (s.mode == 0) coef = s.mass;
-  if (s.mode == 1) coef = s.mass / (pd ? pd[a] : s.rest_density);
-  for (int o = 0; o < total; ++o) {
-    int n[3] = {0, 0, 0};
-    if (s.nd == 2) { n[0] = o / span - s.nsize; n[1] = o % span - s.nsize; }
-    else { n[0] = o / (span * span) - s.nsize; n[1] = (o / span) % span - s.nsize; n[2] = o % span - s.nsize; }
-    float d2 = 0.f;
-    int c[3];
-    for (int k = 0; k < s.nd; ++k) {
-      const float rr = P.r[k] - (float)n[k] * s.cell;
-      d2 += rr * rr;
-      c[k] = P.idx[k] + n[k];
-    }
+  float pdv;
+  const float coef = mode_coef(s, pd, a, pdv);
+  hood_each(s, P, [&](const int* c, const float*, float d2) {
     const float w = cubic_w(sqrtf(d2) / s.h, s.sigma);
-    if (w == 0.f) continue;
+    if (w == 0.f) return;
     const int64_t ci = cell_index(s, c);
-    if (ci < 0) continue;
+    if (ci < 0) return;
     if (s.mode == 0) {
       atomicAdd(grid + ci, coef * w);
     } else {
       for (int ch = 0; ch < C; ++ch) atomicAdd(grid + ci * C + ch, coef * w * attr[a * C + ch]);
       if (s.mode == 2) atomicAdd(wsum + ci, w);
     }
-  }
+  });
 }
+
+// The box of cells the own cells of a block's 256 particles span, widened by NS and clipped to the grid: what the
+// forward accumulates and the adjoint stages in LDS.  Written once, as statements that expand in the two kernels: behind
+// a function call (a struct's members or free functions alike) the same lines moved the compiler's choice between fma
+// and mul + add in Hood::each's d2 for the (2,1), (2,2), (2,3) adjoints and the (2,2) forward, and with it result bits.
+// NFS_BOX_REDUCE: from each lane's lo / hi (its particle's cell, or 0x7fffffff / -1 without one) to the block's box:
+// defines ext[3], vol (cells of the box) and any (the block has a live particle); red: 6 x 4 ints of LDS; t = threadIdx.x.
+#define NFS_BOX_REDUCE(ND_, NS_)                                                                                         \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                                       \
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) {                                                                \
+      lo[k] = min(lo[k], __shfl_xor(lo[k], o, 64));                                                                      \
+      hi[k] = max(hi[k], __shfl_xor(hi[k], o, 64));                                                                      \
+    }                                                                                                                    \
+    if ((t & 63) == 0) { red[(2 * k) * 4 + (t >> 6)] = lo[k]; red[(2 * k + 1) * 4 + (t >> 6)] = hi[k]; }                 \
+  }                                                                                                                      \
+  __syncthreads();                                                                                                       \
+  int ext[3] = {1, 1, 1};                                                                                                \
+  bool any = true;                                                                                                       \
+  int64_t vol = 1;                                                                                                       \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                                       \
+    const int* r0 = red + (2 * k) * 4;                                                                                   \
+    const int* r1 = red + (2 * k + 1) * 4;                                                                               \
+    lo[k] = min(min(r0[0], r0[1]), min(r0[2], r0[3]));                                                                   \
+    hi[k] = max(max(r1[0], r1[1]), max(r1[2], r1[3]));                                                                   \
+    if (k < ND_) {                                                                                                       \
+      any = any && hi[k] >= lo[k];                                                                                       \
+      lo[k] = max(lo[k] - NS_, 0);                                                                                       \
+      hi[k] = min(hi[k] + NS_, s.res[k] - 1);                                                                            \
+      ext[k] = hi[k] - lo[k] + 1;                                                                                        \
+      vol *= ext[k] > 0 ? ext[k] : 1;                                                                                    \
+    } else {                                                                                                             \
+      lo[k] = 0; hi[k] = 0;                                                                                              \
+    }                                                                                                                    \
+  }
+// NFS_BOX_OFFSETS: defines off[3][SP], the address term of the cell along each axis for Hood's (i0, i1, i2), or -1
+// outside the box (which is clipped to the grid): the slot of a cell is off[0][i0] + off[1][i1] + off[2][i2], and the
+// cell lies outside when their OR is < 0
+#define NFS_BOX_OFFSETS(ND_, NS_)                                                                                        \
+  constexpr int SP = 2 * NS_ + 1;                                                                                        \
+  int off[3][SP];                                                                                                        \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k)                                                                         \
+    _Pragma("unroll") for (int i = 0; i < SP; ++i) {                                                                    \
+      const int c = P.idx[k] + i - NS_;                                                                                  \
+      const bool in = k < ND_ && c >= lo[k] && c <= hi[k];                                                               \
+      const int stride = k == 0 ? ext[1] * ext[2] : (k == 1 ? ext[2] : 1);                                               \
+      off[k][i] = in ? (c - lo[k]) * stride : (k < ND_ ? -1 : 0);                                                        \
+    }
+// NFS_BOX_CELL: defines c[3], the cell of slot i of the box
+#define NFS_BOX_CELL(i_)                                                                                                 \
+  int c[3];                                                                                                              \
+  c[2] = lo[2] + (i_) % ext[2];                                                                                          \
+  const int r = (i_) / ext[2];                                                                                           \
+  c[1] = lo[1] + r % ext[1];                                                                                             \
+  c[0] = lo[0] + r / ext[1];
 
 // The same scatter with the block's cells privatised in LDS.  Particles arrive in the order of the grid (Styler.run
 // sorts them once per sequence, by 8-cell bricks), so the own cells of a block's 256 particles sit in a small box
@@ -179,7 +261,7 @@ __device__ __forceinline__ unsigned long long splat_fix64(float c) {     // c = 
 // (the flush runs at the global-atomic rate, ~85 G/s), more than the 29 us the scattered atomics of those blocks take.
 // Where the 116 us go: block skeleton (reductions, LDS clear, barriers) ~40, accumulation ~45 (neighbouring lanes hold
 // particles of the same cell: same-address LDS atomics serialise), flush ~35, fallback blocks ~29.
-template <int ND, int NS>          // (ND, NS) = (nd, nsize) known at compile time, or ND = 0: generic loops
+template <int ND, int NS>          // (ND, NS) = (nd, nsize) known at compile time
 __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const float* __restrict__ p,
                                                           const float* __restrict__ attr, const float* __restrict__ pd,
                                                           float* __restrict__ grid, float* __restrict__ wsum, int N,
@@ -194,8 +276,8 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
   if (a < N) {
     P = load_particle(s, p, a);
     if (P.valid) {
-      if (s.mode == 0) coef = s.mass;
-      if (s.mode == 1) coef = s.mass / (pd ? pd[a] : s.rest_density);
+      float pdv;
+      coef = mode_coef(s, pd, a, pdv);
       float am = 1.f;
       if (s.mode != 0) {
         am = s.mode == 2 ? 1.f : 0.f;                   // (mode 2 also accumulates the bare weights)
@@ -224,35 +306,15 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
   };
   // the whole neighbourhood of the particle through global atomics
   auto all_global = [&]() {
-    if (ND > 0) {
-      constexpr int NDc = ND > 0 ? ND : 3, NSc = ND > 0 ? NS : 1;
-      Hood<NDc, NSc> hd;
-      hd.init(s, P);
-      hd.each([&](int i0, int i1, int i2, float d2) {
-        if (d2 > h2) return;
-        const float w = weight(d2);
-        if (w == 0.f) return;
-        const int c[3] = {P.idx[0] + i0 - NSc, P.idx[1] + i1 - NSc, NDc > 2 ? P.idx[2] + i2 - NSc : 0};
-        to_global(c, w);
-      });
-    } else {
-      const int span = 2 * s.nsize + 1;
-      const int total = s.nd == 2 ? span * span : span * span * span;
-      for (int o = 0; o < total; ++o) {
-        int n[3] = {0, 0, 0};
-        if (s.nd == 2) { n[0] = o / span - s.nsize; n[1] = o % span - s.nsize; }
-        else { n[0] = o / (span * span) - s.nsize; n[1] = (o / span) % span - s.nsize; n[2] = o % span - s.nsize; }
-        float d2 = 0.f;
-        int c[3] = {0, 0, 0};
-        for (int k = 0; k < s.nd; ++k) {
-          const float rr = P.r[k] - (float)n[k] * s.cell;
-          d2 += rr * rr;
-          c[k] = P.idx[k] + n[k];
-        }
-        const float w = cubic_w(sqrtf(d2) / s.h, s.sigma);
-        if (w != 0.f) to_global(c, w);
-      }
-    }
+    Hood<ND, NS> hd;
+    hd.init(s, P);
+    hd.each([&](int i0, int i1, int i2, float d2) {
+      if (d2 > h2) return;
+      const float w = weight(d2);
+      if (w == 0.f) return;
+      const int c[3] = {P.idx[0] + i0 - NS, P.idx[1] + i1 - NS, ND > 2 ? P.idx[2] + i2 - NS : 0};
+      to_global(c, w);
+    });
   };
   // block-wide maximum of cmax -> fixed-point scale 2^kexp: |any cell sum| <= 256 sigma cmax < 2^ebound stays below 2^62
 #pragma unroll
@@ -272,44 +334,15 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
     fs = ldexpf(1.f, k1);
     fs2 = ldexpf(1.f, ks - k1);                               // (2^ks may exceed the float range: two factors)
   }
-  if (!(allow_lds && scalable && ND > 0)) {                   // generic neighbourhoods / unscalable values: global atomics
+  if (!(allow_lds && scalable)) {                             // NFS_SPLAT_LDS=0 / unscalable values: global atomics
     if (P.valid) all_global();
     return;
   }
-  constexpr int NDc = ND > 0 ? ND : 3, NSc = ND > 0 ? NS : 1;
   int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
   if (P.valid)
 #pragma unroll
     for (int k = 0; k < 3; ++k) { lo[k] = P.idx[k]; hi[k] = P.idx[k]; }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[k] = min(lo[k], __shfl_xor(lo[k], o, 64));
-      hi[k] = max(hi[k], __shfl_xor(hi[k], o, 64));
-    }
-    if ((t & 63) == 0) { red[(2 * k) * 4 + (t >> 6)] = lo[k]; red[(2 * k + 1) * 4 + (t >> 6)] = hi[k]; }
-  }
-  __syncthreads();
-  int ext[3] = {1, 1, 1};
-  bool any = true;
-  int64_t vol = 1;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int* r0 = red + (2 * k) * 4;
-    const int* r1 = red + (2 * k + 1) * 4;
-    lo[k] = min(min(r0[0], r0[1]), min(r0[2], r0[3]));
-    hi[k] = max(max(r1[0], r1[1]), max(r1[2], r1[3]));
-    if (k < NDc) {
-      any = any && hi[k] >= lo[k];
-      lo[k] = max(lo[k] - NSc, 0);
-      hi[k] = min(hi[k] + NSc, s.res[k] - 1);
-      ext[k] = hi[k] - lo[k] + 1;
-      vol *= ext[k] > 0 ? ext[k] : 1;
-    } else {
-      lo[k] = 0; hi[k] = 0;
-    }
-  }
+  NFS_BOX_REDUCE(ND, NS)
   if (!any) return;                                           // no live particle in the block
   if (vol * nch > SPL_LDS) {
     if (P.valid) all_global();
@@ -319,19 +352,9 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
   for (int i = t; i < nvol * nch; i += 256) acc[i] = 0ull;
   __syncthreads();
   if (P.valid) {
-    Hood<NDc, NSc> hd;
+    Hood<ND, NS> hd;
     hd.init(s, P);
-    constexpr int SP = 2 * NSc + 1;
-    int off[3][SP];                  // address term of the cell along each axis, or -1 outside the grid
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int i = 0; i < SP; ++i) {
-        const int c = P.idx[k] + i - NSc;
-        const bool in = k < NDc && c >= lo[k] && c <= hi[k];        // (the box is clipped to the grid)
-        const int stride = k == 0 ? ext[1] * ext[2] : (k == 1 ? ext[2] : 1);
-        off[k][i] = in ? (c - lo[k]) * stride : (k < NDc ? -1 : 0);
-      }
+    NFS_BOX_OFFSETS(ND, NS)
     hd.each([&](int i0, int i1, int i2, float d2) {
       if (d2 > h2) return;
       if ((off[0][i0] | off[1][i1] | off[2][i2]) < 0) return;
@@ -348,11 +371,7 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
   }
   __syncthreads();
   for (int i = t; i < nvol; i += 256) {
-    int c[3];
-    c[2] = lo[2] + i % ext[2];
-    const int r = i / ext[2];
-    c[1] = lo[1] + r % ext[1];
-    c[0] = lo[0] + r / ext[1];
+    NFS_BOX_CELL(i)
     const unsigned long long* src = acc + (int64_t)i * nch;
     bool nz = false;
     for (int ch = 0; ch < nch; ++ch) nz = nz || src[ch] != 0ull;
@@ -370,6 +389,85 @@ __global__ void __launch_bounds__(256) p2g_fwd_lds_kernel(SplatDev s, const floa
   }
 }
 
+
+// WAVG: mode 2 with the adjoint of nfs_p2g_wavg_finish folded in -- g_grid is then dL/d(out) of the finished average,
+// fin.xsum / fin.wsum the raw accumulators, and the gradients wrt the accumulators are formed per cell while the box is
+// staged, instead of in a 5-array streaming pass over the whole grid (240 MB at 200 x 300 x 200).
+struct WavgFinish { const float* xsum; const float* wsum; float eps; };
+
+// adjoint of the weighted-average finish for one cell: gx[ch] = g / w and the return value -sum g x / w^2 where w > eps,
+// g and 0 elsewhere
+__device__ __forceinline__ float wavg_finish_adj(const WavgFinish& fin, const float* __restrict__ g_out, int64_t cell,
+                                                 int C, float* gx) {
+  const float w = fin.wsum[cell];
+  float gw = 0.f;
+  for (int ch = 0; ch < C; ++ch) {
+    const float g = g_out[cell * C + ch];
+    if (w > fin.eps) {
+      gx[ch] = g / w;
+      gw -= g * fin.xsum[cell * C + ch] / (w * w);
+    } else {
+      gx[ch] = g;
+    }
+  }
+  return gw;
+}
+
+// the gradient of one cell as the adjoint reads it: gv[0..C) per channel, gv[C] wrt the weight sum (mode 2)
+template <bool WAVG>
+__device__ __forceinline__ void load_cell_grad(const SplatDev& s, const float* __restrict__ g_grid,
+                                               const float* __restrict__ g_wsum, const WavgFinish& fin, int64_t cell,
+                                               int C, float* gv) {
+  if (WAVG) {
+    gv[C] = wavg_finish_adj(fin, g_grid, cell, C, gv);
+  } else {
+    for (int ch = 0; ch < C; ++ch) gv[ch] = g_grid[cell * C + ch];
+    if (s.mode == 2) gv[C] = g_wsum[cell];
+  }
+}
+
+// One cell of a particle's neighbourhood added to its gradients gp / ga / gpd: gv the cell's gradient (load_cell_grad),
+// q = |r| / h, rr the offsets r_k - n_k cell; over_dist_h(x) = x / (|r| h) in the caller's own arithmetic (the generic
+// kernel divides, the box kernel multiplies by the rsq it already holds: the one place where the two differ).
+template <class F>
+__device__ __forceinline__ void adj_cell(const SplatDev& s, int nd, int C, float coef, float pdv, const float* at,
+                                         const float* gv, float q, const float* rr, bool radial, F&& over_dist_h,
+                                         float* gp, float* ga, float& gpd) {
+  const float w = cubic_w(q, s.sigma);
+  // dL/dW for this (particle, cell)
+  float gw;
+  if (s.mode == 0) {
+    gw = coef * gv[0];
+  } else {
+    float dot = 0.f;
+    for (int ch = 0; ch < C; ++ch) {
+      dot += at[ch] * gv[ch];
+      ga[ch] += coef * w * gv[ch];
+    }
+    // (mode 2 as ONE fma, the form both adjoints have always compiled to; written out so that it cannot move)
+    gw = s.mode == 2 ? __fmaf_rn(coef, dot, gv[C]) : coef * dot;
+    if (s.mode == 1) gpd -= coef * w * dot / pdv;
+  }
+  if (radial) {  // safe sqrt: zero gradient at the cell centre
+    const float f = over_dist_h(gw * cubic_dw(q, s.sigma));
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < nd) gp[k] += f * rr[k];
+  }
+}
+
+// the final stores of a particle's gradients
+__device__ __forceinline__ void adj_store(const SplatDev& s, const Particle& P, int64_t a, int nd, int C, const float* gp,
+                                          const float* ga, float gpd, float* __restrict__ g_p,
+                                          float* __restrict__ g_attr, float* __restrict__ g_pd) {
+  if (g_p)
+    for (int k = 0; k < nd; ++k) g_p[a * nd + k] = P.grad_ok[k] ? gp[k] * s.dom[k] : 0.f;
+  if (g_attr)
+    for (int ch = 0; ch < C; ++ch) g_attr[a * C + ch] = ga[ch];
+  if (g_pd) g_pd[a] = gpd;
+}
+
+// The gather from global memory: any nd / nsize, 64-bit cell indices.
 __global__ void __launch_bounds__(256) p2g_bwd_kernel(SplatDev s, const float* __restrict__ p,
                                                       const float* __restrict__ attr, const float* __restrict__ pd,
                                                       const float* __restrict__ g_grid,
@@ -383,69 +481,31 @@ __global__ void __launch_bounds__(256) p2g_bwd_kernel(SplatDev s, const float* _
   float ga[4] = {0.f, 0.f, 0.f, 0.f};  // C <= 4
   float gpd = 0.f;
   if (P.valid) {
-    const int span = 2 * s.nsize + 1;
-    const int total = s.nd == 2 ? span * span : span * span * span;
-    const float pdv = (s.mode == 1) ? (pd ? pd[a] : s.rest_density) : 1.f;
-    float coef = 1.f;
-    if (s.mode == 0) coef = s.mass;
-    if (s.mode == 1) coef = s.mass / pdv;
-    for (int o = 0; o < total; ++o) {
-      int n[3] = {0, 0, 0};
-      if (s.nd == 2) { n[0] = o / span - s.nsize; n[1] = o % span - s.nsize; }
-      else { n[0] = o / (span * span) - s.nsize; n[1] = (o / span) % span - s.nsize; n[2] = o % span - s.nsize; }
-      float d2 = 0.f, rr[3] = {0.f, 0.f, 0.f};
-      int c[3];
-      for (int k = 0; k < s.nd; ++k) {
-        rr[k] = P.r[k] - (float)n[k] * s.cell;
-        d2 += rr[k] * rr[k];
-        c[k] = P.idx[k] + n[k];
-      }
+    float pdv;
+    const float coef = mode_coef(s, pd, a, pdv);
+    const float* at = attr + a * C;          // (read per cell, as in the forward)
+    hood_each(s, P, [&](const int* c, const float* rr, float d2) {
       const float dist = sqrtf(d2);
       const float q = dist / s.h;
-      if (q > 1.f) continue;
+      if (q > 1.f) return;
       const int64_t ci = cell_index(s, c);
-      if (ci < 0) continue;
-      const float w = cubic_w(q, s.sigma);
-      // dL/dW for this (particle, cell)
-      float gw;
-      if (s.mode == 0) {
-        gw = coef * g_grid[ci];
-      } else {
-        float dot = 0.f;
-        for (int ch = 0; ch < C; ++ch) {
-          const float g = g_grid[ci * C + ch];
-          dot += attr[a * C + ch] * g;
-          ga[ch] += coef * w * g;
-        }
-        gw = coef * dot;
-        if (s.mode == 1) gpd -= coef * w * dot / pdv;
-        if (s.mode == 2) gw += g_wsum[ci];
-      }
-      if (g_p && dist > 0.f) {  // safe sqrt: zero gradient at the cell centre
-        const float f = gw * cubic_dw(q, s.sigma) / (dist * s.h);
-        for (int k = 0; k < s.nd; ++k) gp[k] += f * rr[k];
-      }
-    }
+      if (ci < 0) return;
+      float gv[5];
+      load_cell_grad<false>(s, g_grid, g_wsum, WavgFinish{nullptr, nullptr, 0.f}, ci, C, gv);
+      adj_cell(s, s.nd, C, coef, pdv, at, gv, q, rr, g_p && dist > 0.f, [&](float x) { return x / (dist * s.h); }, gp, ga,
+               gpd);
+    });
   }
-  if (g_p)
-    for (int k = 0; k < s.nd; ++k) g_p[a * s.nd + k] = P.grad_ok[k] ? gp[k] * s.dom[k] : 0.f;
-  if (g_attr)
-    for (int ch = 0; ch < C; ++ch) g_attr[a * C + ch] = ga[ch];
-  if (g_pd) g_pd[a] = gpd;
+  adj_store(s, P, a, s.nd, C, gp, ga, gpd, g_p, g_attr, g_pd);
 }
 
 // The adjoint with compile-time neighbourhoods and the block's box of the grid gradient staged in LDS: the 256 particles
 // of a block (grid order) read the same ~1000 cells 27 times between them -- one coalesced pass brings them in, the
-// gathers are LDS reads.  Same per-cell arithmetic and the same order of the sums as p2g_bwd_kernel (cells in the
-// order of the generic loop: axis 0 outermost), so the two agree bit for bit; a block whose box does not fit falls
-// back to global gathers.
+// gathers are LDS reads.  Same per-cell sums in the same order as p2g_bwd_kernel (cells in the order of the generic
+// loop: axis 0 outermost), but not the same bits: q and 1 / (|r| h) come from one rsq here, from sqrtf and divisions
+// there (1-2 ulp; each is held to the float64 bound of tests/splat_ref.py on its own).  A block whose box does not fit
+// falls back to global gathers with this kernel's arithmetic.
 constexpr int SPB_LDS = 12288;     // floats of staged gradient (48 KB)
-
-// WAVG: mode 2 with the adjoint of nfs_p2g_wavg_finish folded in -- g_grid is then dL/d(out) of the finished average,
-// fin.xsum / fin.wsum the raw accumulators, and the gradients wrt the accumulators (g / w and -sum g x / w^2 where
-// w > eps, g and 0 elsewhere: wavg_finish_bwd_kernel's lines) are formed per cell while the box is staged, instead of
-// in a 5-array streaming pass over the whole grid (240 MB at 200 x 300 x 200).
-struct WavgFinish { const float* xsum; const float* wsum; float eps; };
 
 template <int ND, int NS, bool WAVG>
 __global__ void __launch_bounds__(256) p2g_bwd_box_kernel(SplatDev s, const float* __restrict__ p,
@@ -467,35 +527,7 @@ __global__ void __launch_bounds__(256) p2g_bwd_box_kernel(SplatDev s, const floa
 #pragma unroll
       for (int k = 0; k < 3; ++k) { lo[k] = P.idx[k]; hi[k] = P.idx[k]; }
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[k] = min(lo[k], __shfl_xor(lo[k], o, 64));
-      hi[k] = max(hi[k], __shfl_xor(hi[k], o, 64));
-    }
-    if ((t & 63) == 0) { red[(2 * k) * 4 + (t >> 6)] = lo[k]; red[(2 * k + 1) * 4 + (t >> 6)] = hi[k]; }
-  }
-  __syncthreads();
-  int ext[3] = {1, 1, 1};
-  bool any = true;
-  int64_t vol = 1;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int* r0 = red + (2 * k) * 4;
-    const int* r1 = red + (2 * k + 1) * 4;
-    lo[k] = min(min(r0[0], r0[1]), min(r0[2], r0[3]));
-    hi[k] = max(max(r1[0], r1[1]), max(r1[2], r1[3]));
-    if (k < ND) {
-      any = any && hi[k] >= lo[k];
-      lo[k] = max(lo[k] - NS, 0);
-      hi[k] = min(hi[k] + NS, s.res[k] - 1);
-      ext[k] = hi[k] - lo[k] + 1;
-      vol *= ext[k] > 0 ? ext[k] : 1;
-    } else {
-      lo[k] = 0; hi[k] = 0;
-    }
-  }
+  NFS_BOX_REDUCE(ND, NS)
   if (!any) {                                  // no live particle in the block: zero gradients
     if (a < N) {
       if (g_p) for (int k = 0; k < ND; ++k) g_p[a * ND + k] = 0.f;
@@ -509,29 +541,8 @@ __global__ void __launch_bounds__(256) p2g_bwd_box_kernel(SplatDev s, const floa
   const int nvol = (int)vol;
   if (staged) {
     for (int i = t; i < nvol; i += 256) {
-      int c[3];
-      c[2] = lo[2] + i % ext[2];
-      const int r = i / ext[2];
-      c[1] = lo[1] + r % ext[1];
-      c[0] = lo[0] + r / ext[1];
-      const int64_t cell = cell_index(s, c);
-      if (WAVG) {
-        const float w = fin.wsum[cell];
-        float gw = 0.f;
-        for (int ch = 0; ch < C; ++ch) {
-          const float g = g_grid[cell * C + ch];
-          if (w > fin.eps) {
-            gbox[i * nch + ch] = g / w;
-            gw -= g * fin.xsum[cell * C + ch] / (w * w);
-          } else {
-            gbox[i * nch + ch] = g;
-          }
-        }
-        gbox[i * nch + C] = gw;
-      } else {
-        for (int ch = 0; ch < C; ++ch) gbox[i * nch + ch] = g_grid[cell * C + ch];
-        if (s.mode == 2) gbox[i * nch + C] = g_wsum[cell];
-      }
+      NFS_BOX_CELL(i)
+      load_cell_grad<WAVG>(s, g_grid, g_wsum, fin, cell_index(s, c), C, gbox + i * nch);
     }
     __syncthreads();
   }
@@ -540,26 +551,14 @@ __global__ void __launch_bounds__(256) p2g_bwd_box_kernel(SplatDev s, const floa
   float ga[4] = {0.f, 0.f, 0.f, 0.f};  // C <= 4
   float gpd = 0.f;
   if (P.valid) {
-    const float pdv = (s.mode == 1) ? (pd ? pd[a] : s.rest_density) : 1.f;
-    float coef = 1.f;
-    if (s.mode == 0) coef = s.mass;
-    if (s.mode == 1) coef = s.mass / pdv;
+    float pdv;
+    const float coef = mode_coef(s, pd, a, pdv);
     float at[4] = {0.f, 0.f, 0.f, 0.f};
     if (s.mode != 0)
       for (int ch = 0; ch < C; ++ch) at[ch] = attr[a * C + ch];
     Hood<ND, NS> hd;
     hd.init(s, P);
-    constexpr int SP = 2 * NS + 1;
-    int off[3][SP];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int i = 0; i < SP; ++i) {
-        const int c = P.idx[k] + i - NS;
-        const bool in = k < ND && c >= lo[k] && c <= hi[k];
-        const int stride = k == 0 ? ext[1] * ext[2] : (k == 1 ? ext[2] : 1);
-        off[k][i] = in ? (c - lo[k]) * stride : (k < ND ? -1 : 0);
-      }
+    NFS_BOX_OFFSETS(ND, NS)
     const float h2 = s.h * s.h, inv_h = 1.f / s.h;
     hd.each([&](int i0, int i1, int i2, float d2) {
       if (d2 > h2) return;
@@ -574,52 +573,15 @@ __global__ void __launch_bounds__(256) p2g_bwd_box_kernel(SplatDev s, const floa
         for (int ch = 0; ch < nch; ++ch) gv[ch] = gbox[li * nch + ch];
       } else {
         const int c[3] = {P.idx[0] + i0 - NS, P.idx[1] + i1 - NS, P.idx[2] + i2 - NS};
-        const int64_t ci = cell_index(s, c);
-        if (WAVG) {
-          const float ws_ = fin.wsum[ci];
-          float gws = 0.f;
-          for (int ch = 0; ch < C; ++ch) {
-            const float g = g_grid[ci * C + ch];
-            if (ws_ > fin.eps) {
-              gv[ch] = g / ws_;
-              gws -= g * fin.xsum[ci * C + ch] / (ws_ * ws_);
-            } else {
-              gv[ch] = g;
-            }
-          }
-          gv[C] = gws;
-        } else {
-          for (int ch = 0; ch < C; ++ch) gv[ch] = g_grid[ci * C + ch];
-          if (s.mode == 2) gv[C] = g_wsum[ci];
-        }
+        load_cell_grad<WAVG>(s, g_grid, g_wsum, fin, cell_index(s, c), C, gv);
       }
-      const float w = cubic_w(q, s.sigma);
-      float gw;
-      if (s.mode == 0) {
-        gw = coef * gv[0];
-      } else {
-        float dot = 0.f;
-        for (int ch = 0; ch < C; ++ch) {
-          dot += at[ch] * gv[ch];
-          ga[ch] += coef * w * gv[ch];
-        }
-        gw = coef * dot;
-        if (s.mode == 1) gpd -= coef * w * dot / pdv;
-        if (s.mode == 2) gw += gv[C];
-      }
-      if (g_p && dist > 0.f) {  // safe sqrt: zero gradient at the cell centre
-        const float f = gw * cubic_dw(q, s.sigma) * (inv_d * inv_h);
-        gp[0] += f * hd.rr[0][i0];
-        if (ND > 1) gp[1] += f * hd.rr[1][i1];
-        if (ND > 2) gp[2] += f * hd.rr[2][i2];
-      }
+      const float rr[3] = {hd.rr[0][i0], hd.rr[1][i1], hd.rr[2][i2]};
+      const float over = inv_d * inv_h;
+      adj_cell(s, ND, C, coef, pdv, at, gv, q, rr, g_p && dist > 0.f, [&](float x) { return x * over; }, gp,
+               ga, gpd);
     });
   }
-  if (g_p)
-    for (int k = 0; k < ND; ++k) g_p[a * ND + k] = P.grad_ok[k] ? gp[k] * s.dom[k] : 0.f;
-  if (g_attr)
-    for (int ch = 0; ch < C; ++ch) g_attr[a * C + ch] = ga[ch];
-  if (g_pd) g_pd[a] = gpd;
+  adj_store(s, P, a, ND, C, gp, ga, gpd, g_p, g_attr, g_pd);
 }
 
 __global__ void __launch_bounds__(256) wavg_finish_kernel(const float* __restrict__ xsum,
@@ -631,25 +593,12 @@ __global__ void __launch_bounds__(256) wavg_finish_kernel(const float* __restric
   for (int c = 0; c < C; ++c) out[i * C + c] = w > eps ? xsum[i * C + c] / w : xsum[i * C + c];
 }
 
-__global__ void __launch_bounds__(256) wavg_finish_bwd_kernel(const float* __restrict__ xsum,
-                                                              const float* __restrict__ wsum,
-                                                              const float* __restrict__ g_out,
+__global__ void __launch_bounds__(256) wavg_finish_bwd_kernel(WavgFinish fin, const float* __restrict__ g_out,
                                                               float* __restrict__ g_xsum, float* __restrict__ g_wsum,
-                                                              int64_t n, int C, float eps) {
+                                                              int64_t n, int C) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float w = wsum[i];
-  float gw = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float g = g_out[i * C + c];
-    if (w > eps) {
-      g_xsum[i * C + c] = g / w;
-      gw -= g * xsum[i * C + c] / (w * w);
-    } else {
-      g_xsum[i * C + c] = g;
-    }
-  }
-  g_wsum[i] = gw;
+  g_wsum[i] = wavg_finish_adj(fin, g_out, i, C, g_xsum + i * C);
 }
 
 static int make_dev_cfg(const nfs_splat_cfg* c, int C, SplatDev& s) {
@@ -737,6 +686,44 @@ __global__ void __launch_bounds__(256) g2p_kernel(G2PArgs a) {
   }
 }
 
+// ---- which kernel runs -------------------------------------------------------------------------------------------------
+// THE list of compile-time (nd, nsize) instances (test_smokegun / chocolate: 3-D nsize 1; test_dambreak2d: 2-D nsize
+// 2..4): f(ND, NS) as integral constants for the one that matches, false when there is none.  Both launchers and
+// nfs_p2g_has_instance dispatch from here; an instance is added by adding its line.
+template <class F>
+static bool with_instance(const SplatDev& s, F&& f) {
+#define NFS_SPLAT_INSTANCE(ND_, NS_)                                                        \
+  if (s.nd == ND_ && s.nsize == NS_) {                                                      \
+    f(std::integral_constant<int, ND_>{}, std::integral_constant<int, NS_>{});              \
+    return true;                                                                            \
+  }
+  NFS_SPLAT_INSTANCE(3, 1)
+  NFS_SPLAT_INSTANCE(3, 2)
+  NFS_SPLAT_INSTANCE(2, 1)
+  NFS_SPLAT_INSTANCE(2, 2)
+  NFS_SPLAT_INSTANCE(2, 3)
+  NFS_SPLAT_INSTANCE(2, 4)
+#undef NFS_SPLAT_INSTANCE
+  return false;
+}
+
+// the instanced kernels keep linear cell indices in 32 bits
+static bool fits_int32(const SplatDev& s) {
+  int64_t cells = 1;
+  for (int k = 0; k < s.nd; ++k) cells *= s.res[k];
+  return cells < ((int64_t)1 << 31);
+}
+
+// NFS_SPLAT_LDS=0: no LDS staging (read once per process)
+static bool splat_lds() {
+  static const int on = [] { const char* e = getenv("NFS_SPLAT_LDS"); return e ? atoi(e) : 1; }();
+  return on != 0;
+}
+
+// the adjoint runs as p2g_bwd_box_kernel (and with it the one-launch weighted-average adjoint exists)
+static bool has_box_adjoint(const SplatDev& s) {
+  return splat_lds() && fits_int32(s) && with_instance(s, [](auto, auto) {});
+}
 
 // p2g adjoint launch: compile-time neighbourhoods with the box staged in LDS where they exist, the generic gather otherwise;
 // fin != nullptr (mode 2): the adjoint of the weighted-average finish folded in (the generic kernel has no such form:
@@ -744,32 +731,22 @@ __global__ void __launch_bounds__(256) g2p_kernel(G2PArgs a) {
 static bool launch_p2g_bwd(const SplatDev& s, const float* p, const float* attr, const float* pd, const float* g_grid,
                            const float* g_wsum, float* g_p, float* g_attr, float* g_pd, int N, int C,
                            const WavgFinish* fin, hipStream_t stream) {
-  int64_t cells = 1;
-  for (int k = 0; k < s.nd; ++k) cells *= s.res[k];
-  static const int allow_box = [] { const char* e = getenv("NFS_SPLAT_LDS"); return e ? atoi(e) : 1; }();
-  const bool box = allow_box && cells < ((int64_t)1 << 31);
   const WavgFinish f = fin ? *fin : WavgFinish{nullptr, nullptr, 0.f};
-#define NFS_SPB_LAUNCH(ND_, NS_)                                                                                       \
-  do {                                                                                                                 \
-    if (fin)                                                                                                           \
-      hipLaunchKernelGGL((p2g_bwd_box_kernel<ND_, NS_, true>), dim3(blocks_for(N, 256)), dim3(256),                    \
-                         SPB_LDS * sizeof(float), stream, s, p, attr, pd, g_grid, g_wsum, g_p, g_attr, g_pd, N, C, f); \
-    else                                                                                                               \
-      hipLaunchKernelGGL((p2g_bwd_box_kernel<ND_, NS_, false>), dim3(blocks_for(N, 256)), dim3(256),                   \
-                         SPB_LDS * sizeof(float), stream, s, p, attr, pd, g_grid, g_wsum, g_p, g_attr, g_pd, N, C, f); \
-  } while (0)
-  if (box && s.nd == 3 && s.nsize == 1) NFS_SPB_LAUNCH(3, 1);
-  else if (box && s.nd == 3 && s.nsize == 2) NFS_SPB_LAUNCH(3, 2);
-  else if (box && s.nd == 2 && s.nsize == 1) NFS_SPB_LAUNCH(2, 1);
-  else if (box && s.nd == 2 && s.nsize == 2) NFS_SPB_LAUNCH(2, 2);
-  else if (box && s.nd == 2 && s.nsize == 3) NFS_SPB_LAUNCH(2, 3);
-  else if (box && s.nd == 2 && s.nsize == 4) NFS_SPB_LAUNCH(2, 4);
-  else {
-    if (fin) return false;
-    hipLaunchKernelGGL(p2g_bwd_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, stream, s, p, attr, pd, g_grid, g_wsum, g_p,
-                       g_attr, g_pd, N, C);
+  if (has_box_adjoint(s)) {
+    with_instance(s, [&](auto nd, auto ns) {
+      constexpr int ND = decltype(nd)::value, NS = decltype(ns)::value;
+      if (fin)
+        hipLaunchKernelGGL((p2g_bwd_box_kernel<ND, NS, true>), dim3(blocks_for(N, 256)), dim3(256),
+                           SPB_LDS * sizeof(float), stream, s, p, attr, pd, g_grid, g_wsum, g_p, g_attr, g_pd, N, C, f);
+      else
+        hipLaunchKernelGGL((p2g_bwd_box_kernel<ND, NS, false>), dim3(blocks_for(N, 256)), dim3(256),
+                           SPB_LDS * sizeof(float), stream, s, p, attr, pd, g_grid, g_wsum, g_p, g_attr, g_pd, N, C, f);
+    });
+    return true;
   }
-#undef NFS_SPB_LAUNCH
+  if (fin) return false;
+  hipLaunchKernelGGL(p2g_bwd_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, stream, s, p, attr, pd, g_grid, g_wsum, g_p,
+                     g_attr, g_pd, N, C);
   return true;
 }
 
@@ -779,6 +756,12 @@ using namespace nfs;
 
 extern "C" {
 
+int nfs_p2g_has_instance(const nfs_splat_cfg* cfg_host) {
+  SplatDev s;
+  if (int e = make_dev_cfg(cfg_host, 1, s)) return e;
+  return has_box_adjoint(s) ? 1 : 0;
+}
+
 int nfs_p2g_fwd(const float* p, const float* attr, const float* pd, float* grid, float* wsum, int N, int C,
                 const nfs_splat_cfg* cfg_host, nfs_stream_t stream) {
   NFS_REQUIRE(p && grid && N > 0, "nfs_p2g_fwd: bad argument");
@@ -787,28 +770,16 @@ int nfs_p2g_fwd(const float* p, const float* attr, const float* pd, float* grid,
   NFS_REQUIRE(s.mode == 0 || attr, "nfs_p2g_fwd: attr required for mode 1/2");
   NFS_REQUIRE(s.mode != 2 || wsum, "nfs_p2g_fwd: wsum required for mode 2");
   NFS_REQUIRE(s.mode != 0 || C == 1, "nfs_p2g_fwd: density mode has C=1");
-  int64_t cells = 1;
-  for (int k = 0; k < s.nd; ++k) cells *= s.res[k];
-  if (cells >= ((int64_t)1 << 31)) {                 // (the LDS form keeps linear cell indices in 32 bits)
+  // 256 particles per block: measured 0.156 ms against 0.184 (512) and 0.247 (1024) on the 5e5-particle blob set.
+  // NFS_SPLAT_LDS=0 keeps an instance's kernel and sends it down its global-atomic branch.
+  const bool instanced = fits_int32(s) && with_instance(s, [&](auto nd, auto ns) {
+    hipLaunchKernelGGL((p2g_fwd_lds_kernel<decltype(nd)::value, decltype(ns)::value>), dim3(blocks_for(N, 256)), dim3(256),
+                       SPL_LDS * sizeof(unsigned long long), as_stream(stream), s, p, attr, pd, grid, wsum, N, C,
+                       (int)splat_lds());
+  });
+  if (!instanced)
     hipLaunchKernelGGL(p2g_fwd_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, as_stream(stream), s, p, attr, pd, grid,
                        wsum, N, C);
-    return check_launch("nfs_p2g_fwd");
-  }
-  static const int allow_lds = [] { const char* e = getenv("NFS_SPLAT_LDS"); return e ? atoi(e) : 1; }();
-  // 256 particles per block: measured 0.156 ms against 0.184 (512) and 0.247 (1024) on the 5e5-particle blob set
-#define NFS_SPL_LAUNCH(ND_, NS_)                                                                                       \
-  hipLaunchKernelGGL((p2g_fwd_lds_kernel<ND_, NS_>), dim3(blocks_for(N, 256)), dim3(256),                         \
-                     SPL_LDS * sizeof(unsigned long long), as_stream(stream), s, p, attr, pd, grid, wsum, N, C, allow_lds)
-  // the neighbourhoods the drivers use as compile-time instances (test_smokegun / chocolate: 3-D nsize 1;
-  // test_dambreak2d: 2-D nsize 2..4), anything else through the generic loops
-  if (s.nd == 3 && s.nsize == 1) NFS_SPL_LAUNCH(3, 1);
-  else if (s.nd == 3 && s.nsize == 2) NFS_SPL_LAUNCH(3, 2);
-  else if (s.nd == 2 && s.nsize == 1) NFS_SPL_LAUNCH(2, 1);
-  else if (s.nd == 2 && s.nsize == 2) NFS_SPL_LAUNCH(2, 2);
-  else if (s.nd == 2 && s.nsize == 3) NFS_SPL_LAUNCH(2, 3);
-  else if (s.nd == 2 && s.nsize == 4) NFS_SPL_LAUNCH(2, 4);
-  else NFS_SPL_LAUNCH(0, 0);
-#undef NFS_SPL_LAUNCH
   return check_launch("nfs_p2g_fwd");
 }
 
@@ -820,13 +791,14 @@ int nfs_p2g_bwd(const float* p, const float* attr, const float* pd, const float*
   if (int e = make_dev_cfg(cfg_host, C, s)) return e;
   NFS_REQUIRE(s.mode == 0 || attr, "nfs_p2g_bwd: attr required for mode 1/2");
   NFS_REQUIRE(s.mode != 2 || g_wsum, "nfs_p2g_bwd: g_wsum required for mode 2");
+  NFS_REQUIRE(s.mode != 0 || C == 1, "nfs_p2g_bwd: density mode has C=1");
   NFS_REQUIRE(s.mode != 0 || (!g_attr && !g_pd), "nfs_p2g_bwd: density mode has no attr/pd gradient");
   (void)launch_p2g_bwd(s, p, attr, pd, g_grid, g_wsum, g_p, g_attr, g_pd, N, C, nullptr, as_stream(stream));
   return check_launch("nfs_p2g_bwd");
 }
 
 /* nfs_p2g_wavg_finish_bwd + nfs_p2g_bwd (mode 2) in one launch: g_out [cells,C] = dL/d(finished average); returns
- * NFS_EINVAL for neighbourhoods without a compile-time instance (the caller then takes the two-step path) */
+ * NFS_EINVAL where nfs_p2g_has_instance answers 0 (the caller then takes the two-step path) */
 int nfs_p2g_wavg_bwd(const float* p, const float* attr, const float* xsum, const float* wsum, const float* g_out,
                      float* g_p, float* g_attr, int N, int C, float eps, const nfs_splat_cfg* cfg_host,
                      nfs_stream_t stream) {
@@ -836,7 +808,8 @@ int nfs_p2g_wavg_bwd(const float* p, const float* attr, const float* xsum, const
   NFS_REQUIRE(s.mode == 2, "nfs_p2g_wavg_bwd: mode 2 (weighted average) only");
   const WavgFinish fin{xsum, wsum, eps};
   NFS_REQUIRE(launch_p2g_bwd(s, p, attr, nullptr, g_out, nullptr, g_p, g_attr, nullptr, N, C, &fin, as_stream(stream)),
-              "nfs_p2g_wavg_bwd: no compile-time instance for nd %d, nsize %d (use nfs_p2g_wavg_finish_bwd + nfs_p2g_bwd)",
+              "nfs_p2g_wavg_bwd: nfs_p2g_has_instance is 0 for nd %d, nsize %d (no instance, >= 2^31 cells or "
+              "NFS_SPLAT_LDS=0): use nfs_p2g_wavg_finish_bwd + nfs_p2g_bwd",
               s.nd, s.nsize);
   return check_launch("nfs_p2g_wavg_bwd");
 }
@@ -852,8 +825,8 @@ int nfs_p2g_wavg_finish(const float* xsum, const float* wsum, float* out, int64_
 int nfs_p2g_wavg_finish_bwd(const float* xsum, const float* wsum, const float* g_out, float* g_xsum, float* g_wsum,
                             int64_t n, int C, float eps, nfs_stream_t stream) {
   NFS_REQUIRE(xsum && wsum && g_out && g_xsum && g_wsum && n > 0 && C > 0, "nfs_p2g_wavg_finish_bwd: bad argument");
-  hipLaunchKernelGGL(wavg_finish_bwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), xsum, wsum,
-                     g_out, g_xsum, g_wsum, n, C, eps);
+  hipLaunchKernelGGL(wavg_finish_bwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream),
+                     WavgFinish{xsum, wsum, eps}, g_out, g_xsum, g_wsum, n, C);
   return check_launch("nfs_p2g_wavg_finish_bwd");
 }
 

@@ -874,25 +874,26 @@ def p2g_bwd(p, cfg, g_grid, attr=None, pd=None, g_wsum=None, need_p=True, need_a
     return g_p, g_attr, g_pd
 
 
+def p2g_has_instance(cfg):
+    """whether the one-launch adjoint forms exist for this configuration (the library's own predicate)"""
+    rc = _lib.lib().nfs_p2g_has_instance(C.byref(cfg))
+    if rc < 0:
+        raise _lib.NfsError("nfs_p2g_has_instance", rc, _lib.lib().nfs_last_error().decode())
+    return bool(rc)
+
+
 def p2g_wavg_bwd(p, cfg, xsum, wsum, g_out, attr, eps=1e-6, need_p=True, need_attr=True):
-    """adjoint of the weighted-average splat in one launch (finish adjoint folded into the gather); None when the
-    neighbourhood has no compile-time instance (the caller takes p2g_wavg_finish_bwd + p2g_bwd)"""
-    if not ((cfg.nd == 3 and cfg.nsize in (1, 2)) or (cfg.nd == 2 and cfg.nsize in (1, 2, 3, 4))):
+    """adjoint of the weighted-average splat in one launch (finish adjoint folded into the gather); None where the
+    library has no such form for the configuration (nfs_p2g_has_instance: the caller takes p2g_wavg_finish_bwd +
+    p2g_bwd)"""
+    if not p2g_has_instance(cfg):
         return None
     N = p.shape[0]
     Cn = attr.shape[-1]
     g_p = _empty(p.shape, p) if need_p else None
     g_attr = _empty(attr.shape, p) if need_attr else None
-    try:
-        _lib.call("nfs_p2g_wavg_bwd", _ptr(p), _ptr(attr), _ptr(xsum), _ptr(wsum), _ptr(g_out), _ptr(g_p), _ptr(g_attr), N,
-                  Cn, float(eps), C.byref(cfg), _stream())
-    except _lib.NfsError as e:
-        # the library's own predicate (launch_p2g_bwd: cells < 2^31, its reading of NFS_SPLAT_LDS) is the authority: the
-        # ONE refusal it documents -- no compile-time instance, nothing launched -- sends the caller down the two-launch
-        # adjoint; any other NFS_EINVAL (a null pointer, a bad N or mode) is an error, not a slow path
-        if e.code != _lib.NFS_EINVAL or "no compile-time instance" not in str(e):
-            raise
-        return None
+    _lib.call("nfs_p2g_wavg_bwd", _ptr(p), _ptr(attr), _ptr(xsum), _ptr(wsum), _ptr(g_out), _ptr(g_p), _ptr(g_attr), N,
+              Cn, float(eps), C.byref(cfg), _stream())
     return g_p, g_attr
 
 

@@ -11,8 +11,6 @@ from __future__ import annotations
 
 import math
 
-import os
-
 import numpy as np
 import torch
 
@@ -384,10 +382,8 @@ class _P2GWavg(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         p2, a, xs, ws = ctx.saved_tensors
-        fused = None
-        if os.environ.get("NFS_SPLAT_LDS", "1") != "0":
-            fused = ops.p2g_wavg_bwd(p2, ctx.cfg, xs, ws, g.contiguous()[0], a, ctx.eps,
-                                     need_p=ctx.needs_input_grad[0], need_attr=ctx.needs_input_grad[1])
+        fused = ops.p2g_wavg_bwd(p2, ctx.cfg, xs, ws, g.contiguous()[0], a, ctx.eps,
+                                 need_p=ctx.needs_input_grad[0], need_attr=ctx.needs_input_grad[1])
         if fused is not None:
             gp, ga = fused
         else:

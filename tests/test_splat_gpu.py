@@ -18,9 +18,9 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 
-# The (nd, nsize) pairs with a compile-time instance: ONE list, to be kept equal to the two dispatchers of
-# csrc/splat.hip -- nfs_p2g_fwd (NFS_SPL_LAUNCH) and launch_p2g_bwd (NFS_SPB_LAUNCH).  An instance added there
-# without an entry here has no test.
+# The (nd, nsize) pairs with a compile-time instance, written down here by hand and NOT read from the library:
+# csrc/splat.hip keeps its own one list (with_instance), and test_instance_list_is_the_librarys holds the two equal,
+# so an instance added there without an entry here fails that test instead of going untested.
 INSTANCES = [(3, 1), (3, 2), (2, 1), (2, 2), (2, 3), (2, 4)]
 # what falls through to the generic loops: any other nsize, 0 included
 GENERIC = [(3, 3), (2, 5), (3, 0), (2, 0)]
@@ -208,6 +208,17 @@ def test_instance_matrix(ops, nd, nsize, clip):
             run_case(ops, rep, S, p, a, pd, g, gw, "mode %d C %d pd %d %s" % (mode, C, use_pd, tag),
                      combos=(tag == "brick"), lds_instance=(nd, nsize) in INSTANCES)
     rep.done()
+
+
+def test_instance_list_is_the_librarys(ops):
+    """nfs_p2g_has_instance, the predicate the dispatchers of splat.hip use, against the hand-written list.  The
+    query also answers 0 for every pair when the process runs under NFS_SPLAT_LDS=0: a failure of this test in such a
+    process says nothing about the list."""
+    for nd in (2, 3):
+        for nsize in range(9):
+            assert ops.p2g_has_instance(splat(nd, nsize, False, 2).ops_cfg(ops)) == ((nd, nsize) in INSTANCES), (nd, nsize)
+    for nd, nsize in GENERIC:
+        assert not ops.p2g_has_instance(splat(nd, nsize, False, 2).ops_cfg(ops))
 
 
 # ---- particle sets ---------------------------------------------------------------------------------------------------------
