@@ -241,6 +241,30 @@ int nfs_advect_maccormack_bwd(const float* d, const float* vel, const float* d_f
 int nfs_curl_fwd(const float* s, float* out, int D, int H, int W, int nd, nfs_stream_t stream);
 int nfs_curl_bwd(const float* g_out, float* g_s, int D, int H, int W, int nd, nfs_stream_t stream);
 
+/* ---- stylising through a stream function (grid variable 's'; curl above, advect A11) ----------------------------------
+ * s [D,H,W,3] is a stream function; its stream velocity is the channel-reversed curl, so that component k moves along
+ * array axis k as advect wants (the curl's output is in (x,y,z) = (W,H,D) order) -- with D_A the forward difference along
+ * array axis A, last slice replicated:
+ *   vel0 = D_W s1 - D_H s0,  vel1 = D_D s0 - D_W s2,  vel2 = D_H s2 - D_D s1   (D_D vel0 + D_H vel1 + D_W vel2 = 0).
+ * No scale factor: one forward difference of s is a normalised advect velocity.
+ * nfs_advect_stream_fwd: out [D,H,W] = advect(d [D,H,W], vel(s)), the velocity formed in registers and never stored
+ *   (20 B per voxel against 44 for nfs_curl_fwd + nfs_advect_fwd); live (nullable, nfs_live_mask_words 64-bit words): the
+ *   mask nfs_advect_fwd_live writes.  Bit-identical to nfs_advect_fwd / nfs_advect_fwd_live on the stored velocity.
+ * nfs_advect_stream_bwd: g_vel [D,H,W,3] = the velocity gradient of that advect, in advect's channel order, the
+ *   velocity recomputed from s; bit-identical to nfs_advect_bwd (g_vel only) on the stored velocity.
+ *   Both run on the four-voxel kernel only: D,H,W >= 2, D*H*W % 4 == 0 and < 2^30, else NFS_EINVAL (compose
+ *   nfs_curl_fwd and nfs_advect_fwd / nfs_advect_bwd there); out must not alias d or s, g_vel none of its inputs.
+ * nfs_stream_bwd_adam: g_s = curl^T(reverse(g_vel)) (nfs_curl_bwd's gather and summation order: no atomics,
+ *   deterministic) consumed on the spot by the TF ApplyAdam update (nfs_adam_tf_step's expression) of s, m, v
+ *   [D,H,W,3] in place; g_s is never stored (84 B per voxel against 108 for nfs_curl_bwd + nfs_adam_tf_step).
+ *   Any D,H,W >= 1; g_vel must not alias s, m or v. */
+int nfs_advect_stream_fwd(const float* d, const float* s, float* out, unsigned long long* live,
+                          int D, int H, int W, nfs_stream_t stream);
+int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, float* g_vel,
+                          int D, int H, int W, nfs_stream_t stream);
+int nfs_stream_bwd_adam(const float* g_vel, float* s, float* m, float* v, int D, int H, int W,
+                        float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream);
+
 /* ---- Laplacian-pyramid gradient normalisation (util.py:57-110) -------------------------------------
  * nfs_lap_down: out [ceil(D/2),ceil(H/2),ceil(W/2),C] = conv(x [D,H,W,C], k, stride 2, 'SAME') (tf.nn.conv3d / conv2d of
  *   lap_split, 60-66); k = k5x5x5 [5][5][5] (nd = 3) or k5x5 [5][5] (nd = 2, D = 1), the same for every channel.

@@ -87,6 +87,9 @@ SIGNATURES = {
     "nfs_advect_maccormack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "nfs_curl_fwd": [_P, _P, _I, _I, _I, _I, _P],
     "nfs_curl_bwd": [_P, _P, _I, _I, _I, _I, _P],
+    "nfs_advect_stream_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_advect_stream_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_stream_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
     "nfs_lap_down": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "nfs_lap_up": [_P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P],
     "nfs_lap_up_rms_parts": [_I, _I, _I, _I, _I],

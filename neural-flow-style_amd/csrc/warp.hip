@@ -254,13 +254,36 @@ __device__ __forceinline__ void lane_start(int first, int n, int H, int W, int& 
 }
 
 
+// Stream velocity of voxel (z, h, w): the channel-reversed curl of a stream function s [D,H,W,3] (curl_fwd_kernel,
+// warp2d.hip: forward differences, last slice replicated), vel_k along array axis k:
+//   vel0 = D_W s1 - D_H s0,  vel1 = D_D s0 - D_W s2,  vel2 = D_H s2 - D_D s1
+// -- differences and one subtraction each, nothing to contract: the bits of nfs_curl_fwd's output, channels reversed.
+// The voxel's own 12-byte vector is one end of all three differences (the lower end, or the upper one on the last slice of
+// an axis): one further vector per axis, the two components that axis differentiates (x: s1 s2 and z: s0 s1 as one 8-byte
+// load).  The x neighbour is the next lane's own vector, the y and z neighbours are re-reads of the next row / plane.
+__device__ __forceinline__ F3u stream_velocity(const float* __restrict__ s, int z, int h, int w, int D, int H, int W) {
+  const size_t own = ((size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w) * 3;
+  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
+  const size_t sx = 3, sy = (size_t)W * 3, sz = (size_t)H * W * 3;
+  const F3u p = *reinterpret_cast<const F3u*>(s + own);
+  const F2u qx = *reinterpret_cast<const F2u*>(s + (fx ? own + sx : own - sx) + 1);   // s1, s2
+  const F3u qy = *reinterpret_cast<const F3u*>(s + (fy ? own + sy : own - sy));       // s0, (s1), s2
+  const F2u qz = *reinterpret_cast<const F2u*>(s + (fz ? own + sz : own - sz));       // s0, s1
+  const float dw1 = fx ? qx.x - p.y : p.y - qx.x, dw2 = fx ? qx.y - p.z : p.z - qx.y;
+  const float dh0 = fy ? qy.x - p.x : p.x - qy.x, dh2 = fy ? qy.z - p.z : p.z - qy.z;
+  const float dd0 = fz ? qz.x - p.x : p.x - qz.x, dd1 = fz ? qz.y - p.y : p.y - qz.y;
+  return F3u{dw1 - dh0, dd0 - dw2, dh2 - dd1};
+}
+
 // MODE 0: forward; 1: velocity gradient -> out; 2: velocity gradient consumed on the spot by the TF-Adam update of
 // the velocity itself (vel, m, v updated in place: every thread reads and writes only its own 4 voxels of them;
 // the 96 MB gradient never goes to HBM)
 // Slab form (zoff, Dfull): vel / g_out / out / the moments hold only the D planes [zoff, zoff + D) of a volume of Dfull
 // planes, d is the WHOLE density (the back-traced points leave the slab); zoff = 0, Dfull = D is the whole volume.
 // EVER (MODE 2 + LIVE, volumes below 2^31 / 12 voxels): ad.ever is set and the streamed accesses are predicated per lane
-template <int MODE, bool LIVE = false, bool EVER = false>   // LIVE: ad.live is set (a compile-time switch: the mask code out of the plain kernels)
+// STREAM (MODE 0 / 1, whole volumes): vel is a stream function and the velocity is stream_velocity() of it, formed in
+// registers and never stored; everything after the fetch is the same code
+template <int MODE, bool LIVE = false, bool EVER = false, bool STREAM = false>   // LIVE: ad.live is set (a compile-time switch: the mask code out of the plain kernels)
 __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ d, const float* vel,
                                                       const float* __restrict__ g_out, float* out,
                                                       int D, int H, int W, AdamFused ad, int zoff, int Dfull) {
@@ -321,11 +344,20 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
   F3u vv[4], mm[4], uu[4];
   float gg[4];
   bool ok[4];
+  [[maybe_unused]] int ws, hs, zs;   // STREAM: the voxel positions, walked here as well (walk64 keeps them inside the volume)
+  if constexpr (STREAM) lane_start(first, n, H, W, ws, hs, zs);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int idx = first + 64 * j;
     ok[j] = idx < n;
     const int ic = ok[j] ? idx : n - 1;
+    if constexpr (STREAM) {
+      static_assert(!STREAM || MODE != 2, "the stream-function update is nfs_stream_bwd_adam");
+      vv[j] = stream_velocity(vel, zs, hs, ws, D, H, W);
+      if (BWD) gg[j] = g_out[ic];
+      walk64(ws, hs, zs, W, H, D - 1);
+      continue;
+    }
     if constexpr (EVER) {
       act[j] = ok[j] && ((ew[j] >> lane) & 1ull);
       const uint32_t o12 = act[j] ? (uint32_t)idx * 12u : 0x80000000u, o4 = act[j] ? (uint32_t)idx * 4u : 0x80000000u;
@@ -1340,8 +1372,9 @@ static bool advect1_takes(int D, int H, int W, int nz) {
 // mode: advect1_kernel's MODE; LIVE follows ad.live, EVER ad.ever (and NFS_EVER_LANES); the planes [z0, z0 + nz) of the
 // volume (vel / g_out / out / the moments hold those only; z0 = 0, nz = D: the whole-volume forms).  The callers have
 // checked their pointers for null.
+// psi: vel is a stream function (STREAM; mode 0 / 1 on whole volumes).
 static int advect1_launch(const char* who, int mode, const float* d, const float* vel, const float* g_out, float* out,
-                          int D, int H, int W, int z0, int nz, const AdamFused& ad, nfs_stream_t stream) {
+                          int D, int H, int W, int z0, int nz, const AdamFused& ad, nfs_stream_t stream, bool psi = false) {
   NFS_REQUIRE(!ad.adv_next || (ad.adv_next != d && ad.adv_next != g_out), "%s: adv_next must not alias d or g_out", who);
   if (int e = check_dims(1, D, H, W, 1)) return e;
   NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "%s: slab outside the volume", who);
@@ -1349,7 +1382,11 @@ static int advect1_launch(const char* who, int mode, const float* d, const float
               "%s: needs D, H, W >= 2, D*H*W < 2^30 and a multiple of 4 voxels (nz*H*W for a slab)", who);
   const int64_t n = (int64_t)nz * H * W;
   auto kernel = ad.live ? advect1_kernel<0, true> : advect1_kernel<0>;
-  if (mode == 1) {
+  if (psi) {
+    NFS_REQUIRE(mode != 2 && z0 == 0 && nz == D, "%s: a stream function takes the forward and the gradient of a whole volume", who);
+    kernel = mode == 1 ? advect1_kernel<1, false, false, true>
+                       : ad.live ? advect1_kernel<0, true, false, true> : advect1_kernel<0, false, false, true>;
+  } else if (mode == 1) {
     kernel = advect1_kernel<1>;
   } else if (mode == 2 && !ad.live) {
     kernel = advect1_kernel<2>;
@@ -1511,6 +1548,25 @@ int nfs_advect_bwd(const float* d, const float* vel, const float* g_out, float* 
   hipLaunchKernelGGL(warp_bwd_kernel<COORD_ADVECT>, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), a,
                      g_out, g_d_acc, g_vel);
   return check_launch("nfs_advect_bwd");
+}
+
+// advect along the stream velocity of s (stream_velocity(): the channel-reversed curl), the velocity never stored; live
+// (nullable): the mask nfs_advect_fwd_live writes.  Bit-identical to nfs_advect_fwd / _live on the stored velocity.
+int nfs_advect_stream_fwd(const float* d, const float* s, float* out, unsigned long long* live, int D, int H, int W,
+                          nfs_stream_t stream) {
+  NFS_REQUIRE(d && s && out, "nfs_advect_stream_fwd: null pointer");
+  NFS_REQUIRE(out != d && out != s, "nfs_advect_stream_fwd: out must not alias d or s");
+  AdamFused ad{};
+  ad.live = live;
+  return advect1_launch("nfs_advect_stream_fwd", 0, d, s, nullptr, out, D, H, W, 0, D, ad, stream, true);
+}
+
+// ... and its velocity gradient g_vel [D,H,W,3] (advect's channel order), the velocity recomputed from s
+int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, float* g_vel, int D, int H, int W,
+                          nfs_stream_t stream) {
+  NFS_REQUIRE(d && s && g_out && g_vel, "nfs_advect_stream_bwd: null pointer");
+  NFS_REQUIRE(g_vel != d && g_vel != s && g_vel != g_out, "nfs_advect_stream_bwd: g_vel must not alias d, s or g_out");
+  return advect1_launch("nfs_advect_stream_bwd", 1, d, s, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, true);
 }
 
 // ---- adjoint of nfs_advect_maccormack_keep (transform.py:570-582, 590-607; the kernels above) ----------------------------

@@ -160,8 +160,6 @@ __global__ void __launch_bounds__(256) maccormack_kernel(const float* __restrict
 // ---- curl of a stream function (forward differences, last slice replicated; transform.py:517-555) ------------------
 // 2-D: s [H,W] -> [H,W,2]: u = ds/dy (axis 0), v = -ds/dx (axis 1).  3-D: s [D,H,W,3] -> [D,H,W,3]:
 //   u = dw/dy - dv/dz, v = du/dz - dw/dx, w = dv/dx - du/dy   with x = axis W, y = axis H, z = axis D.
-__device__ __forceinline__ int fd_lo(int i, int n) { return i < n - 1 ? i : (n >= 2 ? n - 2 : 0); }
-
 __global__ void __launch_bounds__(256) curl_fwd_kernel(const float* __restrict__ s, float* __restrict__ out, int D, int H,
                                                        int W, int nd) {
   const int64_t n = (int64_t)D * H * W;
@@ -225,6 +223,39 @@ __global__ void __launch_bounds__(256) curl_bwd_kernel(const float* __restrict__
   gs[vox * 3] = fd_adj(g, bz, (int64_t)H * W, z, D, 1, 3) - fd_adj(g, by, W, y, H, 2, 3);
   gs[vox * 3 + 1] = fd_adj(g, bx, 1, x, W, 2, 3) - fd_adj(g, bz, (int64_t)H * W, z, D, 0, 3);
   gs[vox * 3 + 2] = fd_adj(g, by, W, y, H, 0, 3) - fd_adj(g, bx, 1, x, W, 1, 3);
+}
+
+// ---- stream-function update: g_s = curl^T(reverse(g_vel)) consumed on the spot by TF ApplyAdam on s -------------------
+// g_vel [D,H,W,3] is a velocity gradient in advect's channel order (component k along array axis k): channel c of the
+// curl's output is channel 2 - c of g_vel, folded into fd_adj's channel argument.  The gather and its summation order are
+// curl_bwd_kernel's, the update is adam_kernel's expression (field.hip).  A thread reads g_vel at its neighbours and its
+// own s, m, v only: in place.  84 B per voxel (12 g_vel + 3 x 12 read + 3 x 12 written); 12-byte vectors, lanes contiguous.
+struct __attribute__((packed, aligned(4))) F3s { float c[3]; };
+
+__global__ void __launch_bounds__(256) stream_bwd_adam_kernel(const float* __restrict__ g, float* __restrict__ s,
+                                                              float* __restrict__ m, float* __restrict__ v, int D, int H,
+                                                              int W, float lr_t, float b1, float b2, float eps) {
+  const int64_t n = (int64_t)D * H * W;
+  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vox >= n) return;
+  F3s xs = reinterpret_cast<const F3s*>(s)[vox], ms = reinterpret_cast<const F3s*>(m)[vox],
+      us = reinterpret_cast<const F3s*>(v)[vox];
+  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
+  const int64_t bx = (int64_t)z * H * W + (int64_t)y * W, by = (int64_t)z * H * W + x, bz = (int64_t)y * W + x;
+  const int64_t sz = (int64_t)H * W;
+  // curl_bwd_kernel's three lines with channel c -> 2 - c
+  const float gs[3] = {fd_adj(g, bz, sz, z, D, 1, 3) - fd_adj(g, by, W, y, H, 0, 3),
+                       fd_adj(g, bx, 1, x, W, 0, 3) - fd_adj(g, bz, sz, z, D, 2, 3),
+                       fd_adj(g, by, W, y, H, 2, 3) - fd_adj(g, bx, 1, x, W, 1, 3)};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ms.c[c] = b1 * ms.c[c] + (1.f - b1) * gs[c];
+    us.c[c] = b2 * us.c[c] + (1.f - b2) * gs[c] * gs[c];
+    xs.c[c] -= lr_t * ms.c[c] / (sqrtf(us.c[c]) + eps);
+  }
+  reinterpret_cast<F3s*>(s)[vox] = xs;
+  reinterpret_cast<F3s*>(m)[vox] = ms;
+  reinterpret_cast<F3s*>(v)[vox] = us;
 }
 
 static int check_dims2(int B, int X, int Y, int C) {
@@ -334,6 +365,17 @@ int nfs_curl_bwd(const float* g_out, float* g_s, int D, int H, int W, int nd, nf
   hipLaunchKernelGGL(curl_bwd_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), g_out,
                      g_s, D, H, W, nd);
   return check_launch("nfs_curl_bwd");
+}
+
+int nfs_stream_bwd_adam(const float* g_vel, float* s, float* m, float* v, int D, int H, int W, float lr_t, float beta1,
+                        float beta2, float eps, nfs_stream_t stream) {
+  NFS_REQUIRE(g_vel && s && m && v, "nfs_stream_bwd_adam: null pointer");
+  NFS_REQUIRE(g_vel != s && g_vel != m && g_vel != v, "nfs_stream_bwd_adam: g_vel must not alias s, m or v (it is a gather)");
+  NFS_REQUIRE(D > 0 && H > 0 && W > 0, "nfs_stream_bwd_adam: non-positive dimension");
+  NFS_REQUIRE((int64_t)D * H * W * 3 < (int64_t)1 << 40, "nfs_stream_bwd_adam: tensor too large");
+  hipLaunchKernelGGL(stream_bwd_adam_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream),
+                     g_vel, s, m, v, D, H, W, lr_t, beta1, beta2, eps);
+  return check_launch("nfs_stream_bwd_adam");
 }
 
 }  // extern "C"

@@ -300,6 +300,60 @@ def curl_bwd(g_out):
     return g_s
 
 
+# ---- stylising through a stream function (include/nfs_hip.h: grid variable 's') ---------------------------------------
+
+def stream_velocity(s):
+    """stream velocity of a stream function s [D,H,W,3]: its curl with the channels reversed, so that component k moves
+    along array axis k as ``advect_fwd`` wants -- divergence-free in forward differences"""
+    return curl_fwd(s).flip(-1).contiguous()
+
+
+def stream_velocity_bwd(g_vel):
+    """adjoint of ``stream_velocity``: g_s = curl^T(reverse(g_vel))"""
+    return curl_bwd(g_vel.flip(-1).contiguous())
+
+
+def advect_stream_takes(D, H, W):
+    """the shapes ``nfs_advect_stream_fwd`` / ``_bwd`` take (the four-voxel advect kernel's, include/nfs_hip.h)"""
+    return min(D, H, W) >= 2 and (D * H * W) % 4 == 0 and D * H * W < (1 << 30)
+
+
+def advect_stream_fwd(d, s, out=None, live=None):
+    """advect_fwd(d, stream_velocity(s)) for a scalar field d [D,H,W,1], the velocity never stored (one kernel; the same
+    bits).  ``live`` as in ``advect_fwd``.  Shapes the fused kernel does not take run the composition."""
+    D, H, W, Cn = d.shape
+    assert Cn == 1 and tuple(s.shape) == (D, H, W, 3) and s.is_contiguous()
+    if not advect_stream_takes(D, H, W):
+        return advect_fwd(d, stream_velocity(s), out=out, live=live)
+    if out is None:
+        out = _empty(d.shape, d)
+    _lib.call("nfs_advect_stream_fwd", _ptr(d), _ptr(s), _ptr(out), _ptr(live), D, H, W, _stream())
+    _written(live)
+    return out
+
+
+def advect_stream_bwd(d, s, g_out, g_vel=None):
+    """velocity gradient [D,H,W,3] (advect's channel order) of ``advect_stream_fwd``, the velocity recomputed from s:
+    the bits of advect_bwd(d, stream_velocity(s), g_out, need_d=False)"""
+    D, H, W, Cn = d.shape
+    assert Cn == 1 and tuple(s.shape) == (D, H, W, 3) and s.is_contiguous()
+    if not advect_stream_takes(D, H, W):
+        return advect_bwd(d, stream_velocity(s), g_out, need_d=False, g_vel=g_vel)[1]
+    if g_vel is None:
+        g_vel = _empty(s.shape, d)
+    _lib.call("nfs_advect_stream_bwd", _ptr(d), _ptr(s), _ptr(g_out), _ptr(g_vel), D, H, W, _stream())
+    return g_vel
+
+
+def stream_bwd_adam(g_vel, s, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """g_s = stream_velocity_bwd(g_vel) consumed on the spot by the TF-Adam update of s (s, m, v [D,H,W,3] in place)"""
+    D, H, W, _ = s.shape
+    assert tuple(g_vel.shape) == tuple(s.shape) == tuple(m.shape) == tuple(v.shape) and s.shape[-1] == 3
+    _lib.call("nfs_stream_bwd_adam", _ptr(g_vel), _ptr(s), _ptr(m), _ptr(v), D, H, W, float(lr_t), float(beta1),
+              float(beta2), float(eps), _stream())
+    _written(s, m, v)
+
+
 def lap_down(x, k):
     """x [D,H,W,C] (3-D, k [5,5,5]) or [H,W,C] (2-D, k [5,5]) -> stride-2 'SAME' smoothing (util.py:60-66)"""
     nd = 3 if x.dim() == 4 else 2
