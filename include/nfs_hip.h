@@ -394,8 +394,11 @@ int nfs_rotate_live_workspace_ints(int D, int H, int W);
 /* d /= reduce_max(d) (styler_3p.py:158): G groups of n contiguous floats, one max per
  * group (v_batch views form one group; v_batch=1 => per view).  gmax [G] is written by
  * fwd and read by bwd; the max gradient is split equally among ties like TF's.  bwd `workspace`
- * (device, >= 64*G floats, nullable): groups of >= 16384 elements are reduced by 32 blocks each with the
- * partial sums combined in a fixed order; without it one block per group does everything. */
+ * (device, >= nfs_maxnorm_workspace_floats(G) floats, nullable): groups of >= 16384 elements are reduced by 32 blocks
+ * each with the partial sums combined in a fixed order; without it one block per group does everything.
+ * nfs_maxnorm_workspace_floats: two floats (sum, tie count) per block and group, 64*G today; launches nothing.  Callers
+ * ask it instead of carrying the block count. */
+int nfs_maxnorm_workspace_floats(int G);
 int nfs_maxnorm_fwd(const float* img, float* out, float* gmax, int G, int n,
                     nfs_stream_t stream);
 int nfs_maxnorm_bwd(const float* img, const float* gmax, const float* g_out, float* g_img,
@@ -404,7 +407,7 @@ int nfs_maxnorm_bwd(const float* img, const float* gmax, const float* g_out, flo
  * net's own size (resize_scale 1): x [.,3] = (img / max) * 255 - mean[c]; adjoint g_img = adjoint_maxnorm(255 * (g_x[.,0] +
  * g_x[.,1] + g_x[.,2])).  To float32 rounding the arithmetic of nfs_maxnorm_fwd + nfs_loss_net_input_fwd and of
  * nfs_loss_net_input_bwd + nfs_maxnorm_bwd, without the [V,H,W] intermediates and two launches less per direction.
- * img [G*n], x / g_x [G*n,3], gmax [G] (written by fwd), workspace >= 64*G floats. */
+ * img [G*n], x / g_x [G*n,3], gmax [G] (written by fwd), workspace >= nfs_maxnorm_workspace_floats(G) floats. */
 int nfs_maxnorm_input_fwd(const float* img, float* x, float* gmax, int G, int n, nfs_stream_t stream);
 int nfs_maxnorm_input_bwd(const float* img, const float* gmax, const float* g_x, float* g_img, int G, int n,
                           float* workspace, nfs_stream_t stream);

@@ -113,6 +113,7 @@ SIGNATURES = {
     "nfs_rotate_bwd_coef_live": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P],
     "nfs_rotate_live_workspace_ints": [_I, _I, _I],
     "nfs_rotate_render_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
+    "nfs_maxnorm_workspace_floats": [_I],
     "nfs_maxnorm_fwd": [_P, _P, _P, _I, _I, _P],
     "nfs_maxnorm_bwd": [_P, _P, _P, _P, _I, _I, _P, _P],
     "nfs_maxnorm_input_fwd": [_P, _P, _P, _I, _I, _P],
@@ -186,7 +187,7 @@ _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 154          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 155          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

@@ -10,14 +10,65 @@
 
 namespace nfs {
 
+// ---- small shared pieces -------------------------------------------------------------
+// exp(-tau a) = exp2(exp2_rate(tau) a): the marches run on the hardware exp2
+__device__ __forceinline__ float exp2_rate(float tau) { return -tau * 1.44269504088896341f; }
+
+// ray gid of a [V][H][W] image -> view v, pixel px of the view and (with W) row h and column w.  Statements that declare
+// their results, not functions: behind a call the compiler orders the index arithmetic of every kernel differently.
+#define NFS_RAY_INDEX(gid, HW, v, px)  \
+  const int v = (int)((gid) / (HW)); \
+  const int px = (int)((gid) - (int64_t)v * (HW))
+#define NFS_RAY_INDEX_HW(gid, HW, W, v, px, h, w) \
+  NFS_RAY_INDEX(gid, HW, v, px);                  \
+  const int h = px / (W), w = px - h * (W)
+
+#define NFS_LOAD_ROT(rot, v, r) /* float r[9]: the row-major rotation of view v (a statement for the same reason) */ \
+  float r[9];                                                     \
+  _Pragma("unroll") for (int i = 0; i < 9; ++i) r[i] = (rot)[(v) * 9 + i]
+
+// ---- the marches' arithmetic, each written once ------------------------------------------
+// forward, far end first, exp2 form: returns what the kept volume receives -- the sample, or (UOUT)
+// u = t + tau i with i the image sum BEFORE the sample, whose largest magnitude umax follows
+template <bool UOUT>
+__device__ __forceinline__ float march_update(float s, float tau, float ntau, float& acc, float& I, float& umax) {
+  acc += s;
+  const float t = __builtin_amdgcn_exp2f(acc * ntau);
+  float o = s;
+  if constexpr (UOUT) {
+    o = fmaf(tau, I, t);
+    umax = fmaxf(umax, fabsf(o));
+  }
+  I = fmaf(s, t, I);
+  return o;
+}
+
+// depth segments of a ray combine far end first: I = sum_s E_s I_s, E_s = exp(-tau P_s), P_s = the ray sums of the
+// segments farther than s.  One segment's turn; returns E_s (Itot before the call is F_s = sum_{s' < s} E_s' I_s').
+__device__ __forceinline__ float seg_combine(float S, float Is, float ntau, float& P, float& Itot) {
+  const float E = __builtin_amdgcn_exp2f(P * ntau);
+  Itot = fmaf(E, Is, Itot);
+  P += S;
+  return E;
+}
+
+// adjoint, near end first: T[z] = exp(-tau (total - prefix)), prefix = the ray sum BEFORE the sample, P = sum_{z' <= z} s T;
+// returns the new P and o = g dI/ds[z].  By value, and prefix += s left to the caller after its store: with the sums
+// behind references the compiler orders the loop's registers differently.
+struct AdjStep { float P, o; };
+__device__ __forceinline__ AdjStep adj_step(float s, float g, float total, float prefix, float P, float tau, float ntau) {
+  const float T = __builtin_amdgcn_exp2f((total - prefix) * ntau);
+  P = fmaf(s, T, P);
+  return AdjStep{P, g * (T - tau * P)};
+}
+
 // ---- un-fused ----------------------------------------------------------------------
 __global__ void __launch_bounds__(256) render_fwd_kernel(const float* __restrict__ d, float* __restrict__ img,
                                                          float* __restrict__ raysum, int V, int D, int HW, float tau,
                                                          int liquid) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)V * HW) return;
-  const int v = (int)(gid / HW);
-  const int px = (int)(gid - (int64_t)v * HW);
+  NFS_RAY_INDEX(gid, HW, v, px);
   const float* col = d + (int64_t)v * D * HW + px;
   if (liquid >= 2) {
     // ray modes of north_star beside the reference's two: 2 = reduce_max along the ray (the line the reference keeps
@@ -57,12 +108,11 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(const float* d,
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float amax = 0.f;
   if (gid < (int64_t)V * HW) {
-    const int v = (int)(gid / HW);
-    const int px = (int)(gid - (int64_t)v * HW);
+    NFS_RAY_INDEX(gid, HW, v, px);
     const int64_t base = (int64_t)v * D * HW + px;
     const float total = raysum[gid];
     const float g = g_img[gid];
-    const float ntau = -tau * 1.44269504088896341f;                 // exp(-tau a) = exp2(ntau a)
+    const float ntau = exp2_rate(tau);
     if (liquid == 2) {
       // reduce_max: the gradient goes to the cells that hold the maximum, split equally among ties (TF's rule); the
       // column is read once to count them and once more as it is overwritten (g_d may be d itself)
@@ -89,11 +139,10 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(const float* d,
       constexpr int RB = 8;
       float prefix = 0.f, P = 0.f;
       auto step = [&](float s, int z) __attribute__((always_inline)) {
-        const float T = __builtin_amdgcn_exp2f((total - prefix) * ntau);
-        P = fmaf(s, T, P);
-        const float o = g * (T - tau * P);
-        g_d[base + (int64_t)z * HW] = o;
-        amax = fmaxf(amax, fabsf(o));
+        const AdjStep a = adj_step(s, g, total, prefix, P, tau, ntau);
+        P = a.P;
+        g_d[base + (int64_t)z * HW] = a.o;
+        amax = fmaxf(amax, fabsf(a.o));
         prefix += s;
       };
       const int nfull = D / RB;
@@ -119,6 +168,60 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(const float* d,
   // optional by-product: max |g_d| (as float bits) for the fixed-point scale of the rotate adjoint that follows
   if (gmax_bits) {
     amax = block_max(amax, red);
+    if (threadIdx.x == 0 && amax > 0.f) atomicMax(gmax_bits, __float_as_uint(fminf(amax, 3.0e38f)));
+  }
+}
+
+// Segmented render adjoint for small batches (one or two views per GPU): with V*H*W = 40 k rays a one-thread-per-ray
+// march is latency-bound (80 us for a 32 MB volume).  Four waves share 64 rays, one depth segment each; a first walk
+// gives every segment its ray sum S and R = sum s*exp(-tau (total - local prefix)), the block combines them into the
+// segment's starting prefix / weighted sum (the transmittance factorises: exp(-tau (total - p0 - local)) =
+// exp(tau p0) * exp(-tau (total - local))), a second walk writes the gradient.  The volume is read twice, so this
+// form is only used while it stays cache-resident (<= 64 MB).
+template <int NSEG>
+__global__ void __launch_bounds__(64 * NSEG) render_bwd_seg_kernel(const float* d, const float* __restrict__ raysum,
+                                                                   const float* __restrict__ g_img, float* g_d, int V,
+                                                                   int D, int HW, float tau,
+                                                                   unsigned* __restrict__ gmax_bits) {
+  __shared__ float seg_S[NSEG][64], seg_R[NSEG][64], red[16];
+  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
+  const int64_t total_rays = (int64_t)V * HW;
+  const int64_t gid_raw = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = gid_raw < total_rays;
+  const int64_t gid = live ? gid_raw : total_rays - 1;
+  NFS_RAY_INDEX(gid, HW, v, px);
+  const int64_t base = (int64_t)v * D * HW + px;
+  const float total = raysum[gid], g = g_img[gid];
+  const float ntau = exp2_rate(tau);
+  const int L = (D + NSEG - 1) / NSEG;
+  const int zlo = min(seg * L, D), zhi = min(zlo + L, D);         // segment 0 starts at z = 0 (prefix order)
+  float S = 0.f, R = 0.f;
+#pragma unroll 4
+  for (int z = zlo; z < zhi; ++z) {
+    const float sv = d[base + (int64_t)z * HW];
+    R = fmaf(sv, __builtin_amdgcn_exp2f((total - S) * ntau), R);
+    S += sv;
+  }
+  seg_S[seg][lane] = S;
+  seg_R[seg][lane] = R;
+  __syncthreads();
+  float p0 = 0.f, P = 0.f;                                        // prefix and weighted sum before this segment
+  for (int j = 0; j < seg; ++j) {
+    P = fmaf(__builtin_amdgcn_exp2f(-p0 * ntau), seg_R[j][lane], P);
+    p0 += seg_S[j][lane];
+  }
+  float prefix = p0, amax = 0.f;
+#pragma unroll 4
+  for (int z = zlo; z < zhi; ++z) {
+    const float sv = d[base + (int64_t)z * HW];
+    const AdjStep a = adj_step(sv, g, total, prefix, P, tau, ntau);
+    P = a.P;
+    if (live) g_d[base + (int64_t)z * HW] = a.o;
+    amax = fmaxf(amax, fabsf(a.o));
+    prefix += sv;
+  }
+  if (gmax_bits) {
+    amax = block_max(live ? amax : 0.f, red);
     if (threadIdx.x == 0 && amax > 0.f) atomicMax(gmax_bits, __float_as_uint(fminf(amax, 3.0e38f)));
   }
 }
@@ -281,11 +384,8 @@ __global__ void __launch_bounds__(256, 4) rotate_render_fwd_seg_kernel(const flo
   if (lxb == 0) {                                                 // 64 consecutive pixels (may wrap to the next row)
     const int64_t gid_raw = (int64_t)logical * 64 + lane;
     live = gid_raw < total;
-    const int64_t g = live ? gid_raw : total - 1;
-    v = (int)(g / HW);
-    const int p = (int)(g - (int64_t)v * HW);
-    h = p / W;
-    w = p - h * W;
+    NFS_RAY_INDEX_HW(live ? gid_raw : total - 1, HW, W, v0, p, h0, w0);
+    v = v0, h = h0, w = w0;
   } else {
     // a wave is a 2^lxb x 2^(6-lxb) pixel tile: under a rotation the 64 x 1 strip spreads over ~64 sin(theta)
     // source planes, one cache line each; a tile spreads over 2^lxb sin(theta) planes and its rows share lines
@@ -313,18 +413,16 @@ __global__ void __launch_bounds__(256, 4) rotate_render_fwd_seg_kernel(const flo
   }
   const int px = h * W + w;
   const int64_t gid = (int64_t)v * HW + px;
-  float r[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r[i] = rot[v * 9 + i];
+  NFS_LOAD_ROT(rot, v, r);
   const RayAffine q = ray_affine(r, D, H, W, h, w);
   const VolDims n{(float)(D - 1), (float)(H - 1), (float)(W - 1), (float)(D - 2), (float)(H - 2), (float)(W - 2),
                   (unsigned)W, (unsigned)HW};
-  const float ntau = -tau * 1.44269504088896341f;                 // exp(-tau a) = exp2(ntau a)
+  const float ntau = exp2_rate(tau);
   const int L = (D + RR_SEG - 1) / RR_SEG;
   const int zhi = D - 1 - seg * L, zlo = max(zhi - L + 1, 0);     // segment 0 is the far end
   float* drow = d_rot ? d_rot + (int64_t)v * D * HW + px : nullptr;
   float acc = 0.f, I = 0.f;
-  [[maybe_unused]] float umax = 0.f;
+  float umax = 0.f;
   int z = zhi;
   // REUSE path: buffer addressing (32-bit byte offsets; the launcher checks the sizes) so that the +W / +HW
   // neighbours and the output plane cost scalar offsets instead of 64-bit vector adds
@@ -392,17 +490,9 @@ __global__ void __launch_bounds__(256, 4) rotate_render_fwd_seg_kernel(const flo
         }
       };
       if constexpr (!UOUT) keep(sv);
-      [[maybe_unused]] float uu[NB];
+      float uu[NB];
 #pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        acc += sv[u];
-        const float t = __builtin_amdgcn_exp2f(acc * ntau);
-        if constexpr (UOUT) {
-          uu[u] = fmaf(tau, I, t);
-          umax = fmaxf(umax, fabsf(uu[u]));
-        }
-        I = fmaf(sv[u], t, I);
-      }
+      for (int u = 0; u < NB; ++u) uu[u] = march_update<UOUT>(sv[u], tau, ntau, acc, I, umax);
       if constexpr (UOUT) keep(uu);
       continue;
     } else {
@@ -411,29 +501,14 @@ __global__ void __launch_bounds__(256, 4) rotate_render_fwd_seg_kernel(const flo
     }
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-      acc += sv[u];
-      const float t = __builtin_amdgcn_exp2f(acc * ntau);
-      float o = sv[u];
-      if (UOUT) {
-        o = fmaf(tau, I, t);
-        umax = fmaxf(umax, fabsf(o));
-      }
+      const float o = march_update<UOUT>(sv[u], tau, ntau, acc, I, umax);
       // rotated volume kept for the adjoint: streaming store, must not evict the volume from L2
       if (drow && live) __builtin_nontemporal_store(o, drow + (int64_t)(z - u) * HW);
-      I = fmaf(sv[u], t, I);
     }
   }
   for (; z >= zlo; --z) {
-    const float sone = lean_sample(d, n, q, (float)z);
-    acc += sone;
-    const float t = __builtin_amdgcn_exp2f(acc * ntau);
-    float o = sone;
-    if (UOUT) {
-      o = fmaf(tau, I, t);
-      umax = fmaxf(umax, fabsf(o));
-    }
+    const float o = march_update<UOUT>(lean_sample(d, n, q, (float)z), tau, ntau, acc, I, umax);
     if (drow && live) __builtin_nontemporal_store(o, drow + (int64_t)z * HW);
-    I = fmaf(sone, t, I);
   }
   if (UOUT && live) {                                             // [3][V][RR_SEG][HW]
     const int64_t plane = (int64_t)V * RR_SEG * HW, at = ((int64_t)v * RR_SEG + seg) * HW + px;
@@ -447,10 +522,7 @@ __global__ void __launch_bounds__(256, 4) rotate_render_fwd_seg_kernel(const flo
   if (seg != 0 || !live) return;
   float P = 0.f, Itot = 0.f;
 #pragma unroll
-  for (int s2 = 0; s2 < RR_SEG; ++s2) {
-    Itot = fmaf(__builtin_amdgcn_exp2f(P * ntau), seg_I[s2][lane], Itot);
-    P += seg_sum[s2][lane];
-  }
+  for (int s2 = 0; s2 < RR_SEG; ++s2) seg_combine(seg_sum[s2][lane], seg_I[s2][lane], ntau, P, Itot);
   img[gid] = liquid ? 1.f - __builtin_amdgcn_exp2f(P * ntau) : Itot;
   if (raysum) raysum[gid] = P;
 }
@@ -463,13 +535,17 @@ __global__ void __launch_bounds__(256) rotate_render_fwd_kernel(const float* __r
   const int HW = H * W;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)V * HW) return;
-  const int v = (int)(gid / HW);
-  const int px = (int)(gid - (int64_t)v * HW);
-  const int h = px / W, w = px - h * W;
-  float r[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r[i] = rot[v * 9 + i];
+  NFS_RAY_INDEX_HW(gid, HW, W, v, px, h, w);
+  NFS_LOAD_ROT(rot, v, r);
   float acc = 0.f, I = 0.f;
+  // one sample, far end first: kept for the adjoint (the rotated volume), then into the ray's sums.  A statement, like
+  // NFS_RAY_INDEX: behind a call or a lambda the address arithmetic of the three loops is ordered differently.
+#define NFS_TAKE(s, z) /* s: a variable */                        \
+  do {                                                            \
+    if (d_rot) d_rot[((int64_t)v * D + (z)) * HW + px] = s;       \
+    acc += s;                                                     \
+    I += s * expf(-acc * tau);                                    \
+  } while (0)
   if (W >= 2) {
     // 4 samples (16 paired gathers) are issued before the serial transmittance update consumes them: a
     // one-sample loop is bound by the L2 round trip of each step, not by bandwidth
@@ -484,20 +560,14 @@ __global__ void __launch_bounds__(256) rotate_render_fwd_kernel(const float* __r
         sv[u] = tri_sample_pairs(d, H, W, az, ay, ax);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (d_rot) d_rot[((int64_t)v * D + (z - u)) * HW + px] = sv[u];  // rotated volume kept for the adjoint
-        acc += sv[u];
-        I += sv[u] * expf(-acc * tau);
-      }
+      for (int u = 0; u < 4; ++u) NFS_TAKE(sv[u], z - u);
     }
     for (; z >= 0; --z) {
       float cx, cy, cz;
       ray_coords(r, D, H, W, z, h, w, cx, cy, cz);
       const Axis az = axis_setup(cx, D), ay = axis_setup(cy, H), ax = axis_setup(cz, W);
       const float sone = tri_sample_pairs(d, H, W, az, ay, ax);
-      if (d_rot) d_rot[((int64_t)v * D + z) * HW + px] = sone;
-      acc += sone;
-      I += sone * expf(-acc * tau);
+      NFS_TAKE(sone, z);
     }
   } else {
     for (int z = D - 1; z >= 0; --z) {
@@ -506,11 +576,10 @@ __global__ void __launch_bounds__(256) rotate_render_fwd_kernel(const float* __r
       Tri t; Axis ax, ay, az;
       tri_setup(cx, cy, cz, D, H, W, t, ax, ay, az);
       const float sone = tri_sample1(d, t);
-      if (d_rot) d_rot[((int64_t)v * D + z) * HW + px] = sone;
-      acc += sone;
-      I += sone * expf(-acc * tau);
+      NFS_TAKE(sone, z);
     }
   }
+#undef NFS_TAKE
   img[gid] = liquid ? 1.f - expf(-acc * tau) : I;
   if (raysum) raysum[gid] = acc;
 }
@@ -524,12 +593,8 @@ __global__ void __launch_bounds__(256) rotate_render_bwd_kernel(const float* __r
   const int HW = H * W;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (int64_t)V * HW) return;
-  const int v = (int)(gid / HW);
-  const int px = (int)(gid - (int64_t)v * HW);
-  const int h = px / W, w = px - h * W;
-  float r[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r[i] = rot[v * 9 + i];
+  NFS_RAY_INDEX_HW(gid, HW, W, v, px, h, w);
+  NFS_LOAD_ROT(rot, v, r);
   const float total = raysum[gid];
   const float g = g_img[gid];
   if (g == 0.f) return;
@@ -559,13 +624,12 @@ __global__ void __launch_bounds__(256) rotate_render_bwd_kernel(const float* __r
 }
 
 // ---- d /= reduce_max(d) ------------------------------------------------------------
-// one 1024-thread block per group (a group is <= a few 10^5 pixels)
-// ---- multi-block max-normalisation (groups of >= 16 k elements: one 1024-thread block per group took 20-30 us
-// on 8 of 256 CUs) -------------------------------------------------------------------------------------------
-constexpr int MN_NB = 32;          // blocks per group
+// Two block layouts: one 1024-thread block per group, and from 16 k elements per group on MN_NB blocks of 256 (one
+// 1024-thread block per group took 20-30 us on 8 of 256 CUs)
+constexpr int MN_NB = 32;          // blocks per group; nfs_maxnorm_workspace_floats() sizes the adjoint's partial sums by it
 
 // float max through integer atomics: non-negative floats order like signed ints, negative ones inversely like
-// unsigned ints; the slot is initialised to -inf by the host (hipMemsetD32Async)
+// unsigned ints; the slot is initialised to -inf by maxnorm_init_kernel
 __device__ __forceinline__ void atomic_max_float(float* addr, float v) {
   if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
   else atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
@@ -578,91 +642,117 @@ __global__ void maxnorm_init_kernel(float* __restrict__ gmax, int G) {
   if (i < G) gmax[i] = -INFINITY;
 }
 
-__global__ void __launch_bounds__(256) maxnorm_max_kernel(const float* __restrict__ img, float* __restrict__ gmax, int n) {
-  __shared__ float red[16];
-  const float* x = img + (int64_t)blockIdx.y * n;
-  float m = -INFINITY;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = fmaxf(m, x[i]);
-  m = block_max(m, red);
-  if (threadIdx.x == 0) atomic_max_float(gmax + blockIdx.y, m);
-}
+// The five pieces of y = x / max(x) and its adjoint -- the strided maximum, the two stores, the adjoint's sums, the
+// adjoint's apply -- each written once and shared by the one-block-per-group kernels (small groups) and the
+// MN_NB-blocks-per-group kernels.  What really differs is a policy: what is stored per element (Store), how the incoming
+// gradient is fetched (Grad).  Every kernel walks the elements first, first + stride, ... of its group; the walk is a
+// statement macro whose arguments the kernel writes in terms of blockIdx / blockDim / gridDim: handed to a function by
+// value they are read once in front of the loop's guard and every one-block kernel's stream changed.
+#define NFS_STRIDED(i, first, n, stride) for (int i = (first); i < (n); i += (stride))
+#define NFS_STRIDED_MAX(m, x, first, n, stride) NFS_STRIDED(i_, first, n, stride) m = fmaxf(m, (x)[i_])
 
-__global__ void __launch_bounds__(256) maxnorm_div_kernel(const float* __restrict__ img, const float* __restrict__ gmax,
-                                                          float* __restrict__ out, int n) {
-  const float m = gmax[blockIdx.y];
-  const float* x = img + (int64_t)blockIdx.y * n;
-  float* o = out + (int64_t)blockIdx.y * n;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) o[i] = x[i] / m;
-}
-
-// adjoint, phase 1: per-block partial sums of g*x and of the tie count -> part[group][block][2]
-__global__ void __launch_bounds__(256) maxnorm_bwd_part_kernel(const float* __restrict__ img,
-                                                               const float* __restrict__ gmax,
-                                                               const float* __restrict__ g_out,
-                                                               float* __restrict__ part, int n) {
-  __shared__ float red[16];
-  const float* x = img + (int64_t)blockIdx.y * n;
-  const float* gy = g_out + (int64_t)blockIdx.y * n;
-  const float m = gmax[blockIdx.y];
-  float s = 0.f, ties = 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float xi = x[i];
-    s += gy[i] * xi;
-    ties += (xi == m) ? 1.f : 0.f;
-  }
-  s = block_sum(s, red);
-  ties = block_sum(ties, red);
-  if (threadIdx.x == 0) {
-    part[((int64_t)blockIdx.y * MN_NB + blockIdx.x) * 2] = s;
-    part[((int64_t)blockIdx.y * MN_NB + blockIdx.x) * 2 + 1] = ties;
-  }
-}
-
-// phase 2: every thread sums the MN_NB partials in the same order (deterministic), then applies
-__global__ void __launch_bounds__(256) maxnorm_bwd_apply_kernel(const float* __restrict__ img,
-                                                                const float* __restrict__ gmax,
-                                                                const float* __restrict__ g_out,
-                                                                const float* __restrict__ part,
-                                                                float* __restrict__ g_img, int n) {
-  const float* x = img + (int64_t)blockIdx.y * n;
-  const float* gy = g_out + (int64_t)blockIdx.y * n;
-  float* gx = g_img + (int64_t)blockIdx.y * n;
-  const float m = gmax[blockIdx.y];
-  float s = 0.f, ties = 0.f;
-#pragma unroll 8
-  for (int k = 0; k < MN_NB; ++k) {
-    s += part[((int64_t)blockIdx.y * MN_NB + k) * 2];
-    ties += part[((int64_t)blockIdx.y * MN_NB + k) * 2 + 1];
-  }
-  const float corr = s / (m * m) / ties;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float g = gy[i] / m;
-    if (x[i] == m) g -= corr;
-    gx[i] = g;
-  }
-}
-
-// ---- max-normalisation fused with the loss-net input (styler_3p.py:158 + styler_base.py:41-45, vgg.py:50-53) ------------
-// The grey render at the loss net's own size (resize_scale 1): x[.,c] = (img / max) * 255 - mean[c] in one pass, and the
-// adjoint g_img = adjoint_maxnorm(255 * (g_x[.,0] + g_x[.,1] + g_x[.,2])) in two (partial sums, apply) -- the same
-// arithmetic (to float32 rounding) as nfs_maxnorm_fwd + nfs_loss_net_input_fwd and nfs_loss_net_input_bwd + nfs_maxnorm_bwd,
-// without the [V,H,W] intermediates and with two launches less per direction.
+// The policies.  Plain is K5, y = x / max and g_y as it comes.  Input is K5f, the max-normalisation fused with the
+// loss-net input (styler_3p.py:158 + styler_base.py:41-45, vgg.py:50-53) for the grey render at the loss net's own size
+// (resize_scale 1): StoreInput writes x[.,c] = (img / max) * 255 - mean[c], GradInput reads
+// 255 * (g_x[.,0] + g_x[.,1] + g_x[.,2]) -- the same arithmetic (to float32 rounding) as nfs_maxnorm_fwd +
+// nfs_loss_net_input_fwd and nfs_loss_net_input_bwd + nfs_maxnorm_bwd, through the same kernels as K5, without the
+// [V,H,W] intermediates and with two launches less per direction.
 __constant__ float kInputMean[3] = {0.485f * 255.f, 0.456f * 255.f, 0.406f * 255.f};
 
-__global__ void __launch_bounds__(256) maxnorm_input_kernel(const float* __restrict__ img, const float* __restrict__ gmax,
-                                                            float* __restrict__ xo, int n) {
-  const float m = gmax[blockIdx.y];
-  const float* x = img + (int64_t)blockIdx.y * n;
-  float* o = xo + (int64_t)blockIdx.y * n * 3;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float v = __fmul_rn(x[i] / m, 255.f);        // (rounded like the stored intermediate of the two-step form)
+struct StorePlain {                                     // y = x / m
+  static constexpr int C = 1;
+  static __device__ __forceinline__ void put(float* __restrict__ o, int i, float x, float m) { o[i] = x / m; }
+};
+struct StoreInput {                                     // the loss net's three channels
+  static constexpr int C = 3;
+  static __device__ __forceinline__ void put(float* __restrict__ o, int i, float x, float m) {
+    const float v = __fmul_rn(x / m, 255.f);            // (rounded like the stored intermediate of the two-step form)
     o[3 * (int64_t)i] = __fsub_rn(v, kInputMean[0]);
     o[3 * (int64_t)i + 1] = __fsub_rn(v, kInputMean[1]);
     o[3 * (int64_t)i + 2] = __fsub_rn(v, kInputMean[2]);
   }
+};
+struct GradPlain {
+  static constexpr int C = 1;
+  static __device__ __forceinline__ float at(const float* __restrict__ g, int i) { return g[i]; }
+};
+struct GradInput {                                      // 255 (g[.,0] + g[.,1] + g[.,2])
+  static constexpr int C = 3;
+  static __device__ __forceinline__ float at(const float* __restrict__ g, int64_t i) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(g[3 * i], 255.f), __fmul_rn(g[3 * i + 1], 255.f)), __fmul_rn(g[3 * i + 2], 255.f));
+  }
+};
+
+// y = x/m, m = max(x):  g_x[i] = g_y[i]/m - [x[i]==m]/ties * sum_j g_y[j] x[j] / m^2
+// element i's share of the adjoint's sums: s = sum g x, ties = the number of x == m
+template <class Grad>
+__device__ __forceinline__ void adj_sums(const float* __restrict__ x, const float* __restrict__ g, float m, int i, float& s,
+                                         float& ties) {
+  const float xi = x[i];
+  s += Grad::at(g, i) * xi;
+  ties += (xi == m) ? 1.f : 0.f;
+}
+// what the adjoint takes off every element that holds the maximum, from the group's sums
+__device__ __forceinline__ float adj_corr(float s, float m, float ties) { return s / (m * m) / ties; }
+template <class Grad>
+__device__ __forceinline__ void adj_apply(const float* __restrict__ x, const float* __restrict__ g, float m, float corr,
+                                          float* __restrict__ gx, int i) {
+  float gi = Grad::at(g, i) / m;
+  if (x[i] == m) gi -= corr;
+  gx[i] = gi;
 }
 
-// large groups, ONE launch: every one of the MN_NB blocks of a group first takes the maximum of the WHOLE group (n floats
+// -- small groups (< 16384 elements): one 1024-thread block per group does the maximum and the pass (no fill, no atomics)
+template <class Store>
+__global__ void __launch_bounds__(1024) maxnorm_fwd_kernel(const float* __restrict__ img, float* __restrict__ gmax,
+                                                           float* __restrict__ out, int n) {
+  __shared__ float red[16];
+  const float* x = img + (int64_t)blockIdx.x * n;
+  float* o = out + (int64_t)blockIdx.x * n * Store::C;
+  float m = -INFINITY;
+  NFS_STRIDED_MAX(m, x, threadIdx.x, n, blockDim.x);
+  m = block_max(m, red);
+  if (threadIdx.x == 0) gmax[blockIdx.x] = m;
+  NFS_STRIDED(i, threadIdx.x, n, blockDim.x) Store::put(o, i, x[i], m);
+}
+
+__global__ void __launch_bounds__(1024) maxnorm_bwd_kernel(const float* __restrict__ img,
+                                                           const float* __restrict__ gmax,
+                                                           const float* __restrict__ g_out,
+                                                           float* __restrict__ g_img, int n) {
+  __shared__ float red[16];
+  const float* x = img + (int64_t)blockIdx.x * n;
+  const float* gy = g_out + (int64_t)blockIdx.x * n;
+  float* gx = g_img + (int64_t)blockIdx.x * n;
+  const float m = gmax[blockIdx.x];
+  float s = 0.f, ties = 0.f;
+  NFS_STRIDED(i, threadIdx.x, n, blockDim.x) adj_sums<GradPlain>(x, gy, m, i, s, ties);
+  s = block_sum(s, red);
+  ties = block_sum(ties, red);
+  const float corr = adj_corr(s, m, ties);
+  NFS_STRIDED(i, threadIdx.x, n, blockDim.x) adj_apply<GradPlain>(x, gy, m, corr, gx, i);
+}
+
+// -- large groups: MN_NB 256-thread blocks per group (grid MN_NB x G)
+__global__ void __launch_bounds__(256) maxnorm_max_kernel(const float* __restrict__ img, float* __restrict__ gmax, int n) {
+  __shared__ float red[16];
+  const float* x = img + (int64_t)blockIdx.y * n;
+  float m = -INFINITY;
+  NFS_STRIDED_MAX(m, x, blockIdx.x * blockDim.x + threadIdx.x, n, gridDim.x * blockDim.x);
+  m = block_max(m, red);
+  if (threadIdx.x == 0) atomic_max_float(gmax + blockIdx.y, m);
+}
+
+template <class Store>
+__global__ void __launch_bounds__(256) maxnorm_store_kernel(const float* __restrict__ img, const float* __restrict__ gmax,
+                                                            float* __restrict__ out, int n) {
+  const float m = gmax[blockIdx.y];
+  const float* x = img + (int64_t)blockIdx.y * n;
+  float* o = out + (int64_t)blockIdx.y * n * Store::C;
+  NFS_STRIDED(i, blockIdx.x * blockDim.x + threadIdx.x, n, gridDim.x * blockDim.x) Store::put(o, i, x[i], m);
+}
+
+// ONE launch: every one of the MN_NB blocks of a group first takes the maximum of the WHOLE group (n floats
 // from L2: 160 KB at 200 x 200 -- the maximum does not depend on the order it is taken in, so all blocks hold the same
 // value), then does its share of the pass.  Replaces -inf fill + atomic-max kernel + pass (three launches of ~5 us each on
 // the latency floor) by one; same arithmetic per pixel, bit-identical x and gmax.
@@ -679,56 +769,27 @@ __global__ void __launch_bounds__(256) maxnorm_input_allmax_kernel(const float* 
       const float4 v = x4[i];
       m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
     }
-    for (int i = 4 * n4 + threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
+    NFS_STRIDED_MAX(m, x, 4 * n4 + threadIdx.x, n, 256);
   } else {
-    for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
+    NFS_STRIDED_MAX(m, x, threadIdx.x, n, 256);
   }
   m = block_max(m, red);
   if (blockIdx.x == 0 && threadIdx.x == 0) gmax[blockIdx.y] = m;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float v = __fmul_rn(x[i] / m, 255.f);        // (rounded like the stored intermediate of the two-step form)
-    o[3 * (int64_t)i] = __fsub_rn(v, kInputMean[0]);
-    o[3 * (int64_t)i + 1] = __fsub_rn(v, kInputMean[1]);
-    o[3 * (int64_t)i + 2] = __fsub_rn(v, kInputMean[2]);
-  }
+  NFS_STRIDED(i, blockIdx.x * blockDim.x + threadIdx.x, n, gridDim.x * blockDim.x) StoreInput::put(o, i, x[i], m);
 }
 
-// small groups (< 16384 pixels): one block per group does the maximum and the pass (no memset, no atomics)
-__global__ void __launch_bounds__(1024) maxnorm_input_small_kernel(const float* __restrict__ img, float* __restrict__ gmax,
-                                                                   float* __restrict__ xo, int n) {
-  __shared__ float red[16];
-  const float* x = img + (int64_t)blockIdx.x * n;
-  float* o = xo + (int64_t)blockIdx.x * n * 3;
-  float m = -INFINITY;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, x[i]);
-  m = block_max(m, red);
-  if (threadIdx.x == 0) gmax[blockIdx.x] = m;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const float v = __fmul_rn(x[i] / m, 255.f);        // (rounded like the stored intermediate of the two-step form)
-    o[3 * (int64_t)i] = __fsub_rn(v, kInputMean[0]);
-    o[3 * (int64_t)i + 1] = __fsub_rn(v, kInputMean[1]);
-    o[3 * (int64_t)i + 2] = __fsub_rn(v, kInputMean[2]);
-  }
-}
-
-__device__ __forceinline__ float input_grad_sum(const float* g, int64_t i) {
-  return __fadd_rn(__fadd_rn(__fmul_rn(g[3 * i], 255.f), __fmul_rn(g[3 * i + 1], 255.f)), __fmul_rn(g[3 * i + 2], 255.f));
-}
-
-__global__ void __launch_bounds__(256) maxnorm_input_bwd_part_kernel(const float* __restrict__ img,
-                                                                     const float* __restrict__ gmax,
-                                                                     const float* __restrict__ g_x,
-                                                                     float* __restrict__ part, int n) {
+// adjoint, phase 1: per-block partial sums of g*x and of the tie count -> part[group][block][2]
+template <class Grad>
+__global__ void __launch_bounds__(256) maxnorm_bwd_part_kernel(const float* __restrict__ img,
+                                                               const float* __restrict__ gmax,
+                                                               const float* __restrict__ g_out,
+                                                               float* __restrict__ part, int n) {
   __shared__ float red[16];
   const float* x = img + (int64_t)blockIdx.y * n;
-  const float* gx = g_x + (int64_t)blockIdx.y * n * 3;
+  const float* gy = g_out + (int64_t)blockIdx.y * n * Grad::C;
   const float m = gmax[blockIdx.y];
   float s = 0.f, ties = 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float xi = x[i];
-    s += input_grad_sum(gx, i) * xi;
-    ties += (xi == m) ? 1.f : 0.f;
-  }
+  NFS_STRIDED(i, blockIdx.x * blockDim.x + threadIdx.x, n, gridDim.x * blockDim.x) adj_sums<Grad>(x, gy, m, i, s, ties);
   s = block_sum(s, red);
   ties = block_sum(ties, red);
   if (threadIdx.x == 0) {
@@ -737,14 +798,16 @@ __global__ void __launch_bounds__(256) maxnorm_input_bwd_part_kernel(const float
   }
 }
 
-__global__ void __launch_bounds__(256) maxnorm_input_bwd_apply_kernel(const float* __restrict__ img,
-                                                                      const float* __restrict__ gmax,
-                                                                      const float* __restrict__ g_x,
-                                                                      const float* __restrict__ part,
-                                                                      float* __restrict__ g_img, int n) {
+// phase 2: every thread sums the MN_NB partials in the same order (deterministic), then applies
+template <class Grad>
+__global__ void __launch_bounds__(256) maxnorm_bwd_apply_kernel(const float* __restrict__ img,
+                                                                const float* __restrict__ gmax,
+                                                                const float* __restrict__ g_out,
+                                                                const float* __restrict__ part,
+                                                                float* __restrict__ g_img, int n) {
   const float* x = img + (int64_t)blockIdx.y * n;
-  const float* gx = g_x + (int64_t)blockIdx.y * n * 3;
-  float* go = g_img + (int64_t)blockIdx.y * n;
+  const float* gy = g_out + (int64_t)blockIdx.y * n * Grad::C;
+  float* gx = g_img + (int64_t)blockIdx.y * n;
   const float m = gmax[blockIdx.y];
   float s = 0.f, ties = 0.f;
 #pragma unroll 8
@@ -752,50 +815,8 @@ __global__ void __launch_bounds__(256) maxnorm_input_bwd_apply_kernel(const floa
     s += part[((int64_t)blockIdx.y * MN_NB + k) * 2];
     ties += part[((int64_t)blockIdx.y * MN_NB + k) * 2 + 1];
   }
-  const float corr = s / (m * m) / ties;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float g = input_grad_sum(gx, i) / m;
-    if (x[i] == m) g -= corr;
-    go[i] = g;
-  }
-}
-
-__global__ void __launch_bounds__(1024) maxnorm_fwd_kernel(const float* __restrict__ img, float* __restrict__ out,
-                                                           float* __restrict__ gmax, int n) {
-  __shared__ float red[16];
-  const float* x = img + (int64_t)blockIdx.x * n;
-  float* o = out + (int64_t)blockIdx.x * n;
-  float m = -INFINITY;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, x[i]);
-  m = block_max(m, red);
-  if (threadIdx.x == 0) gmax[blockIdx.x] = m;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = x[i] / m;
-}
-
-// y = x/m, m = max(x):  g_x[i] = g_y[i]/m - [x[i]==m]/ties * sum_j g_y[j] x[j] / m^2
-__global__ void __launch_bounds__(1024) maxnorm_bwd_kernel(const float* __restrict__ img,
-                                                           const float* __restrict__ gmax,
-                                                           const float* __restrict__ g_out,
-                                                           float* __restrict__ g_img, int n) {
-  __shared__ float red[16];
-  const float* x = img + (int64_t)blockIdx.x * n;
-  const float* gy = g_out + (int64_t)blockIdx.x * n;
-  float* gx = g_img + (int64_t)blockIdx.x * n;
-  const float m = gmax[blockIdx.x];
-  float s = 0.f, ties = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const float xi = x[i];
-    s += gy[i] * xi;
-    ties += (xi == m) ? 1.f : 0.f;
-  }
-  s = block_sum(s, red);
-  ties = block_sum(ties, red);
-  const float corr = s / (m * m) / ties;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    float g = gy[i] / m;
-    if (x[i] == m) g -= corr;
-    gx[i] = g;
-  }
+  const float corr = adj_corr(s, m, ties);
+  NFS_STRIDED(i, blockIdx.x * blockDim.x + threadIdx.x, n, gridDim.x * blockDim.x) adj_apply<Grad>(x, gy, m, corr, gx, i);
 }
 
 // per (view, depth segment, ray): the coefficients of dI/ds = A u - B for the rotate adjoint's COEF form, from the UOUT
@@ -812,20 +833,18 @@ __global__ void __launch_bounds__(256) render_ray_coef_kernel(const float* __res
   const int64_t total = (int64_t)V * HW, gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float bound = 0.f;
   if (gid < total) {
-    const int v = (int)(gid / HW), px = (int)(gid - (int64_t)v * HW);
+    NFS_RAY_INDEX(gid, HW, v, px);
     const int64_t plane = (int64_t)V * RR_SEG * HW, at0 = (int64_t)v * RR_SEG * HW + px;
-    const float ntau = -tau * 1.44269504088896341f, g = g_img[gid];
+    const float ntau = exp2_rate(tau), g = g_img[gid];
     float S[RR_SEG], Is[RR_SEG], um[RR_SEG], E[RR_SEG], F[RR_SEG];
     float P = 0.f, Itot = 0.f;
 #pragma unroll
-    for (int s2 = 0; s2 < RR_SEG; ++s2) {          // same order of sums as the forward's own combination
+    for (int s2 = 0; s2 < RR_SEG; ++s2) {          // the forward's own combination
       S[s2] = seg[at0 + (int64_t)s2 * HW];
       Is[s2] = seg[plane + at0 + (int64_t)s2 * HW];
       um[s2] = seg[2 * plane + at0 + (int64_t)s2 * HW];
-      E[s2] = __builtin_amdgcn_exp2f(P * ntau);
       F[s2] = Itot;
-      Itot = fmaf(E[s2], Is[s2], Itot);
-      P += S[s2];
+      E[s2] = seg_combine(S[s2], Is[s2], ntau, P, Itot);
     }
 #pragma unroll
     for (int s2 = 0; s2 < RR_SEG; ++s2) {
@@ -838,6 +857,43 @@ __global__ void __launch_bounds__(256) render_ray_coef_kernel(const float* __res
   if (threadIdx.x == 0) bounds[blockIdx.x] = bound > 0.f ? fminf(bound, 3.0e38f) : 0.f;   // (NaN -> 0: no finite scale)
 }
 
+// ---- launch side -----------------------------------------------------------------------
+static int check_view_dims(const char* who, int V, int D, int H, int W) {
+  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "%s: non-positive dimension", who);
+  return NFS_OK;
+}
+static int check_ray_mode(const char* who, int liquid) {
+  NFS_REQUIRE(liquid >= 0 && liquid <= 3, "%s: mode must be 0 (transmittance), 1 (liquid), 2 (max) or 3 (mean)", who);
+  return NFS_OK;
+}
+
+// does the segmented forward take this shape?  need32: with the buffer addressing of its REUSE form (32-bit byte offsets
+// into the kept volume), which the u / coefficient form of the adjoint needs
+static bool seg_takes(int V, int D, int H, int W, bool need32) {
+  return W >= 2 && H >= 2 && D >= 4 * RR_SEG && (int64_t)D * H * W < (1ll << 31) &&
+         (!need32 || (int64_t)V * D * H * W < (1ll << 30));
+}
+
+// the one launch of rotate_render_fwd_seg_kernel, for a shape seg_takes() accepts.  seg_out: the coefficient form (UOUT).
+// tile / band / reuse: the NFS_RR_TILE / NFS_RR_BAND / NFS_RR_NOREUSE ablation switches of nfs_rotate_render_fwd.
+struct SegOpts { int tile = -1, band = 1; bool reuse = true; };
+static int seg_launch(const char* who, const SegOpts& o, const float* d, const float* rot, float* img, float* raysum,
+                      float* d_rot, float* seg_out, int V, int D, int H, int W, float tau, int liquid,
+                      nfs_stream_t stream) {
+  // wave footprint: 16 x 4 pixel tiles when the image has room for them, else 64 consecutive pixels
+  const int lxb = o.tile >= 0 ? o.tile : (W >= 16 && H >= 4 ? 4 : 0);
+  int64_t waves = blocks_for((int64_t)V * H * W, 64);
+  const int64_t tiles_v = (int64_t)((W + (1 << lxb) - 1) >> lxb) * ((H + (64 >> lxb) - 1) / (64 >> lxb));
+  if (lxb) waves = (int64_t)V * tiles_v;
+  if (lxb && o.band) waves = (int64_t)V * ((tiles_v + 7) / 8) * 8;
+  auto kernel = seg_out ? rotate_render_fwd_seg_kernel<true, true>
+                        : o.reuse && seg_takes(V, D, H, W, true) ? rotate_render_fwd_seg_kernel<true>
+                                                                 : rotate_render_fwd_seg_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((waves + 7) / 8 * 8), dim3(256), 0, as_stream(stream), d, rot, img, raysum, d_rot, V,
+                     D, H, W, tau, liquid, lxb, lxb ? o.band : 0, seg_out);
+  return check_launch(who);
+}
+
 }  // namespace nfs
 
 using namespace nfs;
@@ -847,80 +903,22 @@ extern "C" {
 int nfs_render_fwd(const float* d, float* img, float* raysum, int V, int D, int H, int W, float tau, int liquid,
                    nfs_stream_t stream) {
   NFS_REQUIRE(d && img, "nfs_render_fwd: null pointer");
-  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "nfs_render_fwd: non-positive dimension");
-  NFS_REQUIRE(liquid >= 0 && liquid <= 3, "nfs_render_fwd: mode must be 0 (transmittance), 1 (liquid), 2 (max) or 3 (mean)");
+  if (int e = check_view_dims("nfs_render_fwd", V, D, H, W)) return e;
+  if (int e = check_ray_mode("nfs_render_fwd", liquid)) return e;
   const int64_t n = (int64_t)V * H * W;
   hipLaunchKernelGGL(render_fwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d, img, raysum, V, D,
                      H * W, tau, liquid);
   return check_launch("nfs_render_fwd");
 }
 
-// Segmented render adjoint for small batches (one or two views per GPU): with V*H*W = 40 k rays a one-thread-per-ray
-// march is latency-bound (80 us for a 32 MB volume).  Four waves share 64 rays, one depth segment each; a first walk
-// gives every segment its ray sum S and R = sum s*exp(-tau (total - local prefix)), the block combines them into the
-// segment's starting prefix / weighted sum (the transmittance factorises: exp(-tau (total - p0 - local)) =
-// exp(tau p0) * exp(-tau (total - local))), a second walk writes the gradient.  The volume is read twice, so this
-// form is only used while it stays cache-resident (<= 64 MB).
-extern "C++" {
-template <int NSEG>
-__global__ void __launch_bounds__(64 * NSEG) render_bwd_seg_kernel(const float* d, const float* __restrict__ raysum,
-                                                                   const float* __restrict__ g_img, float* g_d, int V,
-                                                                   int D, int HW, float tau,
-                                                                   unsigned* __restrict__ gmax_bits) {
-  __shared__ float seg_S[NSEG][64], seg_R[NSEG][64], red[16];
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int64_t total_rays = (int64_t)V * HW;
-  const int64_t gid_raw = (int64_t)blockIdx.x * 64 + lane;
-  const bool live = gid_raw < total_rays;
-  const int64_t gid = live ? gid_raw : total_rays - 1;
-  const int v = (int)(gid / HW);
-  const int px = (int)(gid - (int64_t)v * HW);
-  const int64_t base = (int64_t)v * D * HW + px;
-  const float total = raysum[gid], g = g_img[gid];
-  const float ntau = -tau * 1.44269504088896341f;
-  const int L = (D + NSEG - 1) / NSEG;
-  const int zlo = min(seg * L, D), zhi = min(zlo + L, D);         // segment 0 starts at z = 0 (prefix order)
-  float S = 0.f, R = 0.f;
-#pragma unroll 4
-  for (int z = zlo; z < zhi; ++z) {
-    const float sv = d[base + (int64_t)z * HW];
-    R = fmaf(sv, __builtin_amdgcn_exp2f((total - S) * ntau), R);
-    S += sv;
-  }
-  seg_S[seg][lane] = S;
-  seg_R[seg][lane] = R;
-  __syncthreads();
-  float p0 = 0.f, P = 0.f;                                        // prefix and weighted sum before this segment
-  for (int j = 0; j < seg; ++j) {
-    P = fmaf(__builtin_amdgcn_exp2f(-p0 * ntau), seg_R[j][lane], P);
-    p0 += seg_S[j][lane];
-  }
-  float prefix = p0, amax = 0.f;
-#pragma unroll 4
-  for (int z = zlo; z < zhi; ++z) {
-    const float sv = d[base + (int64_t)z * HW];
-    const float T = __builtin_amdgcn_exp2f((total - prefix) * ntau);
-    P = fmaf(sv, T, P);
-    const float o = g * (T - tau * P);
-    if (live) g_d[base + (int64_t)z * HW] = o;
-    amax = fmaxf(amax, fabsf(o));
-    prefix += sv;
-  }
-  if (gmax_bits) {
-    amax = block_max(live ? amax : 0.f, red);
-    if (threadIdx.x == 0 && amax > 0.f) atomicMax(gmax_bits, __float_as_uint(fminf(amax, 3.0e38f)));
-  }
-}
-}  // extern "C++"
-
 int nfs_render_bwd(const float* d, const float* raysum, const float* g_img, float* g_d, int V, int D, int H, int W,
                    float tau, int liquid, float* gmax_out, nfs_stream_t stream) {
   NFS_REQUIRE(d && raysum && g_img && g_d, "nfs_render_bwd: null pointer");
-  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "nfs_render_bwd: non-positive dimension");
+  if (int e = check_view_dims("nfs_render_bwd", V, D, H, W)) return e;
   const int64_t n = (int64_t)V * H * W;
   if (gmax_out) zero_words(gmax_out, 1, as_stream(stream));               // (a kernel, not a memset node: common.h)
   static const bool no_seg = getenv("NFS_RB_NOSEG") != nullptr;   // timing comparisons only
-  NFS_REQUIRE(liquid >= 0 && liquid <= 3, "nfs_render_bwd: mode must be 0 (transmittance), 1 (liquid), 2 (max) or 3 (mean)");
+  if (int e = check_ray_mode("nfs_render_bwd", liquid)) return e;
   if (!liquid && !no_seg && D >= 4 * RR_SEG && (int64_t)V * D * H * W <= ((int64_t)16 << 20)) {
     // segments per ray: 4, or 8 while the 64-ray blocks are few (200^2 rays: one view 32.5 -> 24.7 us, two views
     // 45.0 -> 41.2 us; 16 segments 25.4 / 39.7; tools/render_family_by_views.py, NFS_RB_SEG forces a count)
@@ -930,15 +928,9 @@ int nfs_render_bwd(const float* d, const float* raysum, const float* g_img, floa
     if (seg_env == 4 || seg_env == 8 || seg_env == 16) nseg = seg_env;
     while (nseg > 4 && D < 4 * nseg) nseg /= 2;
     unsigned* gm = reinterpret_cast<unsigned*>(gmax_out);
-    if (nseg == 16)
-      hipLaunchKernelGGL(render_bwd_seg_kernel<16>, dim3(blocks), dim3(1024), 0, as_stream(stream), d, raysum, g_img, g_d,
-                         V, D, H * W, tau, gm);
-    else if (nseg == 8)
-      hipLaunchKernelGGL(render_bwd_seg_kernel<8>, dim3(blocks), dim3(512), 0, as_stream(stream), d, raysum, g_img, g_d,
-                         V, D, H * W, tau, gm);
-    else
-      hipLaunchKernelGGL(render_bwd_seg_kernel<4>, dim3(blocks), dim3(256), 0, as_stream(stream), d, raysum, g_img, g_d,
-                         V, D, H * W, tau, gm);
+    auto kernel = nseg == 16 ? render_bwd_seg_kernel<16> : nseg == 8 ? render_bwd_seg_kernel<8> : render_bwd_seg_kernel<4>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * nseg), 0, as_stream(stream), d, raysum, g_img, g_d, V, D, H * W,
+                       tau, gm);
     return check_launch("nfs_render_bwd(segmented)");
   }
   hipLaunchKernelGGL(render_bwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d, raysum, g_img, g_d,
@@ -949,46 +941,27 @@ int nfs_render_bwd(const float* d, const float* raysum, const float* g_img, floa
 int nfs_rotate_render_fwd(const float* d, const float* rot, float* img, float* raysum, float* d_rot, int V, int D,
                           int H, int W, float tau, int liquid, nfs_stream_t stream) {
   NFS_REQUIRE(d && rot && img, "nfs_rotate_render_fwd: null pointer");
-  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "nfs_rotate_render_fwd: non-positive dimension");
+  if (int e = check_view_dims("nfs_rotate_render_fwd", V, D, H, W)) return e;
   NFS_REQUIRE(liquid == 0 || liquid == 1, "nfs_rotate_render_fwd: ray modes 2 / 3 go through nfs_rotate_fwd + nfs_render_fwd");
-  const int64_t n = (int64_t)V * H * W;
-  static const bool no_seg = getenv("NFS_RR_NOSEG") != nullptr;   // timing comparisons only
-  static const bool no_reuse = getenv("NFS_RR_NOREUSE") != nullptr;   // timing comparisons only
-  static const int tile_env = getenv("NFS_RR_TILE") ? atoi(getenv("NFS_RR_TILE")) : -1;
-  if (W >= 2 && H >= 2 && D >= 4 * RR_SEG && (int64_t)D * H * W < (1ll << 31) && !no_seg) {
-    // wave footprint: 16 x 4 pixel tiles when the image has room for them, else 64 consecutive pixels
-    const int lxb = tile_env >= 0 ? tile_env : (W >= 16 && H >= 4 ? 4 : 0);
-    static const int band = getenv("NFS_RR_BAND") ? atoi(getenv("NFS_RR_BAND")) : 1;   // 0: one view per XCD
-    int64_t waves = blocks_for(n, 64);
-    const int64_t tiles_v = (int64_t)((W + (1 << lxb) - 1) >> lxb) * ((H + (64 >> lxb) - 1) / (64 >> lxb));
-    if (lxb) waves = (int64_t)V * tiles_v;
-    if (lxb && band) waves = (int64_t)V * ((tiles_v + 7) / 8) * 8;
-    const dim3 grid((waves + 7) / 8 * 8);
-    const bool fits32 = (int64_t)V * D * H * W < (1ll << 30);      // byte offsets of the buffer addressing
-    if (fits32 && !no_reuse)
-      hipLaunchKernelGGL(rotate_render_fwd_seg_kernel<true>, grid, dim3(256), 0, as_stream(stream), d, rot, img,
-                         raysum, d_rot, V, D, H, W, tau, liquid, lxb, lxb ? band : 0);
-    else
-      hipLaunchKernelGGL(rotate_render_fwd_seg_kernel<false>, grid, dim3(256), 0, as_stream(stream), d, rot, img,
-                         raysum, d_rot, V, D, H, W, tau, liquid, lxb, lxb ? band : 0);
-  } else
-    hipLaunchKernelGGL(rotate_render_fwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d, rot,
-                       img, raysum, d_rot, V, D, H, W, tau, liquid);
+  static const bool no_seg = getenv("NFS_RR_NOSEG") != nullptr;   // the four: timing comparisons only
+  static const SegOpts opts{getenv("NFS_RR_TILE") ? atoi(getenv("NFS_RR_TILE")) : -1,
+                            getenv("NFS_RR_BAND") ? atoi(getenv("NFS_RR_BAND")) : 1,   // 0: one view per XCD
+                            getenv("NFS_RR_NOREUSE") == nullptr};
+  if (seg_takes(V, D, H, W, false) && !no_seg)
+    return seg_launch("nfs_rotate_render_fwd", opts, d, rot, img, raysum, d_rot, nullptr, V, D, H, W, tau, liquid, stream);
+  hipLaunchKernelGGL(rotate_render_fwd_kernel, dim3(blocks_for((int64_t)V * H * W, 256)), dim3(256), 0, as_stream(stream),
+                     d, rot, img, raysum, d_rot, V, D, H, W, tau, liquid);
   return check_launch("nfs_rotate_render_fwd");
 }
 
 // does the segmented forward (and with it the u / coefficient form of the adjoint) take this shape?  nseg / seg_len: the
 // depth segments of a ray, far end first (segment of plane z = (D - 1 - z) / seg_len)
 int nfs_render_coef_layout(int V, int D, int H, int W, int* nseg, int* seg_len) {
-  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "nfs_render_coef_layout: non-positive dimension");
+  if (int e = check_view_dims("nfs_render_coef_layout", V, D, H, W)) return e;
   if (nseg) *nseg = RR_SEG;
   if (seg_len) *seg_len = (D + RR_SEG - 1) / RR_SEG;
-  const bool ok = W >= 2 && H >= 2 && D >= 4 * RR_SEG && (int64_t)D * H * W < (1ll << 31) &&
-                  (int64_t)V * D * H * W < (1ll << 30);
-  if (!ok) {
-    set_error("nfs_render_coef_layout: shape outside the segmented forward (needs D >= 16, H, W >= 2, V*D*H*W < 2^30)");
-    return NFS_EINVAL;
-  }
+  NFS_REQUIRE(seg_takes(V, D, H, W, true),
+              "nfs_render_coef_layout: shape outside the segmented forward (needs D >= 16, H, W >= 2, V*D*H*W < 2^30)");
   return NFS_OK;
 }
 
@@ -996,13 +969,7 @@ int nfs_rotate_render_fwd_coef(const float* d, const float* rot, float* img, flo
                                int V, int D, int H, int W, float tau, nfs_stream_t stream) {
   NFS_REQUIRE(d && rot && img && u_rot && seg, "nfs_rotate_render_fwd_coef: null pointer");
   if (int e = nfs_render_coef_layout(V, D, H, W, nullptr, nullptr)) return e;
-  const int lxb = W >= 16 && H >= 4 ? 4 : 0;
-  int64_t waves = blocks_for((int64_t)V * H * W, 64);
-  const int64_t tiles_v = (int64_t)((W + (1 << lxb) - 1) >> lxb) * ((H + (64 >> lxb) - 1) / (64 >> lxb));
-  if (lxb) waves = (int64_t)V * ((tiles_v + 7) / 8) * 8;
-  hipLaunchKernelGGL((rotate_render_fwd_seg_kernel<true, true>), dim3((waves + 7) / 8 * 8), dim3(256), 0,
-                     as_stream(stream), d, rot, img, raysum, u_rot, V, D, H, W, tau, 0, lxb, lxb ? 1 : 0, seg);
-  return check_launch("nfs_rotate_render_fwd_coef");
+  return seg_launch("nfs_rotate_render_fwd_coef", SegOpts{}, d, rot, img, raysum, u_rot, seg, V, D, H, W, tau, 0, stream);
 }
 
 int nfs_render_ray_coef_bounds(int V, int H, int W) {
@@ -1013,7 +980,7 @@ int nfs_render_ray_coef_bounds(int V, int H, int W) {
 int nfs_render_ray_coef(const float* g_img, const float* seg, float* ab, float* bounds, int V, int H, int W, float tau,
                         nfs_stream_t stream) {
   NFS_REQUIRE(g_img && seg && ab && bounds, "nfs_render_ray_coef: null pointer");
-  NFS_REQUIRE(V > 0 && H > 0 && W > 0, "nfs_render_ray_coef: non-positive dimension");
+  if (int e = check_view_dims("nfs_render_ray_coef", V, /* no depth here: D = */ 1, H, W)) return e;
   const int64_t n = (int64_t)V * H * W;
   hipLaunchKernelGGL(render_ray_coef_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), g_img, seg,
                      reinterpret_cast<float2*>(ab), V, H * W, tau, bounds);
@@ -1023,7 +990,7 @@ int nfs_render_ray_coef(const float* g_img, const float* seg, float* ab, float* 
 int nfs_rotate_render_bwd(const float* d, const float* rot, const float* raysum, const float* g_img, float* g_d_acc,
                           int V, int D, int H, int W, float tau, int liquid, nfs_stream_t stream) {
   NFS_REQUIRE(d && rot && raysum && g_img && g_d_acc, "nfs_rotate_render_bwd: null pointer");
-  NFS_REQUIRE(V > 0 && D > 0 && H > 0 && W > 0, "nfs_rotate_render_bwd: non-positive dimension");
+  if (int e = check_view_dims("nfs_rotate_render_bwd", V, D, H, W)) return e;
   NFS_REQUIRE(liquid == 0 || liquid == 1, "nfs_rotate_render_bwd: ray modes 2 / 3 go through nfs_render_bwd + nfs_rotate_bwd");
   const int64_t n = (int64_t)V * H * W;
   hipLaunchKernelGGL(rotate_render_bwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d, rot, raysum,
@@ -1031,16 +998,18 @@ int nfs_rotate_render_bwd(const float* d, const float* rot, const float* raysum,
   return check_launch("nfs_rotate_render_bwd");
 }
 
+int nfs_maxnorm_workspace_floats(int G) { return 2 * MN_NB * G; }
+
 int nfs_maxnorm_fwd(const float* img, float* out, float* gmax, int G, int n, nfs_stream_t stream) {
   NFS_REQUIRE(img && out && gmax, "nfs_maxnorm_fwd: null pointer");
   NFS_REQUIRE(G > 0 && n > 0, "nfs_maxnorm_fwd: non-positive size");
   if (n >= 16384) {
     hipLaunchKernelGGL(maxnorm_init_kernel, dim3((G + 63) / 64), dim3(64), 0, as_stream(stream), gmax, G);
     hipLaunchKernelGGL(maxnorm_max_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, n);
-    hipLaunchKernelGGL(maxnorm_div_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, out, n);
+    hipLaunchKernelGGL(maxnorm_store_kernel<StorePlain>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, out, n);
     return check_launch("nfs_maxnorm_fwd(multi-block)");
   }
-  hipLaunchKernelGGL(maxnorm_fwd_kernel, dim3(G), dim3(1024), 0, as_stream(stream), img, out, gmax, n);
+  hipLaunchKernelGGL(maxnorm_fwd_kernel<StorePlain>, dim3(G), dim3(1024), 0, as_stream(stream), img, gmax, out, n);
   return check_launch("nfs_maxnorm_fwd");
 }
 
@@ -1048,7 +1017,7 @@ int nfs_maxnorm_input_fwd(const float* img, float* x, float* gmax, int G, int n,
   NFS_REQUIRE(img && x && gmax, "nfs_maxnorm_input_fwd: null pointer");
   NFS_REQUIRE(G > 0 && n > 0, "nfs_maxnorm_input_fwd: non-positive size");
   if (n < 16384) {
-    hipLaunchKernelGGL(maxnorm_input_small_kernel, dim3(G), dim3(1024), 0, as_stream(stream), img, gmax, x, n);
+    hipLaunchKernelGGL(maxnorm_fwd_kernel<StoreInput>, dim3(G), dim3(1024), 0, as_stream(stream), img, gmax, x, n);
     return check_launch("nfs_maxnorm_input_fwd");
   }
   static const bool three = [] { const char* e = getenv("NFS_MAXNORM_3K"); return e && atoi(e) != 0; }();
@@ -1058,7 +1027,7 @@ int nfs_maxnorm_input_fwd(const float* img, float* x, float* gmax, int G, int n,
   }
   hipLaunchKernelGGL(maxnorm_init_kernel, dim3((G + 63) / 64), dim3(64), 0, as_stream(stream), gmax, G);
   hipLaunchKernelGGL(maxnorm_max_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, n);
-  hipLaunchKernelGGL(maxnorm_input_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, x, n);
+  hipLaunchKernelGGL(maxnorm_store_kernel<StoreInput>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, x, n);
   return check_launch("nfs_maxnorm_input_fwd");
 }
 
@@ -1066,9 +1035,9 @@ int nfs_maxnorm_input_bwd(const float* img, const float* gmax, const float* g_x,
                           float* workspace, nfs_stream_t stream) {
   NFS_REQUIRE(img && gmax && g_x && g_img && workspace, "nfs_maxnorm_input_bwd: null pointer");
   NFS_REQUIRE(G > 0 && n > 0, "nfs_maxnorm_input_bwd: non-positive size");
-  hipLaunchKernelGGL(maxnorm_input_bwd_part_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_x,
+  hipLaunchKernelGGL(maxnorm_bwd_part_kernel<GradInput>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_x,
                      workspace, n);
-  hipLaunchKernelGGL(maxnorm_input_bwd_apply_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_x,
+  hipLaunchKernelGGL(maxnorm_bwd_apply_kernel<GradInput>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_x,
                      workspace, g_img, n);
   return check_launch("nfs_maxnorm_input_bwd");
 }
@@ -1078,9 +1047,9 @@ int nfs_maxnorm_bwd(const float* img, const float* gmax, const float* g_out, flo
   NFS_REQUIRE(img && gmax && g_out && g_img, "nfs_maxnorm_bwd: null pointer");
   NFS_REQUIRE(G > 0 && n > 0, "nfs_maxnorm_bwd: non-positive size");
   if (workspace && n >= 16384) {   // two-phase, MN_NB blocks per group, partial sums through the workspace
-    hipLaunchKernelGGL(maxnorm_bwd_part_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_out,
+    hipLaunchKernelGGL(maxnorm_bwd_part_kernel<GradPlain>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_out,
                        workspace, n);
-    hipLaunchKernelGGL(maxnorm_bwd_apply_kernel, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_out,
+    hipLaunchKernelGGL(maxnorm_bwd_apply_kernel<GradPlain>, dim3(MN_NB, G), dim3(256), 0, as_stream(stream), img, gmax, g_out,
                        workspace, g_img, n);
     return check_launch("nfs_maxnorm_bwd(multi-block)");
   }

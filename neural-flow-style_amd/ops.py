@@ -566,7 +566,7 @@ def maxnorm_bwd(img, gmax, g_out, g_img=None):
     n = img.numel() // groups
     if g_img is None:
         g_img = _empty(img.shape, img)
-    ws = _empty((64 * groups,), img)            # partial sums of the multi-block path
+    ws = _empty((_lib.lib().nfs_maxnorm_workspace_floats(groups),), img)     # partial sums of the multi-block path
     _lib.call("nfs_maxnorm_bwd", _ptr(img), _ptr(gmax), _ptr(g_out), _ptr(g_img), groups, n, _ptr(ws), _stream())
     return g_img
 
@@ -585,7 +585,7 @@ def maxnorm_input_bwd(img, gmax, g_x):
     """adjoint of maxnorm_input_fwd: g_x [V,H,W,3] -> g_img [V,H,W]"""
     groups = gmax.numel()
     g_img = _empty(img.shape, img)
-    ws = _empty((64 * groups,), img)
+    ws = _empty((_lib.lib().nfs_maxnorm_workspace_floats(groups),), img)
     _lib.call("nfs_maxnorm_input_bwd", _ptr(img), _ptr(gmax), _ptr(g_x), _ptr(g_img), groups, img.numel() // groups,
               _ptr(ws), _stream())
     return g_img

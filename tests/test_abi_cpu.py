@@ -33,6 +33,8 @@ def test_argument_errors_do_not_need_a_gpu():
     _lib = _ensure_built()
     with pytest.raises(RuntimeError, match="null pointer"):
         _lib.call("nfs_render_fwd", None, None, None, 1, 1, 1, 1, 0.1, 0, None)
+    assert _lib.lib().nfs_version() >= _lib.ABI_VERSION                              # the binding's table and the library
+    assert _lib.lib().nfs_maxnorm_workspace_floats(3) == 2 * 32 * 3                  # (sum, ties) x 32 blocks x groups
     assert _lib.lib().nfs_conv3x3_packed_floats(3, 64, 0) == 9 * 3 * 64              # conv1_1: direct only
     # + Winograd F(4x4,3x3) filters (36 floats per (ci, co))
     # + the same filters in MFMA fragment order, for the 32x32x2 and the 16x16x4 instruction (36 + 36)

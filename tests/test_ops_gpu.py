@@ -233,6 +233,124 @@ def test_maxnorm_multiblock(ops, sign):
     assert torch.equal(gx_h, ops.maxnorm_bwd(dev(x), gmax, dev(g)))
 
 
+@pytest.mark.parametrize("n", [16383, 16384])     # one 1024-thread block per group / 32 blocks per group
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_maxnorm_block_layout_boundary(ops, sign, n):
+    """the two sides of the switch between the one-block and the 32-block kernels, G = 3: the assertions of
+    test_maxnorm_multiblock, and the fused loss-net-input forms against the two-step form on the same data with the
+    bounds of test_maxnorm_input_fused_equals_the_two_step_form.  That test's 4e-5 on x is 2 ulp of the product
+    255 * (normalised value) for a normalised image in [0, 1]; an all-negative group normalises to
+    [1, max |x| / min |x|] (up to 22 here), so each element's bound is 4e-5 times its own normalised magnitude where that
+    exceeds 1: the same 2 ulp of the same product element by element, and 4e-5 itself throughout the positive case"""
+    torch.manual_seed(12)
+    x = (torch.rand(3, n) + 0.1) * sign
+    x[1, 7] = x[1, n - 3] = x[1].max() + 0.5 if sign > 0 else x[1].max() * 0.5    # a tie at the maximum
+    x = x.requires_grad_()
+    y = x / x.amax(dim=1, keepdim=True)
+    g = torch.randn_like(x)
+    (gx,) = torch.autograd.grad(y, x, g)
+    out, gmax = ops.maxnorm_fwd(dev(x), 3)
+    assert torch.equal(gmax.cpu(), x.detach().amax(dim=1)) and rel(out, y) < 1e-6
+    gx_h = ops.maxnorm_bwd(dev(x), gmax, dev(g))
+    assert rel(gx_h, gx) < 1e-5
+    assert torch.equal(gx_h, ops.maxnorm_bwd(dev(x), gmax, dev(g)))
+    # fused with the loss-net input, as an image [3, 1, n]
+    it = dev(x).reshape(3, 1, n)
+    gt = torch.randn(3, 1, n, 3, generator=torch.Generator().manual_seed(13)).cuda()
+    _, x_ref = ops.loss_net_input_fwd(out.reshape(3, 1, n, 1), 1, n, want_d_img=False)
+    gi_ref = ops.maxnorm_bwd(it, gmax, ops.loss_net_input_bwd(gt, 1, n, 1).reshape(3, 1, n))
+    xf, gmax2 = ops.maxnorm_input_fwd(it, 3)
+    gi = ops.maxnorm_input_bwd(it, gmax2, gt)
+    bound = 4e-5 * out.abs().clamp(min=1.0).reshape(3, 1, n, 1)         # |x + mean| <= 255 |out|: 2 ulp, per element
+    worst = float(((xf - x_ref).abs() / bound).max())
+    print("maxnorm boundary n=%d sign=%+d: |x - x_ref| %.3g, worst err/bound %.3g, adjoint rel %.3g"
+          % (n, sign, float((xf - x_ref).abs().max()), worst, rel(gi, gi_ref)))
+    assert torch.equal(gmax, gmax2) and worst <= 1.0
+    assert rel(gi, gi_ref) < 1e-6
+    assert torch.equal(gi, ops.maxnorm_input_bwd(it, gmax2, gt))
+
+
+_MAXNORM_INPUT_SCRIPT = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+import neural_flow_style_amd.ops as ops
+out = {}
+for G, n in ((3, 16387), (1, 16384)):
+    rng = np.random.RandomState(7 + G)
+    x = rng.rand(G, n).astype(np.float32) + 0.1
+    x[G - 1] *= -1.0                                  # an all-negative group
+    x[0, 5] = x[0, n - 2] = 2.0 if G > 1 else 0.5 * x[0].max()        # a tie at the maximum (G = 1: of the negative group)
+    xo, gmax = ops.maxnorm_input_fwd(torch.tensor(x, device="cuda").reshape(G, 1, n), G)
+    out["x_%%d_%%d" %% (G, n)], out["gmax_%%d_%%d" %% (G, n)] = xo.cpu().numpy(), gmax.cpu().numpy()
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_maxnorm_input_one_launch_equals_three_launches(tmp_path):
+    """nfs_maxnorm_input_fwd for large groups: the one-launch form (every block takes the whole group's maximum) and the
+    fill + atomic-max + pass form behind NFS_MAXNORM_3K (read once per process, hence subprocesses) give the same bits,
+    x and gmax -- 16-byte-aligned groups and groups off alignment (n = 16387), a tie, an all-negative group"""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = {}
+    for tag, env in (("one", {}), ("three", {"NFS_MAXNORM_3K": "1"})):
+        f = str(tmp_path / (tag + ".npz"))
+        e = dict(os.environ); e.pop("NFS_MAXNORM_3K", None); e.update(env)
+        subprocess.run([sys.executable, "-c", _MAXNORM_INPUT_SCRIPT % root, f], check=True, env=e, timeout=300)
+        outs[tag] = dict(np.load(f))
+    assert sorted(outs["one"]) == sorted(outs["three"]) and len(outs["one"]) == 4
+    for k, a in outs["one"].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), k
+        assert np.array_equal(a, outs["three"][k]), k
+    assert outs["one"]["gmax_3_16387"][0] == 2.0 and outs["one"]["gmax_3_16387"][2] < 0 and outs["one"]["gmax_1_16384"][0] < 0
+
+
+_RB_SEG_SCRIPT = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+import neural_flow_style_amd.ops as ops
+rng = np.random.RandomState(21)
+d = torch.tensor((rng.rand(2, 64, 5, 13) * 1.2 - 0.2).astype(np.float32), device="cuda")
+g = torch.tensor(rng.randn(2, 5, 13).astype(np.float32), device="cuda")
+img, rs = ops.render_fwd(d, 0.8, 0)
+gd = d.clone()
+_, gmax = ops.render_bwd(gd, rs, g, 0.8, 0, g_d=gd, want_max=True)          # in place
+np.savez(sys.argv[1], d=d.cpu().numpy(), g=g.cpu().numpy(), g_d=gd.cpu().numpy(), gmax=gmax.cpu().numpy())
+"""
+
+
+def test_render_bwd_segment_counts(tmp_path):
+    """the render adjoint with 4, 8 and 16 depth segments per ray and one thread per ray (NFS_RB_SEG / NFS_RB_NOSEG, read
+    once per process, hence subprocesses), transmittance mode, in place, D = 64 (the smallest depth that keeps 16
+    segments), 130 rays (a ragged last 64-ray block): every g_d within the per-element bound of the float64 ray of
+    tests/view_ref.py (as test_render_fwd_bwd, mode 0), the returned maximum exactly max |g_d| of the same run"""
+    import os, subprocess, sys
+    from tests import view_ref as VR
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ref, g_ds = None, {}
+    for tag, env in (("seg4", {"NFS_RB_SEG": "4"}), ("seg8", {"NFS_RB_SEG": "8"}), ("seg16", {"NFS_RB_SEG": "16"}),
+                     ("noseg", {"NFS_RB_NOSEG": "1"})):
+        f = str(tmp_path / (tag + ".npz"))
+        e = dict(os.environ); e.pop("NFS_RB_SEG", None); e.pop("NFS_RB_NOSEG", None); e.update(env)
+        subprocess.run([sys.executable, "-c", _RB_SEG_SCRIPT % root, f], check=True, env=e, timeout=300)
+        o = np.load(f)
+        if ref is None:                                               # the same inputs in every child: one reference
+            d, g = torch.tensor(o["d"]).double(), torch.tensor(o["g"]).double()
+            ref = [VR.ray(d[v], torch.zeros_like(d[v]), 0.8, g[v]) for v in range(2)]
+        worst = max(VR.err_ratio((torch.tensor(o["g_d"][v]).double() - ref[v]["grad"]).abs(), ref[v]["e_grad"])
+                    for v in range(2))
+        print("render_bwd %s: g_d max err/bound %.3g" % (tag, worst))
+        assert worst <= 1.0, (tag, worst)
+        assert float(o["gmax"][0]) == float(np.abs(o["g_d"]).max()), tag
+        g_ds[tag] = o["g_d"]
+    # were the switches read?  Each form sums a ray's 64 samples in another order, so over 8320 values two forms differ in
+    # some last bit; equal bits mean that a child ignored its switch and ran another form, not that a result is wrong
+    tags = sorted(g_ds)
+    for i, a in enumerate(tags):
+        for b in tags[i + 1:]:
+            assert not np.array_equal(g_ds[a], g_ds[b]), "%s and %s gave the same bits: NFS_RB_SEG / NFS_RB_NOSEG not read?" % (a, b)
+
+
 def test_maxnorm_ties_split_like_tf(ops):
     x = torch.tensor([[1.0, 3.0, 3.0, 2.0]]).requires_grad_()
     y = x / x.amax()
