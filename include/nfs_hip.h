@@ -265,6 +265,41 @@ int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, fl
 int nfs_stream_bwd_adam(const float* g_vel, float* s, float* m, float* v, int D, int H, int W,
                         float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream);
 
+/* ---- gradient of a potential (transform.py:508-515) and stylising through it (grid variables 'p', 'sp') ----------------
+ * D_A is the forward difference along array axis A, the last slice replicated, zero along an axis of length 1.
+ * nfs_grad_fwd: out [D,H,W,3] = (D_W p, D_H p, D_D p) of p [D,H,W]: the reference's (dx, dy, dz) channel order.  3-D only.
+ * nfs_grad_bwd: g_p [D,H,W] = the transpose applied to g_out [D,H,W,3]: a gather (no atomics, deterministic).
+ * Potential velocity of phi [D,H,W]: vel0 = D_D phi, vel1 = D_H phi, vel2 = D_W phi -- nfs_grad_fwd with its channels
+ *   reversed, so that component k moves along array axis k as advect wants.  No scale factor: one forward difference of
+ *   phi is a normalised advect velocity.  The flow is irrotational: D_A vel_B = D_B vel_A.
+ * Transpose: g_phi = D_D^T g0 + D_H^T g1 + D_W^T g2, summed in this order (D, then H, then W) in nfs_grad_bwd and in the
+ *   two updates below alike: the same bits.
+ * Helmholtz variable a [D,H,W,4] = (psi0, psi1, psi2, phi), one 16-byte vector per voxel:
+ *   vel_k = fl(stream velocity of psi_k + potential velocity of phi_k), each summand formed as in its own function, then
+ *   added once; its transpose: channels 0-2 nfs_stream_bwd_adam's three lines, channel 3 the potential transpose.
+ * nfs_advect_potential_fwd / _bwd, nfs_advect_helmholtz_fwd / _bwd: nfs_advect_stream_fwd / _bwd with the velocity formed
+ *   from phi / a instead (phi: its own value and one neighbour per axis; a: four 16-byte vectors, so a must be 16-byte
+ *   aligned, else NFS_EINVAL): bit-identical to
+ *   nfs_advect_fwd / _live / nfs_advect_bwd (g_vel only) on the stored velocity; the same shapes (else NFS_EINVAL: compose),
+ *   live mask and alias rules.
+ * nfs_potential_bwd_adam: g_phi gathered and consumed on the spot by the TF ApplyAdam update (nfs_adam_tf_step's
+ *   expression) of phi, m, v [D,H,W] in place; g_phi is never stored.  nfs_helmholtz_bwd_adam: the same on a, m, v
+ *   [D,H,W,4], all three 16-byte aligned.  Any D,H,W >= 1; g_vel [D,H,W,3] (advect's channel order) must not alias the variable, m or v. */
+int nfs_grad_fwd(const float* p, float* out, int D, int H, int W, nfs_stream_t stream);
+int nfs_grad_bwd(const float* g_out, float* g_p, int D, int H, int W, nfs_stream_t stream);
+int nfs_advect_potential_fwd(const float* d, const float* phi, float* out, unsigned long long* live,
+                             int D, int H, int W, nfs_stream_t stream);
+int nfs_advect_potential_bwd(const float* d, const float* phi, const float* g_out, float* g_vel,
+                             int D, int H, int W, nfs_stream_t stream);
+int nfs_advect_helmholtz_fwd(const float* d, const float* a, float* out, unsigned long long* live,
+                             int D, int H, int W, nfs_stream_t stream);
+int nfs_advect_helmholtz_bwd(const float* d, const float* a, const float* g_out, float* g_vel,
+                             int D, int H, int W, nfs_stream_t stream);
+int nfs_potential_bwd_adam(const float* g_vel, float* phi, float* m, float* v, int D, int H, int W,
+                           float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream);
+int nfs_helmholtz_bwd_adam(const float* g_vel, float* a, float* m, float* v, int D, int H, int W,
+                           float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream);
+
 /* ---- Laplacian-pyramid gradient normalisation (util.py:57-110) -------------------------------------
  * nfs_lap_down: out [ceil(D/2),ceil(H/2),ceil(W/2),C] = conv(x [D,H,W,C], k, stride 2, 'SAME') (tf.nn.conv3d / conv2d of
  *   lap_split, 60-66); k = k5x5x5 [5][5][5] (nd = 3) or k5x5 [5][5] (nd = 2, D = 1), the same for every channel.

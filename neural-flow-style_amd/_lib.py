@@ -90,6 +90,14 @@ SIGNATURES = {
     "nfs_advect_stream_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "nfs_advect_stream_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "nfs_stream_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
+    "nfs_grad_fwd": [_P, _P, _I, _I, _I, _P],
+    "nfs_grad_bwd": [_P, _P, _I, _I, _I, _P],
+    "nfs_advect_potential_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_advect_potential_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_advect_helmholtz_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_advect_helmholtz_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "nfs_potential_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
+    "nfs_helmholtz_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
     "nfs_lap_down": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "nfs_lap_up": [_P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P],
     "nfs_lap_up_rms_parts": [_I, _I, _I, _I, _I],
@@ -187,7 +195,7 @@ _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 155          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 156          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

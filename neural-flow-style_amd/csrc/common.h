@@ -181,6 +181,9 @@ __device__ __forceinline__ float lin_coord(int i, int n) {
   return -1.f + step * (float)i;
 }
 
+// float4 accesses need it (a contiguous tensor view may start anywhere in its storage)
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // forward difference with the last slice replicated (transform.py:517-555): output i is s[l + 1] - s[l] at l = fd_lo(i, n)
 __device__ __forceinline__ int fd_lo(int i, int n) { return i < n - 1 ? i : (n >= 2 ? n - 2 : 0); }
 

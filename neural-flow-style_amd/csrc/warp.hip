@@ -275,15 +275,50 @@ __device__ __forceinline__ F3u stream_velocity(const float* __restrict__ s, int 
   return F3u{dw1 - dh0, dd0 - dw2, dh2 - dd1};
 }
 
+// Potential velocity of voxel (z, h, w): forward differences of a potential phi [D,H,W] (grad_fwd_kernel, warp2d.hip, its
+// channels reversed), vel_k along array axis k:
+//   vel0 = D_D phi,  vel1 = D_H phi,  vel2 = D_W phi
+// -- the voxel's own phi and one neighbour per axis: the upper one, or the lower one on the last slice of the axis.
+__device__ __forceinline__ F3u potential_velocity(const float* __restrict__ phi, int z, int h, int w, int D, int H, int W) {
+  const size_t own = (size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w;
+  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
+  const size_t sy = (size_t)W, sz = (size_t)H * W;
+  const float p = phi[own];
+  const float qx = phi[fx ? own + 1 : own - 1], qy = phi[fy ? own + sy : own - sy], qz = phi[fz ? own + sz : own - sz];
+  return F3u{fz ? qz - p : p - qz, fy ? qy - p : p - qy, fx ? qx - p : p - qx};
+}
+
+// Helmholtz velocity of voxel (z, h, w): a [D,H,W,4] = (psi0, psi1, psi2, phi), one 16-byte vector per voxel;
+//   vel_k = fl(stream_velocity(psi)_k + potential_velocity(phi)_k)
+// -- each summand formed exactly as in its own function, then added once (differences and sums only: nothing to contract).
+// The voxel's own vector and one neighbour's per axis, four 16-byte vectors (of which the compiler loads only the components
+// used), hold every difference both parts need.  a is 16-byte aligned (the entry points check).
+__device__ __forceinline__ F3u helmholtz_velocity(const float* __restrict__ a, int z, int h, int w, int D, int H, int W) {
+  const size_t own = (size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w;
+  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
+  const size_t sy = (size_t)W, sz = (size_t)H * W;
+  const float4* a4 = reinterpret_cast<const float4*>(a);
+  const float4 p = a4[own], qx = a4[fx ? own + 1 : own - 1], qy = a4[fy ? own + sy : own - sy],
+               qz = a4[fz ? own + sz : own - sz];
+  const float dw1 = fx ? qx.y - p.y : p.y - qx.y, dw2 = fx ? qx.z - p.z : p.z - qx.z, dw3 = fx ? qx.w - p.w : p.w - qx.w;
+  const float dh0 = fy ? qy.x - p.x : p.x - qy.x, dh2 = fy ? qy.z - p.z : p.z - qy.z, dh3 = fy ? qy.w - p.w : p.w - qy.w;
+  const float dd0 = fz ? qz.x - p.x : p.x - qz.x, dd1 = fz ? qz.y - p.y : p.y - qz.y, dd3 = fz ? qz.w - p.w : p.w - qz.w;
+  return F3u{(dw1 - dh0) + dd3, (dd0 - dw2) + dh3, (dh2 - dd1) + dw3};
+}
+
+// where advect1_kernel's velocity comes from: the stored field, or one of the three variables it is a function of
+enum { SRC_VEL = 0, SRC_STREAM = 1, SRC_POTENTIAL = 2, SRC_HELMHOLTZ = 3 };
+
 // MODE 0: forward; 1: velocity gradient -> out; 2: velocity gradient consumed on the spot by the TF-Adam update of
 // the velocity itself (vel, m, v updated in place: every thread reads and writes only its own 4 voxels of them;
 // the 96 MB gradient never goes to HBM)
 // Slab form (zoff, Dfull): vel / g_out / out / the moments hold only the D planes [zoff, zoff + D) of a volume of Dfull
 // planes, d is the WHOLE density (the back-traced points leave the slab); zoff = 0, Dfull = D is the whole volume.
 // EVER (MODE 2 + LIVE, volumes below 2^31 / 12 voxels): ad.ever is set and the streamed accesses are predicated per lane
-// STREAM (MODE 0 / 1, whole volumes): vel is a stream function and the velocity is stream_velocity() of it, formed in
-// registers and never stored; everything after the fetch is the same code
-template <int MODE, bool LIVE = false, bool EVER = false, bool STREAM = false>   // LIVE: ad.live is set (a compile-time switch: the mask code out of the plain kernels)
+// SRC (other than SRC_VEL: MODE 0 / 1, whole volumes): vel is a stream function [D,H,W,3], a potential [D,H,W] or a
+// Helmholtz variable [D,H,W,4] and the velocity is stream_velocity() / potential_velocity() / helmholtz_velocity() of it,
+// formed in registers and never stored; everything after the fetch is the same code
+template <int MODE, bool LIVE = false, bool EVER = false, int SRC = SRC_VEL>   // LIVE: ad.live is set (a compile-time switch: the mask code out of the plain kernels)
 __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ d, const float* vel,
                                                       const float* __restrict__ g_out, float* out,
                                                       int D, int H, int W, AdamFused ad, int zoff, int Dfull) {
@@ -344,16 +379,18 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
   F3u vv[4], mm[4], uu[4];
   float gg[4];
   bool ok[4];
-  [[maybe_unused]] int ws, hs, zs;   // STREAM: the voxel positions, walked here as well (walk64 keeps them inside the volume)
-  if constexpr (STREAM) lane_start(first, n, H, W, ws, hs, zs);
+  [[maybe_unused]] int ws, hs, zs;   // SRC: the voxel positions, walked here as well (walk64 keeps them inside the volume)
+  if constexpr (SRC != SRC_VEL) lane_start(first, n, H, W, ws, hs, zs);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int idx = first + 64 * j;
     ok[j] = idx < n;
     const int ic = ok[j] ? idx : n - 1;
-    if constexpr (STREAM) {
-      static_assert(!STREAM || MODE != 2, "the stream-function update is nfs_stream_bwd_adam");
-      vv[j] = stream_velocity(vel, zs, hs, ws, D, H, W);
+    if constexpr (SRC != SRC_VEL) {
+      static_assert(SRC == SRC_VEL || MODE != 2, "the updates are nfs_stream_bwd_adam / nfs_potential_bwd_adam / nfs_helmholtz_bwd_adam");
+      if constexpr (SRC == SRC_STREAM) vv[j] = stream_velocity(vel, zs, hs, ws, D, H, W);
+      else if constexpr (SRC == SRC_POTENTIAL) vv[j] = potential_velocity(vel, zs, hs, ws, D, H, W);
+      else vv[j] = helmholtz_velocity(vel, zs, hs, ws, D, H, W);
       if (BWD) gg[j] = g_out[ic];
       walk64(ws, hs, zs, W, H, D - 1);
       continue;
@@ -1372,9 +1409,15 @@ static bool advect1_takes(int D, int H, int W, int nz) {
 // mode: advect1_kernel's MODE; LIVE follows ad.live, EVER ad.ever (and NFS_EVER_LANES); the planes [z0, z0 + nz) of the
 // volume (vel / g_out / out / the moments hold those only; z0 = 0, nz = D: the whole-volume forms).  The callers have
 // checked their pointers for null.
-// psi: vel is a stream function (STREAM; mode 0 / 1 on whole volumes).
+// src: what vel is (advect1_kernel's SRC; other than SRC_VEL: mode 0 / 1 on whole volumes).
+template <int SRC>
+static auto advect1_from(int mode, bool live) {
+  return mode == 1 ? advect1_kernel<1, false, false, SRC>
+                   : live ? advect1_kernel<0, true, false, SRC> : advect1_kernel<0, false, false, SRC>;
+}
+
 static int advect1_launch(const char* who, int mode, const float* d, const float* vel, const float* g_out, float* out,
-                          int D, int H, int W, int z0, int nz, const AdamFused& ad, nfs_stream_t stream, bool psi = false) {
+                          int D, int H, int W, int z0, int nz, const AdamFused& ad, nfs_stream_t stream, int src = SRC_VEL) {
   NFS_REQUIRE(!ad.adv_next || (ad.adv_next != d && ad.adv_next != g_out), "%s: adv_next must not alias d or g_out", who);
   if (int e = check_dims(1, D, H, W, 1)) return e;
   NFS_REQUIRE(z0 >= 0 && nz >= 1 && z0 + nz <= D, "%s: slab outside the volume", who);
@@ -1382,10 +1425,11 @@ static int advect1_launch(const char* who, int mode, const float* d, const float
               "%s: needs D, H, W >= 2, D*H*W < 2^30 and a multiple of 4 voxels (nz*H*W for a slab)", who);
   const int64_t n = (int64_t)nz * H * W;
   auto kernel = ad.live ? advect1_kernel<0, true> : advect1_kernel<0>;
-  if (psi) {
-    NFS_REQUIRE(mode != 2 && z0 == 0 && nz == D, "%s: a stream function takes the forward and the gradient of a whole volume", who);
-    kernel = mode == 1 ? advect1_kernel<1, false, false, true>
-                       : ad.live ? advect1_kernel<0, true, false, true> : advect1_kernel<0, false, false, true>;
+  if (src != SRC_VEL) {
+    NFS_REQUIRE(mode != 2 && z0 == 0 && nz == D,
+                "%s: a stream function or potential takes the forward and the gradient of a whole volume", who);
+    kernel = src == SRC_STREAM ? advect1_from<SRC_STREAM>(mode, ad.live)
+             : src == SRC_POTENTIAL ? advect1_from<SRC_POTENTIAL>(mode, ad.live) : advect1_from<SRC_HELMHOLTZ>(mode, ad.live);
   } else if (mode == 1) {
     kernel = advect1_kernel<1>;
   } else if (mode == 2 && !ad.live) {
@@ -1558,7 +1602,7 @@ int nfs_advect_stream_fwd(const float* d, const float* s, float* out, unsigned l
   NFS_REQUIRE(out != d && out != s, "nfs_advect_stream_fwd: out must not alias d or s");
   AdamFused ad{};
   ad.live = live;
-  return advect1_launch("nfs_advect_stream_fwd", 0, d, s, nullptr, out, D, H, W, 0, D, ad, stream, true);
+  return advect1_launch("nfs_advect_stream_fwd", 0, d, s, nullptr, out, D, H, W, 0, D, ad, stream, SRC_STREAM);
 }
 
 // ... and its velocity gradient g_vel [D,H,W,3] (advect's channel order), the velocity recomputed from s
@@ -1566,7 +1610,48 @@ int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, fl
                           nfs_stream_t stream) {
   NFS_REQUIRE(d && s && g_out && g_vel, "nfs_advect_stream_bwd: null pointer");
   NFS_REQUIRE(g_vel != d && g_vel != s && g_vel != g_out, "nfs_advect_stream_bwd: g_vel must not alias d, s or g_out");
-  return advect1_launch("nfs_advect_stream_bwd", 1, d, s, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, true);
+  return advect1_launch("nfs_advect_stream_bwd", 1, d, s, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, SRC_STREAM);
+}
+
+// the same pair along the potential velocity of phi [D,H,W] (potential_velocity()) and along the Helmholtz velocity of
+// a [D,H,W,4] (helmholtz_velocity()): bit-identical to nfs_grad_fwd (reversed; for a: + nfs_curl_fwd reversed, added once)
+// followed by nfs_advect_fwd / _live / nfs_advect_bwd (g_vel only)
+static int advect_from_fwd(const char* who, int src, const float* d, const float* var, float* out, unsigned long long* live,
+                           int D, int H, int W, nfs_stream_t stream) {
+  NFS_REQUIRE(d && var && out, "%s: null pointer", who);
+  NFS_REQUIRE(out != d && out != var, "%s: out must not alias d or the variable", who);
+  NFS_REQUIRE(src != SRC_HELMHOLTZ || aligned16(var), "%s: the Helmholtz variable must be 16-byte aligned", who);
+  AdamFused ad{};
+  ad.live = live;
+  return advect1_launch(who, 0, d, var, nullptr, out, D, H, W, 0, D, ad, stream, src);
+}
+
+static int advect_from_bwd(const char* who, int src, const float* d, const float* var, const float* g_out, float* g_vel,
+                           int D, int H, int W, nfs_stream_t stream) {
+  NFS_REQUIRE(d && var && g_out && g_vel, "%s: null pointer", who);
+  NFS_REQUIRE(g_vel != d && g_vel != var && g_vel != g_out, "%s: g_vel must not alias d, the variable or g_out", who);
+  NFS_REQUIRE(src != SRC_HELMHOLTZ || aligned16(var), "%s: the Helmholtz variable must be 16-byte aligned", who);
+  return advect1_launch(who, 1, d, var, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, src);
+}
+
+int nfs_advect_potential_fwd(const float* d, const float* phi, float* out, unsigned long long* live, int D, int H, int W,
+                             nfs_stream_t stream) {
+  return advect_from_fwd("nfs_advect_potential_fwd", SRC_POTENTIAL, d, phi, out, live, D, H, W, stream);
+}
+
+int nfs_advect_potential_bwd(const float* d, const float* phi, const float* g_out, float* g_vel, int D, int H, int W,
+                             nfs_stream_t stream) {
+  return advect_from_bwd("nfs_advect_potential_bwd", SRC_POTENTIAL, d, phi, g_out, g_vel, D, H, W, stream);
+}
+
+int nfs_advect_helmholtz_fwd(const float* d, const float* a, float* out, unsigned long long* live, int D, int H, int W,
+                             nfs_stream_t stream) {
+  return advect_from_fwd("nfs_advect_helmholtz_fwd", SRC_HELMHOLTZ, d, a, out, live, D, H, W, stream);
+}
+
+int nfs_advect_helmholtz_bwd(const float* d, const float* a, const float* g_out, float* g_vel, int D, int H, int W,
+                             nfs_stream_t stream) {
+  return advect_from_bwd("nfs_advect_helmholtz_bwd", SRC_HELMHOLTZ, d, a, g_out, g_vel, D, H, W, stream);
 }
 
 // ---- adjoint of nfs_advect_maccormack_keep (transform.py:570-582, 590-607; the kernels above) ----------------------------

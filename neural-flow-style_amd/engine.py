@@ -650,16 +650,17 @@ class TFAdamState(object):
         lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
         ops.adam_tf_step(x, self.m, self.v, g, float(lr_t), float(self.b1), float(self.b2), float(self.eps))
 
-    def step_through_stream(self, s, g_vel, lr):
-        """the same update for a stream function ``s`` given the gradient ``g_vel`` of its stream velocity
-        (``ops.stream_velocity``): g_s = curl^T(reverse(g_vel)) is gathered and consumed inside one kernel"""
-        if self.m is None or self.m.shape != s.shape:
-            self.m = torch.zeros_like(s)
-            self.v = torch.zeros_like(s)
+    def step_through_source(self, kind, x, g_vel, lr):
+        """the same update for a variable ``x`` the velocity is a function of -- ``kind`` 's': a stream function [D,H,W,3],
+        'p': a potential [D,H,W], 'sp': the Helmholtz pair [D,H,W,4] -- given the gradient ``g_vel`` of that velocity
+        (``ops.source_velocity``): g_x = ``ops.source_velocity_bwd(kind, g_vel)`` is gathered and consumed inside one kernel"""
+        if self.m is None or self.m.shape != x.shape:
+            self.m = torch.zeros_like(x)
+            self.v = torch.zeros_like(x)
         self.b1p = np.float32(self.b1p * self.b1)
         self.b2p = np.float32(self.b2p * self.b2)
         lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
-        ops.stream_bwd_adam(g_vel, s, self.m, self.v, float(lr_t), float(self.b1), float(self.b2), float(self.eps))
+        ops.source_bwd_adam(kind, g_vel, x, self.m, self.v, float(lr_t), float(self.b1), float(self.b2), float(self.eps))
 
     def step_through_advect(self, vel, d0, g_adv, lr, adv_next=None, live_next=None, live_current=False):
         """the same update for the velocity variable of ``advect(d0, vel)`` given dL/d(advected density): the
@@ -779,6 +780,9 @@ def make_optimizer(kind="adam"):
     raise ValueError("optimizer %r: 'adam' or 'lbfgs'" % (kind,))
 
 
+SOURCED = ("s", "p", "sp")      # the grid variables a velocity is a function of (ops.source_velocity)
+
+
 class GridStylizer(object):
     """TNST-style grid path assembled from the reference's operators:
         d^ = advect(d0, vel)  ->  smooth+max  ->  RenderStyleLoss
@@ -798,13 +802,18 @@ class GridStylizer(object):
     on the summed density gradient and, the adjoint being bit-reproducible, arrives at the identical variable.  With
     ``target='d'`` there is no advect: ``adv_order`` is accepted and has no effect.
     ``target='s'``: order 1 advects along the stream velocity without storing it (``ops.advect_stream_fwd`` / ``_bwd``) and
-    the Adam step gathers curl^T inside the update (``TFAdamState.step_through_stream``); the next forward sample and its
+    the Adam step gathers curl^T inside the update (``TFAdamState.step_through_source``); the next forward sample and its
     live mask are written by a launch of their own at the end of ``step()`` and are then handled exactly as the velocity
     variable's (dead-region skipping, hipGraph replay starting from the stored sample).  Order 2 materialises the
-    velocity.  Over ranks: the all-reduce mode."""
+    velocity.  Over ranks: the all-reduce mode.
+    ``target='p'``: a potential ``phi`` [D,H,W] whose forward differences are the velocity (``ops.potential_velocity``:
+    irrotational by construction -- local sources and sinks); ``target='sp'``: the Helmholtz pair ``a`` [D,H,W,4] =
+    (psi, phi) with v = stream_velocity(psi) + potential_velocity(phi) (``ops.helmholtz_velocity``).  Both run exactly as
+    's' does, through ``ops.advect_source_fwd`` / ``_bwd`` and ``ops.source_bwd_adam`` of their kind."""
 
     def __init__(self, loss, d0, k=3, target="v", lr=0.1, process_group=None, graph=None, optimizer="adam", adv_order=1):
-        assert target in ("v", "d", "s"), "target is 'v' (velocity), 's' (stream function) or 'd' (density)"
+        assert target in ("v", "d") + SOURCED, \
+            "target is 'v' (velocity), 's' (stream function), 'p' (potential), 'sp' (both) or 'd' (density)"
         self.loss = loss
         self.d0 = d0.contiguous()
         self.k = float(k)
@@ -823,7 +832,7 @@ class GridStylizer(object):
         # buffers: a captured forward writes them at every replay, the adjoint outside the capture reads what it wrote)
         self._mc_fwd = None
         self._mc_keep = None
-        self._mc_vel = None                          # (target 's': the stream velocity that forward was advected along)
+        self._mc_vel = None                          # (targets 's', 'p', 'sp': the velocity that forward was advected along)
         # hipGraph replay of the forward + adjoint (about 130 launches a step; the host needs 1.25 ms to issue
         # them one by one, which is the whole step at one view per rank)
         # (measured: 200^3 x 8 views 3.98 -> 3.90 ms, 200^3 x 1 view 1.35 -> 1.41 ms, 100^3 x 1 view 1.20 -> 1.06 ms:
@@ -852,8 +861,10 @@ class GridStylizer(object):
         self._live_buf = None
         self._live_mark = None
         D, H, W = d0.shape
-        if target in ("v", "s"):
+        if target == "v":
             self.var = torch.zeros(D, H, W, 3, dtype=torch.float32, device=d0.device)
+        elif target in SOURCED:
+            self.var = torch.zeros(ops.source_shape(target, D, H, W), dtype=torch.float32, device=d0.device)
         else:
             self.var = d0.clone()
         # field gradient and the summed loss share one buffer: the multi-rank exchange is ONE all-reduce
@@ -1001,9 +1012,9 @@ class GridStylizer(object):
 
     # ---- the forward advect of iteration i + 1 rides in the Adam kernel of iteration i ---------------------------------------
     def _adv_target(self):
-        """the buffer the fused Adam kernel ('v') or the launch after the update ('s') writes the next forward sample into
+        """the buffer the fused Adam kernel ('v') or the launch after the update ('s', 'p', 'sp') writes the next forward sample into
         (None: fusion off / not applicable)"""
-        if not (self.fuse_advect and (self._fused_step_ok() or self._stream_stored())):
+        if not (self.fuse_advect and (self._fused_step_ok() or self._source_stored())):
             return None
         sl = self.slab
         shape = tuple(self.d0.shape) if sl is None else (sl.hi - sl.lo,) + tuple(self.d0.shape[1:])
@@ -1019,15 +1030,17 @@ class GridStylizer(object):
         D, H, W = self.d0.shape
         return self.target == "v" and self.fuse_adam and min(D, H, W) >= 2 and (D * H * W) % 4 == 0
 
-    def _stream_stored(self):
-        """stream-function variable, order 1, on the shapes the fused advect takes: the forward sample lives in the fixed
-        buffer as the velocity variable's does (written by ``_advect_now``, which ``step()`` calls after the update)"""
-        return self.target == "s" and self.adv_order == 1 and ops.advect_stream_takes(*self.d0.shape)
+    def _source_stored(self):
+        """stream-function, potential or Helmholtz variable, order 1, on the shapes the fused advect takes: the forward sample
+        lives in the fixed buffer as the velocity variable's does (written by ``_advect_now``, which ``step()`` calls after
+        the update)"""
+        return self.target in SOURCED and self.adv_order == 1 and ops.advect_source_takes(*self.d0.shape)
 
     def velocity(self):
-        """the velocity the density is advected along: the variable itself ('v') or its stream velocity ('s')"""
-        assert self.target in ("v", "s"), "the density variable has no velocity"
-        return self.var if self.target == "v" else ops.stream_velocity(self.var)
+        """the velocity the density is advected along: the variable itself ('v'), its stream velocity ('s'), its potential
+        velocity ('p') or the sum of both parts ('sp')"""
+        assert self.target == "v" or self.target in SOURCED, "the density variable has no velocity"
+        return self.var if self.target == "v" else ops.source_velocity(self.target, self.var)
 
     def _adv_mark(self, live=False):
         self._adv_src = (self.var, self.var._version, self.d0, self.d0._version)
@@ -1077,9 +1090,9 @@ class GridStylizer(object):
         live = self._live_target()
         if buf is not None and self._adv_valid() and (live is None or self._live_valid()):
             return buf
-        if self.target == "s":
-            out = ops.advect_stream_fwd(self.d0.unsqueeze(-1), self.var, out=None if buf is None else buf.unsqueeze(-1),
-                                        live=live).squeeze(-1)
+        if self.target in SOURCED:
+            out = ops.advect_source_fwd(self.target, self.d0.unsqueeze(-1), self.var,
+                                        out=None if buf is None else buf.unsqueeze(-1), live=live).squeeze(-1)
         elif sl is None:
             out = ops.advect_fwd(self.d0.unsqueeze(-1), self.var, out=None if buf is None else buf.unsqueeze(-1),
                                  live=live).squeeze(-1)
@@ -1096,17 +1109,17 @@ class GridStylizer(object):
             self._mc_fwd = torch.empty_like(d4)
             self._mc_keep = ops.maccormack_mask(d4.shape, d4)
         vel = self.var
-        if self.target == "s":
-            if self._mc_vel is None or self._mc_vel.shape != self.var.shape:
-                self._mc_vel = torch.empty_like(self.var)
-            vel = self._mc_vel.copy_(ops.curl_fwd(self.var).flip(-1))        # (ops.stream_velocity into the fixed buffer)
+        if self.target in SOURCED:
+            if self._mc_vel is None or self._mc_vel.shape[:3] != self.var.shape[:3]:
+                self._mc_vel = torch.empty(tuple(self.d0.shape) + (3,), dtype=torch.float32, device=self.d0.device)
+            vel = self._mc_vel.copy_(ops.source_velocity(self.target, self.var))
         return ops.advect_maccormack(d4, vel, keep=self._mc_keep, d_fwd=self._mc_fwd).squeeze(-1)
 
     def forward_field(self):
         if self.slab is not None:
             return self._forward_field_slab()
         self._apply_binding()
-        if self.target in ("v", "s"):
+        if self.target != "d":
             self.d_adv = self._advect_now()
         else:
             self.d_adv = self.var
@@ -1139,8 +1152,8 @@ class GridStylizer(object):
         """adjoint of smooth+max and advect: dL/d variable from dL/d d_s (deterministic kernels: every
         rank computes the identical result from the all-reduced g_ds)"""
         g_adv = ops.smooth3d_relu_bwd(self.d_s, g_ds, self.k)
-        if self.target == "s":
-            return ops.stream_velocity_bwd(self._stream_velocity_gradient(g_adv))
+        if self.target in SOURCED:
+            return ops.source_velocity_bwd(self.target, self._source_velocity_gradient(g_adv))
         if self.target == "v" and self.adv_order == 2:
             _, g_var = ops.advect_maccormack_bwd(self.d0.unsqueeze(-1), self.var, self._mc_fwd, self._mc_keep,
                                                  g_adv.unsqueeze(-1), need_d=False, need_vel=True)
@@ -1151,17 +1164,17 @@ class GridStylizer(object):
             return g_var
         return g_adv
 
-    def _stream_velocity_gradient(self, g_adv):
-        """target 's': dL/d(stream velocity) from dL/d(advected density), along the forward's own velocity"""
+    def _source_velocity_gradient(self, g_adv):
+        """targets 's', 'p', 'sp': dL/d(velocity) from dL/d(advected density), along the forward's own velocity"""
         d4 = self.d0.unsqueeze(-1)
         if self.adv_order == 2:
             return ops.advect_maccormack_bwd(d4, self._mc_vel, self._mc_fwd, self._mc_keep, g_adv.unsqueeze(-1),
                                              need_d=False, need_vel=True)[1]
-        return ops.advect_stream_bwd(d4, self.var, g_adv.unsqueeze(-1))
+        return ops.advect_source_bwd(self.target, d4, self.var, g_adv.unsqueeze(-1))
 
     def gradient(self, rot_local):
         """one forward+backward over the local views; returns (loss_per_view, grad wrt variable)"""
-        losses, g_ds = self.field_gradient(rot_local, for_variable=self.target in ("v", "s"))
+        losses, g_ds = self.field_gradient(rot_local, for_variable=self.target != "d")
         return losses, self.variable_gradient(g_ds)
 
     def _capture_key(self, rot_local):
@@ -1181,13 +1194,13 @@ class GridStylizer(object):
         (style / content targets, loss hyper-parameters, the addresses of d0 and the variable, the number of views):
         when any of that changes the graph is dropped and captured again.  The view matrices are copied into a
         static buffer."""
-        body = ((lambda r: self.field_gradient(r, total=True, for_variable=self.target in ("v", "s"))) if with_field
+        body = ((lambda r: self.field_gradient(r, total=True, for_variable=self.target != "d")) if with_field
                 else (lambda r: self._loss_gradient(self.d_s, r, total=True)))
 
         def to_slot(losses):              # (None: the loss chain has written the total into the slot itself)
             if losses is not None:
                 torch.sum(losses, dim=0, keepdim=True, out=self._loss_slot)     # one kernel: reduce straight into the slot
-        if with_field and self.target in ("v", "s") and self._adv_target() is not None:
+        if with_field and self.target != "d" and self._adv_target() is not None:
             # the captured forward starts from the advected density in its fixed buffer: bring it up to date eagerly when
             # the previous step's Adam kernel has not left it there (first step, a re-bound frame, a variable set by hand)
             self._apply_binding()
@@ -1258,11 +1271,11 @@ class GridStylizer(object):
         if self.use_graph:
             total, g_ds = self._field_gradient_graphed(rot_local)
         elif self.pg is None:
-            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target in ("v", "s"))
+            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target != "d")
             total = self._loss_slot if losses is None else None
             total_new = None if losses is None else losses.sum()             # (one kernel, a fresh tensor: no slot, no copy)
         else:
-            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target in ("v", "s"))
+            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target != "d")
             if losses is not None:
                 torch.sum(losses, dim=0, keepdim=True, out=self._loss_slot)  # (one kernel: reduce straight into the slot)
             total = self._loss_slot
@@ -1285,9 +1298,9 @@ class GridStylizer(object):
                                           live_next=live, live_current=live is not None and self._live_valid())
             if adv is not None:
                 self._adv_mark(live=live is not None)
-        elif self.target == "s" and self.fuse_adam:
+        elif self.target in SOURCED and self.fuse_adam:
             g_adv = ops.smooth3d_relu_bwd(self.d_s, g_ds, self.k)
-            self.adam.step_through_stream(self.var, self._stream_velocity_gradient(g_adv), self.lr)
+            self.adam.step_through_source(self.target, self.var, self._source_velocity_gradient(g_adv), self.lr)
             if self._adv_target() is not None:
                 self._advect_now()        # (the next forward sample and its mask, into the fixed buffers)
         else:

@@ -313,45 +313,161 @@ def stream_velocity_bwd(g_vel):
     return curl_bwd(g_vel.flip(-1).contiguous())
 
 
-def advect_stream_takes(D, H, W):
-    """the shapes ``nfs_advect_stream_fwd`` / ``_bwd`` take (the four-voxel advect kernel's, include/nfs_hip.h)"""
+def advect_source_takes(D, H, W):
+    """the shapes ``nfs_advect_stream_fwd`` / ``_bwd`` and their potential and Helmholtz twins take (the four-voxel advect
+    kernel's, include/nfs_hip.h)"""
     return min(D, H, W) >= 2 and (D * H * W) % 4 == 0 and D * H * W < (1 << 30)
+
+
+advect_stream_takes = advect_source_takes          # (the name the stream-function variable introduced it under)
 
 
 def advect_stream_fwd(d, s, out=None, live=None):
     """advect_fwd(d, stream_velocity(s)) for a scalar field d [D,H,W,1], the velocity never stored (one kernel; the same
     bits).  ``live`` as in ``advect_fwd``.  Shapes the fused kernel does not take run the composition."""
-    D, H, W, Cn = d.shape
-    assert Cn == 1 and tuple(s.shape) == (D, H, W, 3) and s.is_contiguous()
-    if not advect_stream_takes(D, H, W):
-        return advect_fwd(d, stream_velocity(s), out=out, live=live)
-    if out is None:
-        out = _empty(d.shape, d)
-    _lib.call("nfs_advect_stream_fwd", _ptr(d), _ptr(s), _ptr(out), _ptr(live), D, H, W, _stream())
-    _written(live)
-    return out
+    return advect_source_fwd("s", d, s, out=out, live=live)
 
 
 def advect_stream_bwd(d, s, g_out, g_vel=None):
     """velocity gradient [D,H,W,3] (advect's channel order) of ``advect_stream_fwd``, the velocity recomputed from s:
     the bits of advect_bwd(d, stream_velocity(s), g_out, need_d=False)"""
-    D, H, W, Cn = d.shape
-    assert Cn == 1 and tuple(s.shape) == (D, H, W, 3) and s.is_contiguous()
-    if not advect_stream_takes(D, H, W):
-        return advect_bwd(d, stream_velocity(s), g_out, need_d=False, g_vel=g_vel)[1]
-    if g_vel is None:
-        g_vel = _empty(s.shape, d)
-    _lib.call("nfs_advect_stream_bwd", _ptr(d), _ptr(s), _ptr(g_out), _ptr(g_vel), D, H, W, _stream())
-    return g_vel
+    return advect_source_bwd("s", d, s, g_out, g_vel=g_vel)
 
 
 def stream_bwd_adam(g_vel, s, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """g_s = stream_velocity_bwd(g_vel) consumed on the spot by the TF-Adam update of s (s, m, v [D,H,W,3] in place)"""
-    D, H, W, _ = s.shape
-    assert tuple(g_vel.shape) == tuple(s.shape) == tuple(m.shape) == tuple(v.shape) and s.shape[-1] == 3
-    _lib.call("nfs_stream_bwd_adam", _ptr(g_vel), _ptr(s), _ptr(m), _ptr(v), D, H, W, float(lr_t), float(beta1),
+    source_bwd_adam("s", g_vel, s, m, v, lr_t, beta1, beta2, eps)
+
+
+# ---- the gradient of a potential and stylising through it (include/nfs_hip.h: grid variables 'p', 'sp') ------------------
+
+def grad_fwd(p):
+    """p [D,H,W] -> [D,H,W,3] = (dx, dy, dz): forward differences, last slice replicated (transform.py:508-515)"""
+    D, H, W = p.shape
+    out = _empty((D, H, W, 3), p)
+    _lib.call("nfs_grad_fwd", _ptr(p), _ptr(out), D, H, W, _stream())
+    return out
+
+
+def grad_bwd(g_out):
+    """adjoint of ``grad_fwd``: g_out [D,H,W,3] -> [D,H,W] (a gather: deterministic)"""
+    D, H, W, _ = g_out.shape
+    g_p = _empty((D, H, W), g_out)
+    _lib.call("nfs_grad_bwd", _ptr(g_out), _ptr(g_p), D, H, W, _stream())
+    return g_p
+
+
+def potential_velocity(phi):
+    """potential velocity of phi [D,H,W]: its gradient with the channels reversed, so that component k moves along array
+    axis k as ``advect_fwd`` wants -- irrotational in forward differences"""
+    return grad_fwd(phi).flip(-1).contiguous()
+
+
+def potential_velocity_bwd(g_vel):
+    """adjoint of ``potential_velocity``: g_phi = grad^T(reverse(g_vel))"""
+    return grad_bwd(g_vel.flip(-1).contiguous())
+
+
+def helmholtz_velocity(a):
+    """velocity of a Helmholtz variable a [D,H,W,4] = (psi, phi): stream_velocity(psi) + potential_velocity(phi)"""
+    assert a.shape[-1] == 4
+    return stream_velocity(a[..., :3].contiguous()) + potential_velocity(a[..., 3].contiguous())
+
+
+def helmholtz_velocity_bwd(g_vel):
+    """adjoint of ``helmholtz_velocity``: [D,H,W,4] = (stream_velocity_bwd(g_vel), potential_velocity_bwd(g_vel))"""
+    return torch.cat([stream_velocity_bwd(g_vel), potential_velocity_bwd(g_vel).unsqueeze(-1)], dim=-1)
+
+
+# what stands for the velocity under each grid variable: (shape of the variable given (D, H, W), velocity, its adjoint,
+# the fused forward / adjoint / update entry points)
+_SOURCES = {
+    "s": (lambda D, H, W: (D, H, W, 3), stream_velocity, stream_velocity_bwd,
+          "nfs_advect_stream_fwd", "nfs_advect_stream_bwd", "nfs_stream_bwd_adam"),
+    "p": (lambda D, H, W: (D, H, W), potential_velocity, potential_velocity_bwd,
+          "nfs_advect_potential_fwd", "nfs_advect_potential_bwd", "nfs_potential_bwd_adam"),
+    "sp": (lambda D, H, W: (D, H, W, 4), helmholtz_velocity, helmholtz_velocity_bwd,
+           "nfs_advect_helmholtz_fwd", "nfs_advect_helmholtz_bwd", "nfs_helmholtz_bwd_adam"),
+}
+
+
+def source_shape(kind, D, H, W):
+    """shape of the variable of kind 's' (stream function), 'p' (potential) or 'sp' (Helmholtz pair) on a [D,H,W] grid"""
+    return _SOURCES[kind][0](D, H, W)
+
+
+def source_velocity(kind, x):
+    """the velocity the variable ``x`` of that kind stands for [D,H,W,3]"""
+    return _SOURCES[kind][1](x)
+
+
+def source_velocity_bwd(kind, g_vel):
+    """its adjoint: the gradient of the variable from the gradient of the velocity"""
+    return _SOURCES[kind][2](g_vel)
+
+
+def advect_source_fwd(kind, d, x, out=None, live=None):
+    """advect_fwd(d, source_velocity(kind, x)) for a scalar field d [D,H,W,1], the velocity never stored (one kernel; the
+    same bits).  ``live`` as in ``advect_fwd``.  Shapes the fused kernel does not take run the composition."""
+    D, H, W, Cn = d.shape
+    assert Cn == 1 and tuple(x.shape) == source_shape(kind, D, H, W) and x.is_contiguous()
+    if not advect_source_takes(D, H, W):
+        return advect_fwd(d, source_velocity(kind, x), out=out, live=live)
+    if out is None:
+        out = _empty(d.shape, d)
+    _lib.call(_SOURCES[kind][3], _ptr(d), _ptr(x), _ptr(out), _ptr(live), D, H, W, _stream())
+    _written(live)
+    return out
+
+
+def advect_source_bwd(kind, d, x, g_out, g_vel=None):
+    """velocity gradient [D,H,W,3] (advect's channel order) of ``advect_source_fwd``, the velocity recomputed from x: the
+    bits of advect_bwd(d, source_velocity(kind, x), g_out, need_d=False)"""
+    D, H, W, Cn = d.shape
+    assert Cn == 1 and tuple(x.shape) == source_shape(kind, D, H, W) and x.is_contiguous()
+    if not advect_source_takes(D, H, W):
+        return advect_bwd(d, source_velocity(kind, x), g_out, need_d=False, g_vel=g_vel)[1]
+    if g_vel is None:
+        g_vel = _empty((D, H, W, 3), d)
+    _lib.call(_SOURCES[kind][4], _ptr(d), _ptr(x), _ptr(g_out), _ptr(g_vel), D, H, W, _stream())
+    return g_vel
+
+
+def source_bwd_adam(kind, g_vel, x, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """g_x = source_velocity_bwd(kind, g_vel) consumed on the spot by the TF-Adam update of x (x, m, v in place)"""
+    D, H, W, _ = g_vel.shape
+    assert g_vel.shape[-1] == 3 and tuple(x.shape) == tuple(m.shape) == tuple(v.shape) == source_shape(kind, D, H, W)
+    _lib.call(_SOURCES[kind][5], _ptr(g_vel), _ptr(x), _ptr(m), _ptr(v), D, H, W, float(lr_t), float(beta1),
               float(beta2), float(eps), _stream())
-    _written(s, m, v)
+    _written(x, m, v)
+
+
+def advect_potential_fwd(d, phi, out=None, live=None):
+    """``advect_stream_fwd`` along the potential velocity of phi [D,H,W]"""
+    return advect_source_fwd("p", d, phi, out=out, live=live)
+
+
+def advect_potential_bwd(d, phi, g_out, g_vel=None):
+    return advect_source_bwd("p", d, phi, g_out, g_vel=g_vel)
+
+
+def advect_helmholtz_fwd(d, a, out=None, live=None):
+    """``advect_stream_fwd`` along the Helmholtz velocity of a [D,H,W,4]"""
+    return advect_source_fwd("sp", d, a, out=out, live=live)
+
+
+def advect_helmholtz_bwd(d, a, g_out, g_vel=None):
+    return advect_source_bwd("sp", d, a, g_out, g_vel=g_vel)
+
+
+def potential_bwd_adam(g_vel, phi, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """``stream_bwd_adam`` for a potential: phi, m, v [D,H,W] in place"""
+    source_bwd_adam("p", g_vel, phi, m, v, lr_t, beta1, beta2, eps)
+
+
+def helmholtz_bwd_adam(g_vel, a, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """``stream_bwd_adam`` for a Helmholtz variable: a, m, v [D,H,W,4] in place"""
+    source_bwd_adam("sp", g_vel, a, m, v, lr_t, beta1, beta2, eps)
 
 
 def lap_down(x, k):

@@ -9,7 +9,9 @@ particle loop is built:
   per key frame t (styler_3p.py:304-363), variable re-assigned from ``g_opt[t]`` (312), one TF-Adam state per
   ``opt_id = t // frames_per_opt`` (315-323):
         d^_t = advect(d_t, v^_t)            ('v': stylisation velocity [D,H,W,3];  'd': the density itself;
-                                             's': a stream function [D,H,W,3], v^_t = its stream velocity)
+                                             's': a stream function [D,H,W,3], v^_t = its stream velocity;
+                                             'p': a potential [D,H,W], v^_t = its forward differences;
+                                             'sp': both [D,H,W,4], v^_t = the sum of the two)
         -> 3x3x3 smooth + max(.,0) -> rotate (all views, ``views=sum``) -> render -> VGG-19 -> Gram style loss
         -> adjoint chain -> one Adam step;      upd_t = new - g_opt[t]   ('d': masked by the original density, 361-363)
   temporal alignment of the updates (380-386).  Per-particle attributes ride on the particles, so the reference filters
@@ -44,13 +46,17 @@ class Styler(StylerBase):
     simulation velocities [D,H,W,3] in ``advect`` units (normalised: one cell = 2/(n-1), component k along array
     axis k).  ``config.grid_variable`` = 'v' (default), 'd', or 's': a stream function whose
     stream velocity (``ops.stream_velocity``, divergence-free) advects the density; it starts from zero or
-    ``params['s_init'][t]``, and the result carries it as ``'s'`` / ``'opt'`` beside the stream velocities ``'v'``."""
+    ``params['s_init'][t]``, and the result carries it as ``'s'`` / ``'opt'`` beside the stream velocities ``'v'``.
+    'p': a potential [D,H,W] (``ops.potential_velocity``, irrotational; ``params['p_init'][t]``), 'sp': the Helmholtz pair
+    [D,H,W,4] = (stream function, potential) (``ops.helmholtz_velocity``; ``params['sp_init'][t]``): ``'opt'`` is the
+    variable, ``'v'`` the velocity it stands for, ``'s'`` its stream-function part ('s', 'sp') and ``'phi'`` its potential
+    ('p', 'sp'); ``'p'`` stays the reference's particle-position key (None on the grid path)."""
 
     def __init__(self, self_dict):
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (styler_3p module docstring)"
         self.target = getattr(self, "grid_variable", "") or "v"
-        assert self.target in ("v", "d", "s")
+        assert self.target in ("v", "d") + engine.SOURCED
         self.adv_order = int(getattr(self, "adv_order", 1) or 1)       # config.py adv_order: 1 = SL, 2 = MacCormack
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
@@ -188,7 +194,7 @@ class Styler(StylerBase):
             raise ValueError("params['v'] (simulation velocities) is needed to align the updates of a sequence")
         st.u = st.u or {}
         D, H, W_ = tuple(self.resolution)
-        st.C = 3 if self.target in ("v", "s") else 1
+        st.C = {"v": 3, "s": 3, "sp": 4}.get(self.target, 1)
         st.shape = (D, H, W_, st.C)
         if self.style_img is not None:
             self.loss.set_style_image(self._style_feature(self.style_img, [H, W_]))
@@ -200,7 +206,7 @@ class Styler(StylerBase):
         # the variable per key frame: stylisation velocity (zero, or params['v_init'][t]) / the density itself.
         # NOTE: at velocity == 0 every back-traced point sits exactly on a grid node, where the trilinear stencil has a
         # kink -- the first gradient is a one-sided derivative whose side depends on float rounding
-        st.v_init = params.get("s_init" if self.target == "s" else "v_init")
+        st.v_init = params.get(self.target + "_init" if self.target in engine.SOURCED else "v_init")
         st.g_opt = {t: self._initial(t) for t in st.mine}
         st.work = torch.zeros(st.shape, device=self.device)     # the variable (re-assigned per frame, 312)
         # (a rank beyond the number of optimiser groups owns no frame: it only takes part in the collectives)
@@ -237,7 +243,7 @@ class Styler(StylerBase):
                 if adam is None:
                     adam = st.opt_[slot] = engine.make_optimizer(getattr(self, "optimizer", "adam"))
                 st.work.copy_(st.g_opt[t])
-                st.gs.bind(st.d[t], st.work.view(D, H, W_, 3) if st.C == 3 else st.work.view(D, H, W_), adam)
+                st.gs.bind(st.d[t], st.work.view(D, H, W_, st.C) if st.C > 1 else st.work.view(D, H, W_), adam)
                 losses[j] = st.gs.step(self._rot())
                 dlt = torch.nan_to_num(st.gs.var.reshape(st.shape)) - st.g_opt[t]
                 if self.target == "d":
@@ -282,14 +288,17 @@ class Styler(StylerBase):
                 for i in range(1, self.interp):
                     if t + self.interp < st.F:
                         full[t + i] = full[t] * float(1 - w[i]) + full[t + self.interp] * float(w[i])
-        d_sty, r_sty, v_sty, u_sty = [], [], [], []        # (u_sty: the stream velocities of a stream-function run)
+        d_sty, r_sty, v_sty, u_sty = [], [], [], []        # (u_sty: the velocities of a run whose variable stands for one)
+        sourced = self.target in engine.SOURCED
         present = [t for t in range(st.F) if t in st.d]
         for t in present:
             var = full.get(t)
             if var is None:                                        # trailing frames past the last key frame
                 var = self._initial(t)
-            vel = ops.stream_velocity(var) if self.target == "s" else var
-            if self.target in ("v", "s"):
+            if self.target == "p":
+                var = var.reshape(D, H, W_)                        # (the potential in the shape of params['p_init'][t])
+            vel = ops.source_velocity(self.target, var) if sourced else var
+            if self.target != "d":
                 # (the order the loop optimised through)
                 advect = ops.advect_maccormack if self.adv_order == 2 else ops.advect_fwd
                 d_adv = advect(st.d[t].unsqueeze(-1), vel).squeeze(-1)
@@ -300,12 +309,14 @@ class Styler(StylerBase):
             d_sty.append(torch.abs(d_out).unsqueeze(-1).cpu().numpy())   # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
             v_sty.append(var.cpu().numpy())
-            if self.target == "s":
+            if sourced:
                 u_sty.append(vel.cpu().numpy())
         hist = [[float(x) for x in l_.cpu()] for l_ in st.hist]
         return {"l": [[x for l_ in hist for x in l_]], "l_frames": hist, "d_intm": [],
-                "d": np.array(d_sty), "r": np.array(r_sty), "v": v_sty if self.target == "v" else u_sty if self.target == "s" else None,
-                "s": v_sty if self.target == "s" else None, "opt": v_sty, "p": None, "c": None, "frames": present}
+                "d": np.array(d_sty), "r": np.array(r_sty), "v": v_sty if self.target == "v" else u_sty if sourced else None,
+                "s": v_sty if self.target == "s" else [a[..., :3] for a in v_sty] if self.target == "sp" else None,
+                "phi": v_sty if self.target == "p" else [a[..., 3] for a in v_sty] if self.target == "sp" else None,
+                "opt": v_sty, "p": None, "c": None, "frames": present}
 
     def run(self, params):
         self.prepare(params)

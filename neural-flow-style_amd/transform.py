@@ -297,6 +297,23 @@ def curl(s, is_2d=True):
     return torch.stack([_Curl.apply(s[b]) for b in range(s.shape[0])])
 
 
+class _Grad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p):
+        return ops.grad_fwd(p.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.grad_bwd(g.contiguous())
+
+
+def grad(p):
+    """gradient of a potential (transform.py:508-515): p [B,D,H,W] -> [B,D,H,W,3] = (dx, dy, dz), forward differences with
+    the last slice replicated.  Differentiable (the TNST parametrisation optimises p).  The reference joins its three
+    differences along the last axis of a field that has no channel axis; here they are the three channels."""
+    return torch.stack([_Grad.apply(p[b]) for b in range(p.shape[0])])
+
+
 class _Permute(torch.autograd.Function):
     """x[:, order] for a PERMUTATION ``order`` of axis 1.  The adjoint of a gather through a permutation is a plain scatter
     (every target written exactly once: ``index_copy_``, no accumulation) -- autograd's generic index backward (a sorted
