@@ -720,6 +720,22 @@ int nfs_adam_tf_step(float* x, float* m, float* v, const float* g, int64_t n,
 int nfs_fill(float* x, float value, int64_t n, nfs_stream_t stream);
 int nfs_axpy(float* y, const float* x, float a, int64_t n, nfs_stream_t stream); /* y += a*x */
 
+/* ---- 3-D resize (util.py:128-167: resize_tf / rescale_tf with is_3d = True) -------------------------------------------
+ * x [D,H,W,C] -> out [oD,oH,oW,C] (out must not alias x), forward only: nothing differentiates it.  The semantics are
+ * the TF-1 legacy kernels' of tf.compat.v1.image.resize (no half-pixel centres), applied as the reference applies them:
+ * over (H, W) of every depth slice (util.py:133-136), then over D (137-140).  Per axis n_in -> n_out, in float32:
+ *   s = float(n_in) / float(n_out), or float(n_in - 1) / float(n_out - 1) with align_corners and n_out > 1;
+ *   p = float(i) * s.
+ * method 1 (bilinear): lo = floor(p), hi = min(ceil(p), n_in - 1), t = p - lo;
+ *   top = tl + (tr - tl) * tw, bot = bl + (br - bl) * tw, r = top + (bot - top) * th   (one depth slice),
+ *   out = (r_lo + (r_hi - r_lo) * td) * scale.
+ * method 0 (nearest): index min(floor(p), n_in - 1), with align_corners min(roundf(p), n_in - 1); out = x[...] * scale.
+ * Every product, sum and difference above is rounded to float32 on its own (no fused multiply-add): the output equals a
+ * float32 restatement of these lines bit for bit.  `scale` carries the factor a resampled potential needs (the grid
+ * octaves of styler_grid: a forward difference of it is a velocity). */
+int nfs_resize3d(const float* x, float* out, int D, int H, int W, int C, int oD, int oH, int oW,
+                 int method, int align_corners, float scale, nfs_stream_t stream);
+
 /* ---- 2-D colour stylizer: the elementwise links of its chain (styler_2p.py:68-102, 259-262) -------------------
  * The reference's graph for one frame is c_ = clip(c, 0, 1) -> p2g(p, pc = c_, pd = r) -> clip(., 0, 1) -> loss net, and
  * per iteration g_opt += nan_to_num(c_new) - g_opt.  As TF ops (or torch autograd nodes) these are a dozen launches of a

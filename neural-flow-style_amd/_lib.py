@@ -168,6 +168,7 @@ SIGNATURES = {
     "nfs_hist_loss_wide_workspace_floats": [_I, _I, _I, _I],
     "nfs_hist_loss_wide": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "nfs_resize_bicubic_tf1": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "nfs_resize3d": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "nfs_style_mask_apply": [_P, _P, _P, _P, _I, _I, _I, _P],
     "nfs_style_mask_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "nfs_tv_loss": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
@@ -195,7 +196,7 @@ _RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64
             "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
 
 _lib = None
-ABI_VERSION = 156          # nfs_version() this table was written against (include/nfs_hip.h)
+ABI_VERSION = 157          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):

@@ -4,6 +4,7 @@
 //   A5  loss-net input                (styler_base.py:33-45, vgg.py:50-53)
 //   A6  2x2 average pool              (vgg.py:93-104)
 //   A12 total variation               (styler_base.py:211-213)
+//   3-D resize                        (util.py:128-167)
 #include "common.h"
 
 namespace nfs {
@@ -417,6 +418,93 @@ __global__ void __launch_bounds__(256) tv_kernel(const float* __restrict__ x, fl
   if (threadIdx.x == 0 && part != 0.f) atomicAdd(loss, part * scale);
 }
 
+// ---- 3-D resize (util.py:128-167: resize_tf / rescale_tf with is_3d) ------------------------------------------------------
+// The TF-1 legacy resize kernels (no half-pixel centres) over (H, W) of every depth slice, then over D.  One thread per
+// output voxel, W fastest; a pure gather of 8 corners whose C channels stay in registers.  The roundings are the
+// contract (nfs_hip.h): every product and sum below is its own float32 operation -- no contraction into FMAs.
+struct RsAxis { int lo, hi; float t; };
+
+__device__ __forceinline__ RsAxis rs_axis(int i, int n_in, float s, int method, int align) {
+#pragma clang fp contract(off)
+  const float p = (float)i * s;
+  RsAxis a;
+  if (method == 0) {
+    const float f = align ? roundf(p) : floorf(p);
+    a.lo = a.hi = min((int)f, n_in - 1);
+    a.t = 0.f;
+  } else {
+    const float f = floorf(p);
+    a.lo = min((int)f, n_in - 1);
+    a.hi = min((int)ceilf(p), n_in - 1);
+    a.t = p - f;
+  }
+  return a;
+}
+
+__device__ __forceinline__ float rs_lerp(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float m = d * t;
+  return a + m;
+}
+
+// 4-byte-aligned rows of C floats (gfx950 global loads only need dword alignment: common.h F2u)
+template <int C> struct __attribute__((packed, aligned(4))) RsVox { float c[C]; };
+
+template <int C>   // C = 0: any channel count, a loop over `Cn`
+__global__ void __launch_bounds__(256) resize3d_kernel(const float* __restrict__ x, float* __restrict__ out, int D, int H,
+                                                       int W, int Cn, int oD, int oH, int oW, float sD, float sH,
+                                                       float sW, int method, int align, float scale) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (int64_t)oD * oH * oW) return;
+  const int od = (int)(gid / ((int64_t)oW * oH));
+  const unsigned rem = (unsigned)(gid - (int64_t)od * oW * oH);         // (an output plane is below 2^31 voxels: the host checks)
+  const int oh = (int)(rem / (unsigned)oW), ow = (int)(rem - (unsigned)oh * (unsigned)oW);
+  const RsAxis ad = rs_axis(od, D, sD, method, align), ah = rs_axis(oh, H, sH, method, align),
+               aw = rs_axis(ow, W, sW, method, align);
+  const int64_t row[4] = {((int64_t)ad.lo * H + ah.lo) * W, ((int64_t)ad.lo * H + ah.hi) * W,
+                          ((int64_t)ad.hi * H + ah.lo) * W, ((int64_t)ad.hi * H + ah.hi) * W};
+  if constexpr (C > 0) {
+    typedef RsVox<C> Vox;
+    const Vox* __restrict__ xv = reinterpret_cast<const Vox*>(x);
+    Vox v[8], r;
+    if (method == 0) {
+      r = xv[row[0] + aw.lo];
+#pragma unroll
+      for (int c = 0; c < C; ++c) r.c[c] *= scale;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[2 * k] = xv[row[k] + aw.lo];
+        v[2 * k + 1] = xv[row[k] + aw.hi];
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float r0 = rs_lerp(rs_lerp(v[0].c[c], v[1].c[c], aw.t), rs_lerp(v[2].c[c], v[3].c[c], aw.t), ah.t);
+        const float r1 = rs_lerp(rs_lerp(v[4].c[c], v[5].c[c], aw.t), rs_lerp(v[6].c[c], v[7].c[c], aw.t), ah.t);
+        r.c[c] = rs_lerp(r0, r1, ad.t) * scale;
+      }
+    }
+    if constexpr (C == 4) {     // (the host picks this instance only for a 16-byte aligned `out`)
+      reinterpret_cast<float4*>(out)[gid] = make_float4(r.c[0], r.c[1], r.c[2], r.c[3]);
+    } else {
+      reinterpret_cast<Vox*>(out)[gid] = r;
+    }
+  } else {
+    float* __restrict__ o = out + gid * Cn;
+    for (int c = 0; c < Cn; ++c) {
+      if (method == 0) {
+        o[c] = x[(row[0] + aw.lo) * Cn + c] * scale;
+        continue;
+      }
+      float q[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = rs_lerp(x[(row[k] + aw.lo) * Cn + c], x[(row[k] + aw.hi) * Cn + c], aw.t);
+      o[c] = rs_lerp(rs_lerp(q[0], q[1], ah.t), rs_lerp(q[2], q[3], ah.t), ad.t) * scale;
+    }
+  }
+}
+
 }  // namespace nfs
 
 using namespace nfs;
@@ -555,6 +643,34 @@ int nfs_tv_loss(const float* d_img, float* loss_acc, float* g_acc, int B, int H,
   hipLaunchKernelGGL(tv_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d_img, loss_acc, g_acc, B, H,
                      W, C, weight / (float)B);
   return check_launch("nfs_tv_loss");
+}
+
+static float resize_factor(int n_in, int n_out, int align_corners) {
+  return (align_corners && n_out > 1) ? (float)(n_in - 1) / (float)(n_out - 1) : (float)n_in / (float)n_out;
+}
+
+int nfs_resize3d(const float* x, float* out, int D, int H, int W, int C, int oD, int oH, int oW, int method,
+                 int align_corners, float scale, nfs_stream_t stream) {
+  NFS_REQUIRE(x && out, "nfs_resize3d: null pointer");
+  NFS_REQUIRE(D > 0 && H > 0 && W > 0 && C > 0, "nfs_resize3d: non-positive input dimension");
+  NFS_REQUIRE(oD > 0 && oH > 0 && oW > 0, "nfs_resize3d: non-positive output dimension");
+  NFS_REQUIRE(method == 0 || method == 1, "nfs_resize3d: method must be 0 (nearest) or 1 (bilinear)");
+  NFS_REQUIRE(x != out, "nfs_resize3d: out must not alias x");
+  const int64_t n = (int64_t)oD * oH * oW;
+  NFS_REQUIRE((int64_t)oH * oW < ((int64_t)1 << 31), "nfs_resize3d: an output plane must stay below 2^31 voxels");
+  NFS_REQUIRE(blocks_for(n, 256) == (n + 255) / 256, "nfs_resize3d: more output voxels than one grid takes");
+  const float sD = resize_factor(D, oD, align_corners), sH = resize_factor(H, oH, align_corners),
+              sW = resize_factor(W, oW, align_corners);
+  const int al = align_corners ? 1 : 0;
+#define NFS_RESIZE3D_GO(C_)                                                                                            \
+  hipLaunchKernelGGL(resize3d_kernel<C_>, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), x, out, D, H, W, \
+                     C, oD, oH, oW, sD, sH, sW, method, al, scale)
+  if (C == 1) NFS_RESIZE3D_GO(1);
+  else if (C == 3) NFS_RESIZE3D_GO(3);
+  else if (C == 4 && aligned16(out)) NFS_RESIZE3D_GO(4);
+  else NFS_RESIZE3D_GO(0);
+#undef NFS_RESIZE3D_GO
+  return check_launch("nfs_resize3d");
 }
 
 }  // extern "C"

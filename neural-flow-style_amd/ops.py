@@ -941,6 +941,25 @@ def resize_bicubic_tf1(x, oh, ow):
     return out
 
 
+RESIZE_METHODS = {"nearest": 0, "bilinear": 1}
+
+
+def resize3d(x, size, method="bilinear", align_corners=False, scale=1.0):
+    """TF-1 legacy resize of a volume x [D,H,W] or [D,H,W,C] -> ``size`` = (oD, oH, oW), times ``scale``: over (H, W) of
+    every depth slice, then over D (util.py:128-143 with is_3d); forward only.  ``method``: 'nearest' or 'bilinear'."""
+    if method not in RESIZE_METHODS:
+        raise ValueError("resize3d method %r: 'nearest' or 'bilinear'" % (method,))
+    if x.dim() not in (3, 4):
+        raise ValueError("resize3d takes [D,H,W] or [D,H,W,C], got %s" % (tuple(x.shape),))
+    D, H, W = x.shape[:3]
+    Cn = x.shape[3] if x.dim() == 4 else 1
+    oD, oH, oW = (int(s) for s in size)
+    out = _empty((oD, oH, oW) + tuple(x.shape[3:]), x)
+    _lib.call("nfs_resize3d", _ptr(x), _ptr(out), D, H, W, Cn, oD, oH, oW, RESIZE_METHODS[method],
+              int(bool(align_corners)), float(scale), _stream())
+    return out
+
+
 def style_mask_apply(F, mask):
     """F [B,h,w,C], mask [B,h,w,1] -> (F * mask, scale [B] = 1 / (2 * sum(mask) * C))  (styler_base.py:167-169)"""
     B, Cn = F.shape[0], F.shape[-1]

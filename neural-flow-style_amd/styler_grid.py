@@ -29,6 +29,17 @@ Frames shard over ranks: contiguous blocks of optimiser g
 (parallel.plan_frames), every rank keeps full view batches, and the only exchange is the halo of per-frame updates
 the temporal filter reaches (point-to-point, parallel.exchange_frames) plus a handful of loss scalars.  The sharded
 run reproduces the single-rank trajectory (tests: world-2 gloo, two ranks on one GPU).
+
+Octaves (``octave_n`` > 1, sizes as in the particle loop, styler_3p.py:240-247, 271-296): the loop runs coarsest first on the
+density frames and simulation velocities resampled from the full-resolution originals (``ops.resize3d``: the reference's
+``util.resize_tf`` of a volume, util.py:128-143), and hands the variable of every key frame to the next octave by the
+same resample.  The grid is corner-aligned (one cell = 2/(n-1) in ``advect``), so every resample is bilinear with
+``align_corners``: node 0 and node n-1 are the same points of the domain at every octave, and a velocity in advect units
+is the same displacement at every octave (factor 1).  A potential or stream function is differentiated per CELL
+(``ops.source_velocity``), so its resample carries the factor f = mean over the axes of (n_out-1)/(n_in-1), which keeps
+the flow it stands for; on an anisotropic grid the three ratios differ slightly and that warm start is approximate.
+Every octave starts with fresh optimiser state (Adam moments, L-BFGS pairs: their shapes belong to the old grid) and a
+fresh ``engine.GridStylizer``.
 """
 from __future__ import annotations
 
@@ -50,7 +61,13 @@ class Styler(StylerBase):
     'p': a potential [D,H,W] (``ops.potential_velocity``, irrotational; ``params['p_init'][t]``), 'sp': the Helmholtz pair
     [D,H,W,4] = (stream function, potential) (``ops.helmholtz_velocity``; ``params['sp_init'][t]``): ``'opt'`` is the
     variable, ``'v'`` the velocity it stands for, ``'s'`` its stream-function part ('s', 'sp') and ``'phi'`` its potential
-    ('p', 'sp'); ``'p'`` stays the reference's particle-position key (None on the grid path)."""
+    ('p', 'sp'); ``'p'`` stays the reference's particle-position key (None on the grid path).
+    ``octave_n`` > 1 (module docstring; not with 'd'): ``run`` is ``prepare``, then per octave ``next_octave()`` (from the
+    second on) and ``iter`` x ``iterate()``, then ``finish()``.  The result's ``'l'`` is one list per octave, ``'l_frames'``
+    the per-iteration rows of all octaves in order, ``'d_intm'`` per octave but the last the uint8 identity-rotation
+    renders of the key frames this rank holds (concatenated along axis 0, styler_3p.py:365-390), ``'opt_octave'`` per
+    octave {own key frame: the variable as the octave left it, at that octave's size}, ``'octave_sizes'`` the sizes;
+    everything else is at full resolution."""
 
     def __init__(self, self_dict):
         StylerBase.__init__(self, self_dict)
@@ -58,6 +75,18 @@ class Styler(StylerBase):
         self.target = getattr(self, "grid_variable", "") or "v"
         assert self.target in ("v", "d") + engine.SOURCED
         self.adv_order = int(getattr(self, "adv_order", 1) or 1)       # config.py adv_order: 1 = SL, 2 = MacCormack
+        self.octave_n = int(self.octave_n)
+        if self.target == "d" and self.octave_n > 1:
+            raise ValueError("grid_variable='d' with octave_n=%d: the variable is the density itself, and resampling it to "
+                             "a coarser octave would discard the fine detail of the input -- use octave_n=1"
+                             % self.octave_n)
+        if abs(getattr(self, "lr_scale", 1) - 1) > 1e-7 and not isinstance(self.lr, list):
+            self.lr = [self.lr / self.lr_scale ** i for i in range(self.octave_n)]      # styler_3p.py:236-238
+        self.octave_sizes = octave_sizes(self.resolution, self.octave_n, self.octave_scale)
+        if self.octave_n > 1 and min(self.octave_sizes[0]) < 2:
+            raise ValueError("octave_n=%d at octave_scale=%g takes resolution %s down to %s: every octave needs at least "
+                             "two nodes per axis" % (self.octave_n, self.octave_scale, list(self.resolution),
+                                                     self.octave_sizes[0]))
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -163,8 +192,6 @@ class Styler(StylerBase):
         """Put this rank's share of the sequence on the device and set up the loop state.  ``params['d']`` /
         ``params['v']`` / ``params['v_init']``: list over frames or {frame: array}; a sharded run only needs the
         frames this rank touches (``frames_needed(rank, world)``; ``frames_on_device`` = its density frames)."""
-        assert self.octave_n == 1, "the grid path has one octave (the reference's octaves resize the SPLAT target, " \
-                                   "styler_3p.py:241-247; a grid sequence comes at its own resolution)"
         F_ = int(self.num_frames)
         rank, world = self._rank_world()
         st = self._st = argparse_ns()
@@ -188,13 +215,45 @@ class Styler(StylerBase):
         want_d = set(range(F_)) if frames_on_device is None else set(frames_on_device) | set(st.mine)
         want_u = set(range(F_)) if frames_on_device is None else \
             set(range(max(min(st.need) - 1, 0), min(max(st.need) + 1, F_))) if st.need else set()
-        st.d = {t: x.reshape(tuple(self.resolution)) for t, x in self._frames(params["d"], sorted(want_d)).items()}
-        st.u = self._frames(params.get("v"), sorted(want_u))
-        if st.Wt is not None and st.mine and not st.u:
+        st.d_full = {t: x.reshape(tuple(self.resolution)) for t, x in self._frames(params["d"], sorted(want_d)).items()}
+        st.u_full = self._frames(params.get("v"), sorted(want_u))
+        if st.Wt is not None and st.mine and not st.u_full:
             raise ValueError("params['v'] (simulation velocities) is needed to align the updates of a sequence")
-        st.u = st.u or {}
-        D, H, W_ = tuple(self.resolution)
+        st.u_full = st.u_full or {}
         st.C = {"v": 3, "s": 3, "sp": 4}.get(self.target, 1)
+        # the variable per key frame: stylisation velocity (zero, or params['v_init'][t]) / the density itself.
+        # NOTE: at velocity == 0 every back-traced point sits exactly on a grid node, where the trilinear stencil has a
+        # kink -- the first gradient is a one-sided derivative whose side depends on float rounding (DESIGN.md section 5)
+        st.v_init = params.get(self.target + "_init" if self.target in engine.SOURCED else "v_init")
+        st.hist, st.hist_octave, st.d_intm, st.opt_octave = [], [], [], []
+        st.octave = 0
+        self._enter_octave(None)
+        return st
+
+    def _resample(self, x, size, factor=1.0):
+        """a volume [D,H,W] or [D,H,W,C] at ``size``: the corner-aligned bilinear resample of the octaves (the very tensor
+        where the size is its own: one octave issues no resize)"""
+        if tuple(x.shape[:3]) == tuple(size):
+            return x
+        return ops.resize3d(x.contiguous(), size, "bilinear", align_corners=True, scale=factor)
+
+    def _factor(self, n_in, n_out):
+        """what a resampled variable is multiplied by: 1 for a velocity; a potential or stream function is differenced
+        per cell, so it takes the mean over the axes of (n_out-1)/(n_in-1) (float64, cast to float32 once)"""
+        if self.target not in engine.SOURCED or tuple(n_in) == tuple(n_out):
+            return 1.0
+        return float(np.float32(np.mean([(float(o) - 1.0) / (float(i) - 1.0) for i, o in zip(n_in, n_out)],
+                                        dtype=np.float64)))
+
+    def _enter_octave(self, prev):
+        """set the loop state up for octave ``st.octave``: inputs resampled from the full-resolution originals, the loss
+        targets at the octave's [H,W], its learning rate, the variable of every own key frame (octave 0: zero or the
+        resampled ``'_init'``; later: ``g_opt`` resampled from the size ``prev``), fresh optimiser state and stylizer"""
+        st = self._st
+        o = st.octave
+        D, H, W_ = size = tuple(int(n) for n in self.octave_sizes[o])
+        st.d = {t: self._resample(x, size) for t, x in st.d_full.items()}
+        st.u = {t: self._resample(x, size) for t, x in st.u_full.items()}
         st.shape = (D, H, W_, st.C)
         if self.style_img is not None:
             self.loss.set_style_image(self._style_feature(self.style_img, [H, W_]))
@@ -202,31 +261,73 @@ class Styler(StylerBase):
                 self.loss.set_hist_image(self._hist_feature(self.style_img, [H, W_]))
         if self.content_img is not None:
             self.loss.set_content_image(self._content_feature(self.content_img, [H, W_]), top_k=self._content_top_k())
-        st.lr = self.lr[0] if isinstance(self.lr, list) else self.lr
-        # the variable per key frame: stylisation velocity (zero, or params['v_init'][t]) / the density itself.
-        # NOTE: at velocity == 0 every back-traced point sits exactly on a grid node, where the trilinear stencil has a
-        # kink -- the first gradient is a one-sided derivative whose side depends on float rounding (DESIGN.md section 5)
-        st.v_init = params.get(self.target + "_init" if self.target in engine.SOURCED else "v_init")
-        st.g_opt = {t: self._initial(t) for t in st.mine}
+        st.lr = self.lr[o] if isinstance(self.lr, list) else self.lr
+        if prev is None:
+            st.g_opt = {t: self._initial(t) for t in st.mine}
+        else:
+            f = self._factor(prev, size)
+            st.g_opt = {t: self._resample(st.g_opt[t], size, f) for t in st.mine}
         st.work = torch.zeros(st.shape, device=self.device)     # the variable (re-assigned per frame, 312)
         # (a rank beyond the number of optimiser groups owns no frame: it only takes part in the collectives)
         first = st.d[st.mine[0]] if st.mine else (next(iter(st.d.values())) if st.d else
-                                                  torch.zeros(tuple(self.resolution), device=self.device))
+                                                  torch.zeros(size, device=self.device))
         st.gs = engine.GridStylizer(self.loss, first, k=self.k, target=self.target, lr=st.lr,
                                     optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
         st.opt_ = {}
-        st.hist = []
-        return st
+        st.hist_octave.append([])
 
     def _initial(self, t):
+        """the variable of frame t before the first step, at the current octave's size (``'_init'`` comes at full
+        resolution)"""
         st = self._st
         if self.target == "d":
             return st.d[t].reshape(st.shape).clone()
         if st.v_init is not None:
             vi = st.v_init[t] if not isinstance(st.v_init, dict) else st.v_init.get(t)
             if vi is not None:
-                return self._dev(vi).reshape(st.shape).clone()
+                full = tuple(int(n) for n in self.resolution)
+                vi = self._dev(vi).reshape(full + (st.C,))
+                return self._resample(vi, st.shape[:3], self._factor(full, st.shape[:3])).reshape(st.shape).clone()
         return torch.zeros(st.shape, device=self.device)
+
+    def _infer(self, t, var):
+        """frame t through its variable: (velocity the variable stands for or None, smoothed density, render with the
+        identity rotation [1,H,W,3])"""
+        st = self._st
+        D, H, W_, _ = st.shape
+        sourced = self.target in engine.SOURCED
+        if self.target == "p":
+            var = var.reshape(D, H, W_)
+        vel = ops.source_velocity(self.target, var) if sourced else var
+        if self.target != "d":
+            # (the order the loop optimised through)
+            advect = ops.advect_maccormack if self.adv_order == 2 else ops.advect_fwd
+            d_adv = advect(st.d[t].unsqueeze(-1), vel).squeeze(-1)
+        else:
+            d_adv = var.reshape(D, H, W_)
+        d_out = ops.smooth3d_relu_fwd(d_adv.contiguous(), float(self.k))
+        return (vel if sourced else None), d_out, self.loss.d_img(d_out, self._identity)
+
+    def _octave_variables(self):
+        """what an octave leaves behind: the variable of every own key frame at the octave's size"""
+        st = self._st
+        shp = st.shape[:3] if self.target == "p" else st.shape
+        return {t: st.g_opt[t].reshape(shp).cpu().numpy() for t in st.mine}
+
+    def next_octave(self):
+        """close the current octave (its key-frame renders go to ``d_intm``, its variables to ``opt_octave``) and set up
+        the next, finer one: returns its size [D,H,W].  No exchange between ranks: every rank resamples its own frames
+        and variables."""
+        st = self._st
+        if st.octave >= self.octave_n - 1:
+            raise ValueError("next_octave(): octave %d of %d is the last" % (st.octave, self.octave_n))
+        st.opt_octave.append(self._octave_variables())
+        imgs = [self._infer(t, st.g_opt[t])[2].cpu().numpy().astype(np.uint8) for t in st.mine]
+        st.d_intm.append(np.concatenate(imgs, axis=0) if imgs else np.zeros((0,) + st.shape[1:3] + (3,), np.uint8))
+        prev = st.shape[:3]
+        st.octave += 1
+        self._enter_octave(prev)
+        return list(st.shape[:3])
 
     def iterate(self):
         """one iteration of the frame loop (styler_3p.py:301-386): a stylisation step per own key frame, the halo
@@ -262,6 +363,7 @@ class Styler(StylerBase):
             for t in st.mine:
                 st.g_opt[t] = st.g_opt[t] + upd[t]
         st.hist.append(losses)
+        st.hist_octave[-1].append(losses)
         return losses
 
     def key_frame_variables(self):
@@ -297,22 +399,16 @@ class Styler(StylerBase):
                 var = self._initial(t)
             if self.target == "p":
                 var = var.reshape(D, H, W_)                        # (the potential in the shape of params['p_init'][t])
-            vel = ops.source_velocity(self.target, var) if sourced else var
-            if self.target != "d":
-                # (the order the loop optimised through)
-                advect = ops.advect_maccormack if self.adv_order == 2 else ops.advect_fwd
-                d_adv = advect(st.d[t].unsqueeze(-1), vel).squeeze(-1)
-            else:
-                d_adv = var.reshape(D, H, W_)
-            d_out = ops.smooth3d_relu_fwd(d_adv.contiguous(), float(self.k))
-            dimg = self.loss.d_img(d_out, self._identity)
+            vel, d_out, dimg = self._infer(t, var)
             d_sty.append(torch.abs(d_out).unsqueeze(-1).cpu().numpy())   # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
             v_sty.append(var.cpu().numpy())
             if sourced:
                 u_sty.append(vel.cpu().numpy())
         hist = [[float(x) for x in l_.cpu()] for l_ in st.hist]
-        return {"l": [[x for l_ in hist for x in l_]], "l_frames": hist, "d_intm": [],
+        per_octave = [[float(x) for l_ in h for x in l_.cpu()] for h in st.hist_octave]
+        return {"l": per_octave, "l_frames": hist, "d_intm": list(st.d_intm), "opt_octave": st.opt_octave + [self._octave_variables()],
+                "octave_sizes": [[int(n) for n in sz] for sz in self.octave_sizes],
                 "d": np.array(d_sty), "r": np.array(r_sty), "v": v_sty if self.target == "v" else u_sty if sourced else None,
                 "s": v_sty if self.target == "s" else [a[..., :3] for a in v_sty] if self.target == "sp" else None,
                 "phi": v_sty if self.target == "p" else [a[..., 3] for a in v_sty] if self.target == "sp" else None,
@@ -320,9 +416,22 @@ class Styler(StylerBase):
 
     def run(self, params):
         self.prepare(params)
-        for _ in range(self.iter):
-            self.iterate()
+        for o in range(self.octave_n):
+            if o:
+                self.next_octave()
+            for _ in range(self.iter):
+                self.iterate()
         return self.finish()
+
+
+def octave_sizes(resolution, octave_n, octave_scale):
+    """the octaves' grid sizes, coarsest first, the last one ``resolution`` itself (styler_3p.py:240-247)"""
+    sizes, dhw = [], np.array(resolution)
+    for _ in range(int(octave_n)):
+        sizes.append(dhw)
+        dhw = (dhw // octave_scale).astype(int)
+    sizes.reverse()
+    return [[int(n) for n in sz] for sz in sizes]
 
 
 class argparse_ns(object):

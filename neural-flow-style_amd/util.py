@@ -1,6 +1,7 @@
 """Host glue of the optimisation path (reference util.py:169-207, 404-425): temporal
 smoothing of the per-frame updates, style-image cropping / resizing, log-dir helpers.
-Everything here is tiny NumPy/SciPy work on the host; nothing is on the GPU hot path."""
+Everything here is tiny NumPy/SciPy work on the host; nothing is on the GPU hot path -- except ``resize_tf`` /
+``rescale_tf`` (util.py:128-167), which take device tensors and run on ``nfs_resize3d``."""
 from __future__ import annotations
 
 import json
@@ -98,6 +99,38 @@ def resize(img, size=None, f=None, order=1):
         out = np.stack([_resize_plane(img[..., c], size, order) for c in range(img.shape[-1])], -1)
     out = out.astype(np.float32)
     return out * (vmax - vmin) + vmin if norm else out
+
+
+def _resize_batch(x, size, method, is_3d):
+    import torch
+    from . import ops
+    want = 5 if is_3d else 4
+    if x.dim() != want:
+        raise ValueError("resize_tf(is_3d=%s) takes [B,%sH,W,C], got %s" % (is_3d, "D," if is_3d else "", tuple(x.shape)))
+    size = [int(s) for s in size]
+    if method == "bicubic" and not is_3d:
+        return ops.resize_bicubic_tf1(x.contiguous(), size[0], size[1])
+    if method not in ops.RESIZE_METHODS:
+        raise ValueError("resize method %r: 'nearest', 'bilinear', or 'bicubic' for images (is_3d=False)" % (method,))
+    x = x.contiguous()
+    if is_3d:
+        return torch.stack([ops.resize3d(x[b], size, method) for b in range(x.shape[0])])
+    # an image is a volume of depth 1: at equal size the depth pass is an exact identity
+    return torch.stack([ops.resize3d(x[b].unsqueeze(0), [1] + size, method)[0] for b in range(x.shape[0])])
+
+
+def resize_tf(x, size, method="nearest", is_3d=False):
+    """util.resize_tf (util.py:128-143) on device tensors: x [B,H,W,C] -> ``size`` = (h, w), or with ``is_3d`` x
+    [B,D,H,W,C] -> ``size`` = (d, h, w) as a resize over (H, W) of every depth slice, then over D.  The TF-1 legacy kernels
+    (``tf.compat.v1.image.resize``: align_corners False, no half-pixel centres); ``method`` 'nearest' (the reference's
+    default), 'bilinear', or -- images only -- 'bicubic'."""
+    return _resize_batch(x, size, method, is_3d)
+
+
+def rescale_tf(x, scale, method="bilinear", is_3d=False):
+    """util.rescale_tf (util.py:145-167): ``resize_tf`` to int(float32(n) * scale) per axis (the reference's casts)"""
+    n = x.shape[1:4] if is_3d else x.shape[1:3]
+    return _resize_batch(x, [int(np.float32(k) * np.float32(scale)) for k in n], method, is_3d)
 
 
 def prepare_dirs_and_logger(config):
