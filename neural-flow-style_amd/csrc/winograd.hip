@@ -13,9 +13,12 @@
 //   winograd_input*_kernel   x [B,H,W,K]            -> V [(m+2)^2][T][K]    T = B * ceil(H/m) * ceil(W/m) tiles
 //   winograd_gemm_kernel     V, U [(m+2)^2][K/32][N][32] -> M [(m+2)^2][T][N]  f32 MFMA, fragment scheme of vgg.hip
 //   winograd_output*_kernel  M                      -> y [B,H,W,N]    + bias/ReLU (fwd) or ReLU mask/addend (dgrad)
+// The F(4x4) transforms exist in two schedules (one thread per tile and channel pair; six waves per tile); what the two
+// must agree on -- the layer epilogue, the layout of the ReLU bit cache, the tile split -- is in winograd_transform.h.
 #include "common.h"
 #include "winograd_math.h"
 #include "winograd_gemm.h"
+#include "winograd_transform.h"
 
 #include <algorithm>
 #include <atomic>
@@ -130,49 +133,8 @@ __global__ void __launch_bounds__(256) winograd_input_kernel(const float* __rest
   }
 }
 
-// ---- F(4x4, 3x3): weights U_k = (G g G^T)[k], k = 0..35, packed [36][K/32][N][32] ----------------------
-// G = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],[1/24,1/12,1/6],[1/24,-1/12,1/6],[0,0,1]]
-__device__ __forceinline__ void wg4_g(const float g0, const float g1, const float g2, float* u) {
-  u[0] = 0.25f * g0;
-  u[1] = (-1.f / 6.f) * (g0 + g1 + g2);
-  u[2] = (-1.f / 6.f) * (g0 - g1 + g2);
-  u[3] = (1.f / 24.f) * g0 + (1.f / 12.f) * g1 + (1.f / 6.f) * g2;
-  u[4] = (1.f / 24.f) * g0 - (1.f / 12.f) * g1 + (1.f / 6.f) * g2;
-  u[5] = g2;
-}
-
-__global__ void __launch_bounds__(256) winograd_pack4_kernel(const float* __restrict__ w, float* __restrict__ up,
-                                                             int Ci, int Co, int kind) {
-  const int Kc = kind == 0 ? Ci : Co, Nc = kind == 0 ? Co : Ci;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (int64_t)Kc * Nc) return;
-  const int n = (int)(gid % Nc), k = (int)(gid / Nc);
-  float g[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      if (kind == 0) g[r][s] = w[((int64_t)(r * 3 + s) * Ci + k) * Co + n];
-      else g[r][s] = w[((int64_t)((2 - r) * 3 + (2 - s)) * Ci + n) * Co + k];
-    }
-  float t[6][3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    float u[6];
-    wg4_g(g[0][s], g[1][s], g[2][s], u);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) t[r][s] = u[r];
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    float u[6];
-    wg4_g(t[r][0], t[r][1], t[r][2], u);
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-      up[(((int64_t)(r * 6 + q) * (Kc / 32) + k / 32) * Nc + n) * 32 + (k & 31)] = u[q];
-  }
-}
-
+// ---- F(4x4, 3x3): weights U_k = (G g G^T)[k], k = 0..35, packed [36][K/32][N][32]: winograd_pack_tile_kernel<6>
+// (winograd_transform.h) ----
 // input transform: one thread = one 6x6 patch x 2 channels (a wave covers 128 contiguous channels per pixel)
 // POOLED: the operand is not stored -- it is the gradient coming through a 2x2 VALID average pool below a ReLU,
 // d(y, x) = 0.25 * gpool[y/2, x/2] * (xmask[y, x] > 0) (0 outside the pooled area), formed on the fly
@@ -192,16 +154,11 @@ __global__ void __launch_bounds__(256) winograd_input4_kernel(const float* __res
   //   POOLED 1: `bits` is READ instead of xmask (recorded by the forward output transform of this layer).
   const int K2 = K >> 1;
   const int64_t T = (int64_t)B * TH * TW;
-  // 6x6 input patches of neighbouring tiles overlap by two pixels: give each XCD a contiguous range of tiles
-  // (workgroups are dealt round-robin to the 8 XCDs), or every shared pixel is fetched from HBM into two L2s
-  // (PMC: 2.0x / 2.5x the compulsory read bytes with the plain order)
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  const int64_t gid = (int64_t)lb * blockDim.x + threadIdx.x;
+  const int64_t gid = (int64_t)wg_xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   if (gid >= T * K2) return;
   const int c2 = (int)(gid % K2);
   const int64_t tile = gid / K2;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int y0 = 4 * ty - 1, x0 = 4 * tx - 1;
   const int PH = H >> 1, PW = W >> 1;
   float2 d[6][6];         // d[s][r]: patch column s, row r
@@ -246,15 +203,13 @@ __global__ void __launch_bounds__(256) winograd_input4_kernel(const float* __res
         const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
         v = make_float2(ok ? v.x : 0.f, ok ? v.y : 0.f);
         if (r >= 1 && r <= 4 && s >= 1 && s <= 4)
-          word |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u)) << (((r - 1) * 4 + (s - 1)) * 2);
+          word |= wg4_bit_pair(v) << NFS_WG4_BIT_SHIFT(r - 1, s - 1);
       } else {
         const bool ok = yy >= 0 && xx >= 0 && (yy >> 1) < PH && (xx >> 1) < PW;
         bool mx, my;
         if (POOLED == 1) {
           // patch row r: tile offset / row inside that tile (row 0 = last row of the tile above, 5 = first below)
-          const int dy = r == 0 ? 0 : (r == 5 ? 2 : 1), ir = r == 0 ? 3 : (r == 5 ? 0 : r - 1);
-          const int dx = s == 0 ? 0 : (s == 5 ? 2 : 1), is = s == 0 ? 3 : (s == 5 ? 0 : s - 1);
-          const uint32_t wv = nb[dy][dx] >> ((ir * 4 + is) * 2);
+          const uint32_t wv = nb[NFS_WG4_NB_TILE(r)][NFS_WG4_NB_TILE(s)] >> NFS_WG4_BIT_SHIFT(NFS_WG4_NB_POS(r), NFS_WG4_NB_POS(s));
           mx = wv & 1u;
           my = wv & 2u;
         } else {
@@ -294,7 +249,7 @@ __global__ void __launch_bounds__(256) winograd_output4_kernel(const float* __re
   if (gid >= T * N2) return;
   const int c2 = (int)(gid % N2);
   const int64_t tile = gid / N2;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int64_t comp_stride = T * N;
   const float* mi = M + tile * N + 2 * c2;
   float2 pool[2][2] = {{make_float2(0.f, 0.f), make_float2(0.f, 0.f)}, {make_float2(0.f, 0.f), make_float2(0.f, 0.f)}};
@@ -342,17 +297,17 @@ __global__ void __launch_bounds__(256) winograd_output4_kernel(const float* __re
       if (xx >= W) continue;
       float2 v = o[c];
       const int64_t idx = (((int64_t)b * H + yy) * W + xx) * N + 2 * c2;
+      // (NFS_WG_EPILOGUE's rule written out: through the macro the two data-gradient instances of this kernel lost the
+      // parent's instruction stream, <1, 2> with 220 VGPRs for 210 -- profiles/winograd_transform_refactor.txt)
       if (MODE == 0) {
         v.x += bias.x; v.y += bias.y;
         if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
-        word |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u)) << ((a * 4 + c) * 2);
+        word |= wg4_bit_pair(v) << NFS_WG4_BIT_SHIFT(a, c);
       } else {
-        // relu != 0 in this mode: the addend has NOT been through the ReLU mask yet (same mask: both are gradients
-        // wrt the output of the layer below), so it is added first and masked with the rest
         const float2 ad = aux1 ? adq[a][c] : make_float2(0.f, 0.f);
         if (relu) { v.x += ad.x; v.y += ad.y; }
         if (bits) {
-          const uint32_t wv = word >> ((a * 4 + c) * 2);
+          const uint32_t wv = word >> NFS_WG4_BIT_SHIFT(a, c);
           v.x = (wv & 1u) ? v.x : 0.f; v.y = (wv & 2u) ? v.y : 0.f;
         } else if (aux0) {
           const float2 xin = *reinterpret_cast<const float2*>(aux0 + idx);
@@ -393,19 +348,18 @@ __global__ void __launch_bounds__(384) winograd_input4w_kernel(const float* __re
   __shared__ uint32_t wk[4][64];                 // the mask bits of patch columns 1..4
   const int K2 = K >> 1, kg = K >> 7;
   const int64_t T = (int64_t)B * TH * TW;
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+  const unsigned lb = wg_xcd_block(blockIdx.x, gridDim.x);
   if ((int64_t)lb >= T * kg) return;
   const int64_t tile = lb / kg;
   const int lane = threadIdx.x, w = threadIdx.y, c2 = (int)(lb % kg) * 64 + lane;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int y0 = 4 * ty - 1, x0 = 4 * tx - 1;
   const int PH = H >> 1, PW = W >> 1;
   const int64_t gid = tile * K2 + c2;
   {
     const int s = w, xx = x0 + s;
     [[maybe_unused]] uint32_t nb[3];             // POOLED 1: the words of the three tiles this patch column reaches into
-    const int dx = s == 0 ? 0 : (s == 5 ? 2 : 1), is = s == 0 ? 3 : (s == 5 ? 0 : s - 1);
+    const int dx = NFS_WG4_NB_TILE(s), is = NFS_WG4_NB_POS(s);
     if (POOLED == 1) {
       const int nx = min(max(tx + dx - 1, 0), TW - 1);
 #pragma unroll
@@ -434,16 +388,15 @@ __global__ void __launch_bounds__(384) winograd_input4w_kernel(const float* __re
       if (!POOLED) {
         const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
         v = make_float2(ok ? v.x : 0.f, ok ? v.y : 0.f);
-        if (r >= 1 && r <= 4) word |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u)) << (((r - 1) * 4) * 2);
+        if (r >= 1 && r <= 4) word |= wg4_bit_pair(v) << NFS_WG4_BIT_SHIFT(r - 1, 0);
       } else {
         const bool ok = yy >= 0 && xx >= 0 && (yy >> 1) < PH && (xx >> 1) < PW;
-        const int dy = r == 0 ? 0 : (r == 5 ? 2 : 1), ir = r == 0 ? 3 : (r == 5 ? 0 : r - 1);
-        const uint32_t wv = nb[dy] >> ((ir * 4 + is) * 2);
+        const uint32_t wv = nb[NFS_WG4_NB_TILE(r)] >> NFS_WG4_BIT_SHIFT(NFS_WG4_NB_POS(r), is);
         v = make_float2((ok && (wv & 1u)) ? 0.25f * v.x : 0.f, (ok && (wv & 2u)) ? 0.25f * v.y : 0.f);
       }
       d[r] = v;
     }
-    if (!POOLED && bits && s >= 1 && s <= 4) wk[s - 1][lane] = word << ((s - 1) * 2);
+    if (!POOLED && bits && s >= 1 && s <= 4) wk[s - 1][lane] = word << NFS_WG4_BIT_SHIFT(0, s - 1);
     float2 t[6];
     wg4_bt(d, t);
 #pragma unroll
@@ -472,7 +425,7 @@ __global__ void __launch_bounds__(384) winograd_output4w_kernel(const float* __r
   const int64_t T = (int64_t)B * TH * TW;
   const int64_t tile = blockIdx.x / ng;
   const int lane = threadIdx.x, w = threadIdx.y, c2 = (int)(blockIdx.x % ng) * 64 + lane;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int64_t comp_stride = T * N, gid = tile * N2 + c2;
   const int a = min(w, 3), yy = 4 * ty + a;
   // the second pass's operands first: row a of the addend and the mask word (clamped addresses, no branch around a load)
@@ -518,22 +471,8 @@ __global__ void __launch_bounds__(384) winograd_output4w_kernel(const float* __r
         float2 v = o[c];
         if (xx < W) {
           const int64_t idx = (((int64_t)b * H + yy) * W + xx) * N + 2 * c2;
-          if (MODE == 0) {
-            v.x += bias.x; v.y += bias.y;
-            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
-            wout |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u)) << ((a * 4 + c) * 2);
-          } else {
-            const float2 ad = aux1 ? adq[c] : make_float2(0.f, 0.f);
-            if (relu) { v.x += ad.x; v.y += ad.y; }
-            if (bits) {
-              const uint32_t wv = word >> ((a * 4 + c) * 2);
-              v.x = (wv & 1u) ? v.x : 0.f; v.y = (wv & 2u) ? v.y : 0.f;
-            } else if (aux0) {
-              const float2 xin = *reinterpret_cast<const float2*>(aux0 + idx);
-              v.x = xin.x > 0.f ? v.x : 0.f; v.y = xin.y > 0.f ? v.y : 0.f;
-            }
-            if (!relu) { v.x += ad.x; v.y += ad.y; }
-          }
+          NFS_WG_EPILOGUE(MODE, float2, make_float2(0.f, 0.f), v, bias, relu, aux1, adq[c], bits, word >> NFS_WG4_BIT_SHIFT(a, c), aux0, idx);
+          if (MODE == 0) wout |= wg4_bit_pair(v) << NFS_WG4_BIT_SHIFT(a, c);
           if (MODE != 0 || y) *reinterpret_cast<float2*>(y + idx) = v;
         }
         if (MODE == 0) vs[a][c][lane] = v;        // (outside the image: never part of a complete pooling window)
@@ -1865,7 +1804,7 @@ int64_t winograd_packed_floats(int Ci, int Co) {
 int winograd_pack(const float* w_hwio, float* up, int Ci, int Co, int kind, hipStream_t s) {
   const int64_t n = (int64_t)Ci * Co;
   if (winograd_tile() == 4) {
-    hipLaunchKernelGGL(winograd_pack4_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, w_hwio, up, Ci, Co, kind);
+    hipLaunchKernelGGL(winograd_pack_tile_kernel<6>, dim3(blocks_for(n, 256)), dim3(256), 0, s, w_hwio, up, Ci, Co, kind);
     const int Kc = kind == 0 ? Ci : Co, Nc = kind == 0 ? Co : Ci;
     hipLaunchKernelGGL(winograd_pack_frag_kernel, dim3(blocks_for(36 * n, 256)), dim3(256), 0, s, up, up + 36 * n, Kc, Nc,
                        36 * n);
@@ -1910,23 +1849,24 @@ int winograd_conv(const float* x, const float* U, const float* aux0, const float
   static const int64_t waves6_max = [] { const char* e = getenv("NFS_W4_WAVES6_MAX"); return e ? atoll(e) : (int64_t)65536; }();
   const bool in6 = m == 4 && K % 128 == 0 && T * K <= waves6_max, out6 = m == 4 && N % 128 == 0 && T * N <= waves6_max;
   const dim3 ig6((unsigned)((T * (K / 128) + 7) / 8 * 8));
-  if (in6 && pooled_grad && mode == 1 && out_bits)
-    hipLaunchKernelGGL(winograd_input4w_kernel<1>, ig6, dim3(64, 6), 0, s, x, V, B, H, W, K, TH, TW, out_bits);
-  else if (in6 && !pooled_grad)
-    hipLaunchKernelGGL(winograd_input4w_kernel<0>, ig6, dim3(64, 6), 0, s, x, V, B, H, W, K, TH, TW,
-                       mode == 0 ? in_bits : (uint32_t*)nullptr);
-  else
-  if (m == 4 && pooled_grad && mode == 1 && out_bits)   // pooled data gradient: the mask of the layer's own output from the bit cache ...
-    hipLaunchKernelGGL(winograd_input4_kernel<1>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW, xmask, out_bits);
-  else if (m == 4 && pooled_grad)                       // ... or from the float output
-    hipLaunchKernelGGL(winograd_input4_kernel<2>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW, xmask,
-                       (uint32_t*)nullptr);
-  else if (m == 4)
-    hipLaunchKernelGGL(winograd_input4_kernel<0>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW,
-                       (const float*)nullptr, mode == 0 ? in_bits : nullptr);
-  else
+  // the pooled data gradient masks from the bit cache of the layer's own output (POOLED 1) or from its float output (2)
+  const bool pool_bits = pooled_grad && mode == 1 && out_bits;
+  uint32_t* const wbits = mode == 0 ? in_bits : nullptr;                 // forward: record the mask of x
+  if (m != 4)
     hipLaunchKernelGGL(winograd_input_kernel, dim3(blocks_for(T * (K / 4), 256)), dim3(256), 0, s, x, V, B, H, W, K, TH,
                        TW);
+  else if (in6 && pool_bits)
+    hipLaunchKernelGGL(winograd_input4w_kernel<1>, ig6, dim3(64, 6), 0, s, x, V, B, H, W, K, TH, TW, out_bits);
+  else if (in6 && !pooled_grad)
+    hipLaunchKernelGGL(winograd_input4w_kernel<0>, ig6, dim3(64, 6), 0, s, x, V, B, H, W, K, TH, TW, wbits);
+  else if (pool_bits)
+    hipLaunchKernelGGL(winograd_input4_kernel<1>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW, xmask, out_bits);
+  else if (pooled_grad)
+    hipLaunchKernelGGL(winograd_input4_kernel<2>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW, xmask,
+                       (uint32_t*)nullptr);
+  else
+    hipLaunchKernelGGL(winograd_input4_kernel<0>, ig, dim3(256), 0, s, x, V, B, H, W, K, TH, TW, (const float*)nullptr,
+                       wbits);
   WgGemmArgs a{V, U, M, T, K, N, (int64_t)K * N, (int64_t)N * 32, 32, 1.f, nullptr, nullptr};
   if (m == 4) {
     a.Uq = U + (int64_t)36 * K * N;
@@ -1936,34 +1876,21 @@ int winograd_conv(const float* x, const float* U, const float* aux0, const float
   const int nsplit = launch_batched_gemm(a, comps, cus, s);
   if (m == 4) {
     const unsigned ob = blocks_for(T * (N / 2), 256);
-    uint32_t* ib = aux0 ? in_bits : nullptr;                              // a mask only where the caller asks for one
     if (nsplit != 1 && nsplit != 2) {
       set_error("winograd_conv: unsupported number of K parts");
       return NFS_EINVAL;
     }
-    if (out6) {
-      const dim3 og6((unsigned)(T * (N / 128)));
-#define NFS_W4_OUT6(MODE_, NS_, POOL_, BITS_)                                                                         \
-      hipLaunchKernelGGL((winograd_output4w_kernel<MODE_, NS_>), og6, dim3(64, 6), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, \
-                         relu, POOL_, BITS_)
-      if (mode == 0 && nsplit == 1) NFS_W4_OUT6(0, 1, ypool, out_bits);
-      else if (mode == 0) NFS_W4_OUT6(0, 2, ypool, out_bits);
-      else if (nsplit == 1) NFS_W4_OUT6(1, 1, (float*)nullptr, ib);
-      else NFS_W4_OUT6(1, 2, (float*)nullptr, ib);
-#undef NFS_W4_OUT6
-    } else
-    if (mode == 0 && nsplit == 1)
-      hipLaunchKernelGGL((winograd_output4_kernel<0, 1>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                         ypool, out_bits);
-    else if (mode == 0)
-      hipLaunchKernelGGL((winograd_output4_kernel<0, 2>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                         ypool, out_bits);
-    else if (nsplit == 1)
-      hipLaunchKernelGGL((winograd_output4_kernel<1, 1>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                         (float*)nullptr, ib);
-    else
-      hipLaunchKernelGGL((winograd_output4_kernel<1, 2>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                         (float*)nullptr, ib);
+    // forward: the pooled output and the mask of y; data gradient: the mask of x_in, only where the caller asks for one
+    float* const op = mode == 0 ? ypool : nullptr;
+    uint32_t* const ob_bits = mode == 0 ? out_bits : (aux0 ? in_bits : nullptr);
+    wg_with_mode_nsplit(mode, nsplit, [&](auto MODE, auto NSPLIT) {
+      if (out6)
+        hipLaunchKernelGGL((winograd_output4w_kernel<decltype(MODE)::value, decltype(NSPLIT)::value>), dim3((unsigned)(T * (N / 128))),
+                           dim3(64, 6), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu, op, ob_bits);
+      else
+        hipLaunchKernelGGL((winograd_output4_kernel<decltype(MODE)::value, decltype(NSPLIT)::value>), dim3(ob), dim3(256), 0, s, M,
+                           aux0, aux1, y, B, H, W, N, TH, TW, relu, op, ob_bits);
+    });
   } else {
     const unsigned ob = blocks_for(T * (N / 4), 256);
     if (mode == 0)

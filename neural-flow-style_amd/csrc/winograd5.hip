@@ -18,79 +18,13 @@
 // bit cache has its own layout here -- two words per (5 x 5 tile, channel pair): bit 2 p + c of the 64 = (x > 0) of pixel p,
 // channel c -- written by the forward input transform (whose thread holds exactly those 50 values), read by the data
 // gradient's output transform (same tiling, one 8-byte load per thread) instead of x_in.
+// The Cook-Toom passes (w5_bt, w5_at), the layer epilogue, the cache layout and the filter pack kernel are in
+// winograd_transform.h, shared by the one-thread-per-(tile, channel) kernels and the seven-wave ones below.
 #include "common.h"
 #include "winograd_gemm.h"
+#include "winograd_transform.h"
 
 namespace nfs {
-
-// G (7 x 3) = {-1/2,0,0} {-1/3,-1/3,-1/3} {1/9,-1/9,1/9} {1/36,1/18,1/9} {-1/60,1/30,-1/15} {32/45,16/45,8/45} {0,0,1}
-__device__ __forceinline__ void w5_g(const float g0, const float g1, const float g2, float* u) {
-  u[0] = -0.5f * g0;
-  u[1] = (-1.f / 3.f) * (g0 + g1 + g2);
-  u[2] = (1.f / 9.f) * (g0 - g1 + g2);
-  u[3] = (1.f / 36.f) * g0 + (1.f / 18.f) * g1 + (1.f / 9.f) * g2;
-  u[4] = (-1.f / 60.f) * g0 + (1.f / 30.f) * g1 - (1.f / 15.f) * g2;
-  u[5] = (32.f / 45.f) * g0 + (16.f / 45.f) * g1 + (8.f / 45.f) * g2;
-  u[6] = g2;
-}
-
-// U_z[ci][co] = (G g G^T)[z], z = 7 r + q, packed [49][K/32][N][32] (the layout of winograd_pack4_kernel); kind as there
-__global__ void __launch_bounds__(256) winograd5_pack_kernel(const float* __restrict__ w, float* __restrict__ up, int Ci,
-                                                             int Co, int kind) {
-  const int Kc = kind == 0 ? Ci : Co, Nc = kind == 0 ? Co : Ci;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (int64_t)Kc * Nc) return;
-  const int n = (int)(gid % Nc), k = (int)(gid / Nc);
-  float g[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      if (kind == 0) g[r][s] = w[((int64_t)(r * 3 + s) * Ci + k) * Co + n];
-      else g[r][s] = w[((int64_t)((2 - r) * 3 + (2 - s)) * Ci + n) * Co + k];
-    }
-  float t[7][3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    float u[7];
-    w5_g(g[0][s], g[1][s], g[2][s], u);
-#pragma unroll
-    for (int r = 0; r < 7; ++r) t[r][s] = u[r];
-  }
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {
-    float u[7];
-    w5_g(t[r][0], t[r][1], t[r][2], u);
-#pragma unroll
-    for (int q = 0; q < 7; ++q) up[(((int64_t)(r * 7 + q) * (Kc / 32) + k / 32) * Nc + n) * 32 + (k & 31)] = u[q];
-  }
-}
-
-// B^T (7 x 7) = {-2,4,5/2,-5,-1/2,1,0} {0,2,-2,-9/2,1/2,1,0} {0,-2,6,-7/2,-3/2,1,0} {0,1,-3/2,-2,3/2,1,0}
-//               {0,-1,5/2,0,-5/2,1,0} {0,4,0,-5,0,1,0} {0,-2,4,5/2,-5,-1/2,1}
-// A^T (5 x 7) = {1,1,1,1,1,1,0} {0,1,-1,2,-2,1/2,0} {0,1,1,4,4,1/4,0} {0,1,-1,8,-8,1/8,0} {0,1,1,16,16,1/16,1}
-// (written for one float; a thread owns ONE channel of a tile: the deep layers have few tiles -- 200 at 25 x 25 and 8 views --
-// and two channels per thread, as in the F(4x4) transforms, leave the chip with less than one wave per SIMD)
-// (no FMA contraction in the two transforms, as in wg4_bt / wg4_at: every kernel that inlines them rounds alike)
-__device__ __forceinline__ void w5_bt(const float* d, float* o) {
-#pragma clang fp contract(off)
-  o[0] = -2.f * d[0] + 4.f * d[1] + 2.5f * d[2] - 5.f * d[3] - 0.5f * d[4] + d[5];
-  o[1] = 2.f * d[1] - 2.f * d[2] - 4.5f * d[3] + 0.5f * d[4] + d[5];
-  o[2] = -2.f * d[1] + 6.f * d[2] - 3.5f * d[3] - 1.5f * d[4] + d[5];
-  o[3] = d[1] - 1.5f * d[2] - 2.f * d[3] + 1.5f * d[4] + d[5];
-  o[4] = -d[1] + 2.5f * d[2] - 2.5f * d[4] + d[5];
-  o[5] = 4.f * d[1] - 5.f * d[3] + d[5];
-  o[6] = -2.f * d[1] + 4.f * d[2] + 2.5f * d[3] - 5.f * d[4] - 0.5f * d[5] + d[6];
-}
-__device__ __forceinline__ void w5_at(const float* m, float* o) {
-#pragma clang fp contract(off)
-  const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-  o[0] = m[0] + s12 + s34 + m[5];
-  o[1] = d12 + 2.f * d34 + 0.5f * m[5];
-  o[2] = s12 + 4.f * s34 + 0.25f * m[5];
-  o[3] = d12 + 8.f * d34 + 0.125f * m[5];
-  o[4] = s12 + 16.f * s34 + 0.0625f * m[5] + m[6];
-}
 
 // input transform: one thread = one 7 x 7 patch x 1 channel (a wave covers 64 contiguous channels per pixel); a contiguous
 // range of tiles per XCD, as in winograd_input4_kernel.  bits (nullable): two words per (tile, channel PAIR) -- the mask of
@@ -99,13 +33,11 @@ __global__ void __launch_bounds__(256) winograd5_input_kernel(const float* __res
                                                               int H, int W, int K, int TH, int TW,
                                                               uint32_t* __restrict__ bits) {
   const int64_t T = (int64_t)B * TH * TW;
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  const int64_t gid = (int64_t)lb * blockDim.x + threadIdx.x;
+  const int64_t gid = (int64_t)wg_xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   if (gid >= T * K) return;
   const int c = (int)(gid % K);
   const int64_t tile = gid / K;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int y0 = 5 * ty - 1, x0 = 5 * tx - 1;
   // all 49 loads go out before anything waits: clamped addresses, the value outside the image dropped by a select
   // (a bounds test around a load is a branch, and hipcc drains vmcnt at the join: three dependent round trips before)
@@ -133,9 +65,7 @@ __global__ void __launch_bounds__(256) winograd5_input_kernel(const float* __res
     w5_bt(d, t[s]);
   }
   if (bits) {
-    const uint32_t lo = (uint32_t)mask, hi = (uint32_t)(mask >> 32);
-    const uint32_t plo = __shfl_xor(lo, 1, 64), phi = __shfl_xor(hi, 1, 64);       // the odd channel of the pair
-    if (!(c & 1)) *reinterpret_cast<uint2*>(bits + gid) = make_uint2(lo | (plo << 1), hi | (phi << 1));   // 2 * (gid / 2)
+    w5_bits_store(bits, gid, c, mask);
   }
   const int64_t comp_stride = T * K;
   float* vo = V + tile * K + c;
@@ -162,7 +92,7 @@ __global__ void __launch_bounds__(256) winograd5_output_kernel(const float* __re
   if (gid >= T * N) return;
   const int c = (int)(gid % N);
   const int64_t tile = gid / N;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int64_t comp_stride = T * N;
   const float* mi = M + tile * N + c;
   // data gradient: the 25 addend values are requested BEFORE the 49 components (clamped addresses, no branch around a
@@ -193,8 +123,7 @@ __global__ void __launch_bounds__(256) winograd5_output_kernel(const float* __re
   const float bias = (MODE == 0 && aux0) ? aux0[c] : 0.f;
   unsigned long long mask = 0ull;
   if (MODE == 1 && bits) {
-    const uint2 mw = *reinterpret_cast<const uint2*>(bits + (gid & ~(int64_t)1));
-    mask = (((unsigned long long)mw.y << 32) | mw.x) >> (c & 1);
+    mask = w5_bits_mask(*w5_bits_at(bits, gid), c);
   }
 #pragma unroll
   for (int a = 0; a < 5; ++a) {
@@ -209,16 +138,7 @@ __global__ void __launch_bounds__(256) winograd5_output_kernel(const float* __re
       if (xx >= W) continue;
       float v = o[cc];
       const int64_t idx = (((int64_t)b * H + yy) * W + xx) * N + c;
-      if (MODE == 0) {
-        v += bias;
-        if (relu) v = fmaxf(v, 0.f);
-      } else {
-        const float adv = aux1 ? ad[a][cc] : 0.f;
-        if (relu) v += adv;                      // addend not yet through the mask: add first
-        if (bits) v = ((mask >> (2 * (a * 5 + cc))) & 1ull) ? v : 0.f;
-        else if (aux0) v = aux0[idx] > 0.f ? v : 0.f;
-        if (!relu) v += adv;
-      }
+      NFS_WG_EPILOGUE(MODE, float, 0.f, v, bias, relu, aux1, ad[a][cc], bits, (bool)((mask >> w5_bit_shift(a, cc)) & 1ull), aux0, idx);
       y[idx] = v;
     }
   }
@@ -235,13 +155,12 @@ __global__ void __launch_bounds__(448) winograd5_input7_kernel(const float* __re
   __shared__ float tl[7][7][64];                 // [column s][row r][channel lane] after the vertical pass
   __shared__ unsigned long long mk[5][64];       // the mask bits of patch columns 1..5
   const int64_t T = (int64_t)B * TH * TW;
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;       // a contiguous range of tiles per XCD
+  const unsigned lb = wg_xcd_block(blockIdx.x, gridDim.x);
   const int kg = K / 64;
   if ((int64_t)lb >= T * kg) return;
   const int64_t tile = lb / kg;
   const int lane = threadIdx.x, w = threadIdx.y, c = (int)(lb % kg) * 64 + lane;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int y0 = 5 * ty - 1, x0 = 5 * tx - 1;
   {
     const int xx = x0 + w, xc = min(max(xx, 0), W - 1);
@@ -268,9 +187,7 @@ __global__ void __launch_bounds__(448) winograd5_input7_kernel(const float* __re
   const int64_t gid = tile * K + c;
   if (bits && w == 6) {
     const unsigned long long mask = mk[0][lane] | mk[1][lane] | mk[2][lane] | mk[3][lane] | mk[4][lane];
-    const uint32_t lo = (uint32_t)mask, hi = (uint32_t)(mask >> 32);
-    const uint32_t plo = __shfl_xor(lo, 1, 64), phi = __shfl_xor(hi, 1, 64);
-    if (!(c & 1)) *reinterpret_cast<uint2*>(bits + gid) = make_uint2(lo | (plo << 1), hi | (phi << 1));
+    w5_bits_store(bits, gid, c, mask);
   }
   const float row[7] = {tl[0][w][lane], tl[1][w][lane], tl[2][w][lane], tl[3][w][lane], tl[4][w][lane], tl[5][w][lane], tl[6][w][lane]};
   float o[7];
@@ -291,7 +208,7 @@ __global__ void __launch_bounds__(448) winograd5_output7_kernel(const float* __r
   const int ng = N / 64;
   const int64_t tile = blockIdx.x / ng;
   const int lane = threadIdx.x, w = threadIdx.y, c = (int)(blockIdx.x % ng) * 64 + lane;
-  const int tx = (int)(tile % TW), ty = (int)((tile / TW) % TH), b = (int)(tile / ((int64_t)TW * TH));
+  NFS_WG_TILE(tile, TH, TW);
   const int64_t comp_stride = T * N, gid = tile * N + c;
   // the operands of the second pass go out first (row a = min(w, 4) of the addend: no branch around a load)
   const int a = min(w, 4), yy = 5 * ty + a;
@@ -302,7 +219,7 @@ __global__ void __launch_bounds__(448) winograd5_output7_kernel(const float* __r
     const int yc = min(yy, H - 1);
 #pragma unroll
     for (int cc = 0; cc < 5; ++cc) ad[cc] = ap[(((int64_t)b * H + yc) * W + min(5 * tx + cc, W - 1)) * N + c];
-    if (bits) mw = *reinterpret_cast<const uint2*>(bits + (gid & ~(int64_t)1));
+    if (bits) mw = *w5_bits_at(bits, gid);
   }
   {
     const float* mi = M + gid + (int64_t)w * comp_stride;         // column s = w: components 7 r + s
@@ -324,23 +241,14 @@ __global__ void __launch_bounds__(448) winograd5_output7_kernel(const float* __r
   float o[5];
   w5_at(row, o);
   const float bias = (MODE == 0 && aux0) ? aux0[c] : 0.f;
-  const unsigned long long mask = ((((unsigned long long)mw.y << 32) | mw.x) >> (c & 1)) >> (2 * (a * 5));
+  const unsigned long long mask = w5_bits_mask(mw, c) >> w5_bit_shift(a, 0);
 #pragma unroll
   for (int cc = 0; cc < 5; ++cc) {
     const int xx = 5 * tx + cc;
     if (xx >= W) continue;
     float v = o[cc];
     const int64_t idx = (((int64_t)b * H + yy) * W + xx) * N + c;
-    if (MODE == 0) {
-      v += bias;
-      if (relu) v = fmaxf(v, 0.f);
-    } else {
-      const float adv = aux1 ? ad[cc] : 0.f;
-      if (relu) v += adv;
-      if (bits) v = ((mask >> (2 * cc)) & 1ull) ? v : 0.f;
-      else if (aux0) v = aux0[idx] > 0.f ? v : 0.f;
-      if (!relu) v += adv;
-    }
+    NFS_WG_EPILOGUE(MODE, float, 0.f, v, bias, relu, aux1, ad[cc], bits, (bool)((mask >> w5_bit_shift(0, cc)) & 1ull), aux0, idx);
     y[idx] = v;
   }
 }
@@ -371,7 +279,7 @@ int64_t winograd5_workspace_floats(int B, int H, int W, int K, int N) {
 int winograd5_pack(const float* w_hwio, float* up5, int Ci, int Co, int kind, hipStream_t s) {
   const int64_t n = (int64_t)Ci * Co;
   const int Kc = kind == 0 ? Ci : Co, Nc = kind == 0 ? Co : Ci;
-  hipLaunchKernelGGL(winograd5_pack_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, w_hwio, up5, Ci, Co, kind);
+  hipLaunchKernelGGL(winograd_pack_tile_kernel<7>, dim3(blocks_for(n, 256)), dim3(256), 0, s, w_hwio, up5, Ci, Co, kind);
   winograd_pack_frag16(up5, up5 + 49 * n, Kc, Nc, 49 * n, s);
   winograd_pack_limbs16(up5 + 49 * n, up5 + 98 * n, Kc, Nc, 49, s);
   return check_launch("winograd5_pack");
@@ -406,29 +314,15 @@ int winograd5_conv(const float* x, const float* U5, const float* aux0, const flo
     set_error("winograd5_conv: unsupported number of K parts");
     return NFS_EINVAL;
   }
-  const uint32_t* ib = aux0 ? in_bits : nullptr;
-  if (T * N <= waves7_max) {
-    const dim3 og((unsigned)(T * (N / 64)));
-#define NFS_W5_OUT7(MODE_, NS_, BITS_)                                                                                \
-    hipLaunchKernelGGL((winograd5_output7_kernel<MODE_, NS_>), og, dim3(64, 7), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW,  \
-                       relu, BITS_)
-    if (mode == 0 && nsplit == 1) NFS_W5_OUT7(0, 1, (const uint32_t*)nullptr);
-    else if (mode == 0) NFS_W5_OUT7(0, 2, (const uint32_t*)nullptr);
-    else if (nsplit == 1) NFS_W5_OUT7(1, 1, ib);
-    else NFS_W5_OUT7(1, 2, ib);
-#undef NFS_W5_OUT7
-    return check_launch("winograd5_conv");
-  }
-  if (mode == 0 && nsplit == 1)
-    hipLaunchKernelGGL((winograd5_output_kernel<0, 1>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                       (const uint32_t*)nullptr);
-  else if (mode == 0)
-    hipLaunchKernelGGL((winograd5_output_kernel<0, 2>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu,
-                       (const uint32_t*)nullptr);
-  else if (nsplit == 1)
-    hipLaunchKernelGGL((winograd5_output_kernel<1, 1>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu, ib);
-  else
-    hipLaunchKernelGGL((winograd5_output_kernel<1, 2>), dim3(ob), dim3(256), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu, ib);
+  const uint32_t* ib = (mode != 0 && aux0) ? in_bits : nullptr;         // a mask only where the caller asks for one
+  wg_with_mode_nsplit(mode, nsplit, [&](auto MODE, auto NSPLIT) {
+    if (T * N <= waves7_max)
+      hipLaunchKernelGGL((winograd5_output7_kernel<decltype(MODE)::value, decltype(NSPLIT)::value>), dim3((unsigned)(T * (N / 64))),
+                         dim3(64, 7), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu, ib);
+    else
+      hipLaunchKernelGGL((winograd5_output_kernel<decltype(MODE)::value, decltype(NSPLIT)::value>), dim3(ob), dim3(256), 0, s, M,
+                         aux0, aux1, y, B, H, W, N, TH, TW, relu, ib);
+  });
   return check_launch("winograd5_conv");
 }
 

@@ -50,7 +50,7 @@ struct WfArgs {
   int dbg = 0;                          // NFS_FUSED_DBG timing ablations
 };
 
-// filters: U [36][K/32][N][32] (winograd_pack4_kernel) -> Uf [K/16][2][18][N/16][64 lanes][zl 2][s 2]; lane (g = l>>4,
+// filters: U [36][K/32][N][32] (winograd_pack_tile_kernel<6>) -> Uf [K/16][2][18][N/16][64 lanes][zl 2][s 2]; lane (g = l>>4,
 // c = l&15), element (zl, s) = U_z[k = 16 j + 4 g + 2 hh + s][n = 16 w + c], z = 2 zp + zl: the B operands of one
 // wave's four MFMAs for the component pair zp and half hh of k-slice j in one float4
 __global__ void __launch_bounds__(256) winograd_pack_fused_kernel(const float* __restrict__ up, float* __restrict__ uf,

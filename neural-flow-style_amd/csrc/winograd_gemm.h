@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+#include <type_traits>
+
 namespace nfs {
 
 // Batched C_z = alpha_z * A_z B_z (optionally masked): the Winograd GEMMs (z = transform component) and the
@@ -39,5 +41,17 @@ int winograd_ksplit(int64_t T, int K);
 void winograd_pack_frag16(const float* up, float* uq, int K, int N, int64_t total, hipStream_t s);
 // Uq16 [Z][N/16][K/16][64][4] floats -> the limb planes [Z][N/16][K/32][3][64][8 bf16] (1.5 x the floats); Z K N / 8 threads
 void winograd_pack_limbs16(const float* uq16, float* ub16, int K, int N, int Z, hipStream_t s);
+
+// Run-time (mode, nsplit) of an output transform -> its compile-time <MODE, NSPLIT>: calls f(MODE, NSPLIT) with two
+// std::integral_constant<int, .> (a generic lambda that launches kernel<decltype(MODE)::value, decltype(NSPLIT)::value>).
+// mode 0 forward, anything else the data gradient; nsplit 1 or 2 (the callers refuse any other number of K parts).
+template <typename F>
+inline void wg_with_mode_nsplit(int mode, int nsplit, F f) {
+  using std::integral_constant;
+  if (mode == 0 && nsplit == 1) f(integral_constant<int, 0>{}, integral_constant<int, 1>{});
+  else if (mode == 0) f(integral_constant<int, 0>{}, integral_constant<int, 2>{});
+  else if (nsplit == 1) f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+  else f(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+}
 
 }  // namespace nfs

@@ -941,6 +941,67 @@ def test_transforms_of_few_and_of_many_tiles_agree(ops, H, W, Ci, Co):
             assert float((a - c).abs().max()) <= 1e-4 * float(a.abs().max())
 
 
+def test_the_two_transform_schedules_agree_bit_for_bit_at_equal_batch(tmp_path):
+    """the two schedules of a transform family (six / seven waves per tile, one thread per tile and
+    channel[-pair]) give identical results.  The same layers at the same batch in two processes (the thresholds are read
+    once per process): default thresholds, under which these sizes take the wave schedules, and both thresholds 0, the
+    thread schedules.  NFS_GEMM_TUNE=0: the GEMM between the transforms is then a function of the shape alone.  F(4x4)
+    with two K parts, F(4x4) ragged plain and pooled, F(5x5) ragged: forward output, pooled output, data gradient from the
+    bit cache with an addend, and the cache words themselves -- all equal bit for bit."""
+    import subprocess, sys, os
+    code = (
+        "import sys, numpy as np, torch\n"
+        "import neural_flow_style_amd.ops as ops\n"
+        "from neural_flow_style_amd import _lib\n"
+        "outs = {}\n"
+        "def keep(k, t): outs[k] = t.cpu().numpy().view(np.uint32)\n"
+        "for B, H, W, Ci, Co in ((1, 12, 12, 512, 512), (2, 13, 11, 256, 256), (2, 9, 14, 128, 256)):\n"
+        "    T4, T5 = B * ((H + 3) // 4) * ((W + 3) // 4), B * ((H + 4) // 5) * ((W + 4) // 5)\n"
+        "    f5 = (H, W) == (9, 14)                       # the family, from the products the call executes\n"
+        "    for K, N in ((Ci, Co), (Co, Ci)):\n"
+        "        fl = _lib.lib().nfs_conv3x3_executed_flops(B, H, W, K, N, 0)\n"
+        "        assert fl == 2.0 * (49 * T5 if f5 else 36 * T4) * K * N and 36 * T4 != 49 * T5, (H, W, K, N, fl)\n"
+        "        assert (T5 if f5 else T4) * K <= 65536       # few enough items for the wave schedules by default\n"
+        "    if (H, W) == (13, 11):                       # the pooled entry points stay on F(4x4)\n"
+        "        for K, N in ((Ci, Co), (Co, Ci)):\n"
+        "            assert _lib.lib().nfs_conv3x3_executed_flops(B, H, W, K, N, 1) == 2.0 * 36 * T4 * K * N\n"
+        "    # K parts, from the workspace: V [36][T][K] and one M [36][T][N] per part (two at 9 rows and K = 512)\n"
+        "    parts = 2 if (H, W) == (12, 12) else 1\n"
+        "    if not f5:\n"
+        "        n = max(Ci, Co)                         # (the query sizes for the larger channel count both ways)\n"
+        "        assert _lib.lib().nfs_conv3x3_workspace_floats(B, H, W, Ci, Co) == 36 * T4 * (n + parts * n), (H, W)\n"
+        "    rng = np.random.RandomState(H * W + Ci)\n"
+        "    cu = lambda a: torch.tensor(np.ascontiguousarray(a, dtype=np.float32), device='cuda')\n"
+        "    x = cu(np.maximum(rng.randn(B, H, W, Ci), 0))\n"
+        "    w, b = cu(rng.randn(3, 3, Ci, Co) * 0.05), cu(rng.randn(Co) * 0.1)\n"
+        "    gy, add = cu(rng.randn(B, H, W, Co)), cu(rng.randn(B, H, W, Ci))\n"
+        "    wf, wd = ops.conv3x3_pack(w, 0), ops.conv3x3_pack(w, 1)\n"
+        "    tag = '%dx%dx%d_' % (H, W, Ci)\n"
+        "    rb = ops.conv3x3_relu_bits(B, H, W, Ci, Co, False, x.device); rb.zero_()\n"
+        "    keep(tag + 'y', ops.conv3x3_fwd(x, wf, b, Co, True, relu_bits=rb))\n"
+        "    keep(tag + 'g', ops.conv3x3_dgrad(gy, wd, Ci, x_in=x, addend=add, relu_bits=rb))\n"
+        "    keep(tag + 'words', rb)\n"
+        "    if (H, W) == (13, 11):\n"
+        "        rbp = ops.conv3x3_relu_bits(B, H, W, Ci, Co, True, x.device); rbp.zero_()\n"
+        "        yp, p = ops.conv3x3_fwd_pool(x, wf, b, Co, True, relu_bits=rbp)\n"
+        "        gp = cu(rng.randn(B, H // 2, W // 2, Co))\n"
+        "        keep(tag + 'pool_y', yp); keep(tag + 'pool_p', p); keep(tag + 'pool_words', rbp)\n"
+        "        keep(tag + 'pool_g', ops.conv3x3_dgrad_pool(gp, None, wd, Ci, x_in=x, addend=add, relu_bits=rbp, hw=(H, W)))\n"
+        "torch.cuda.synchronize()\n"
+        "np.savez(sys.argv[1], **outs)\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = []
+    for tag, env in (("waves", {}), ("threads", {"NFS_W4_WAVES6_MAX": "0", "NFS_W5_WAVES7_MAX": "0"})):
+        out = str(tmp_path / (tag + ".npz"))
+        e = {k: v for k, v in os.environ.items() if k not in ("NFS_W4_WAVES6_MAX", "NFS_W5_WAVES7_MAX")}
+        e.update(env, NFS_GEMM_TUNE="0", PYTHONPATH=root)
+        subprocess.run([sys.executable, "-c", code, out], check=True, env=e, cwd=root, timeout=600)
+        res.append(np.load(out))
+    assert len(res[0].files) == 13 and sorted(res[0].files) == sorted(res[1].files)
+    for k in res[0].files:
+        assert np.array_equal(res[0][k], res[1][k]), k
+
+
 @pytest.mark.parametrize("shape", [(2, 18, 22, 64, 128), (2, 20, 24, 64, 128)])     # three-kernel / single-kernel path
 def test_pooled_layer_without_full_resolution_output(ops, shape):
     """with the bit cache a pooled layer need not write its full-resolution output: forward (pool only) and data
