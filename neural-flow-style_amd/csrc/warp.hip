@@ -3,7 +3,7 @@
 // stores and near-coalesced gathers; coordinates are generated in registers (the
 // reference materialises 3 coordinate volumes + 8 index/weight/gather tensors).
 // HBM-bound: algorithmic bytes = read volume once + write output once.
-#include "common.h"
+#include "source_ops.h"
 #include <stdlib.h>
 
 namespace nfs {
@@ -162,8 +162,6 @@ __device__ __forceinline__ bool corners_differ(const F2u (&p)[4]) {
   return !(p[0].y == a && p[1].x == a && p[1].y == a && p[2].x == a && p[2].y == a && p[3].x == a && p[3].y == a);
 }
 
-struct __attribute__((packed, aligned(4))) F3u { float x, y, z; };
-
 // ---- the lean stencil (advect1_kernel, transport_step_kernel), every piece of it written once ---------------------
 // per-volume constants: (n-1)/2 per axis (velocity -> voxels), n-1 per axis (the clamp), row and plane strides
 struct LeanDims { float hz, hy, hx, nz1, ny1, nx1; unsigned uW, uHW; };
@@ -253,62 +251,6 @@ __device__ __forceinline__ void lane_start(int first, int n, int H, int W, int& 
   h = t2 % H; z = t2 / H;
 }
 
-
-// Stream velocity of voxel (z, h, w): the channel-reversed curl of a stream function s [D,H,W,3] (curl_fwd_kernel,
-// warp2d.hip: forward differences, last slice replicated), vel_k along array axis k:
-//   vel0 = D_W s1 - D_H s0,  vel1 = D_D s0 - D_W s2,  vel2 = D_H s2 - D_D s1
-// -- differences and one subtraction each, nothing to contract: the bits of nfs_curl_fwd's output, channels reversed.
-// The voxel's own 12-byte vector is one end of all three differences (the lower end, or the upper one on the last slice of
-// an axis): one further vector per axis, the two components that axis differentiates (x: s1 s2 and z: s0 s1 as one 8-byte
-// load).  The x neighbour is the next lane's own vector, the y and z neighbours are re-reads of the next row / plane.
-__device__ __forceinline__ F3u stream_velocity(const float* __restrict__ s, int z, int h, int w, int D, int H, int W) {
-  const size_t own = ((size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w) * 3;
-  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
-  const size_t sx = 3, sy = (size_t)W * 3, sz = (size_t)H * W * 3;
-  const F3u p = *reinterpret_cast<const F3u*>(s + own);
-  const F2u qx = *reinterpret_cast<const F2u*>(s + (fx ? own + sx : own - sx) + 1);   // s1, s2
-  const F3u qy = *reinterpret_cast<const F3u*>(s + (fy ? own + sy : own - sy));       // s0, (s1), s2
-  const F2u qz = *reinterpret_cast<const F2u*>(s + (fz ? own + sz : own - sz));       // s0, s1
-  const float dw1 = fx ? qx.x - p.y : p.y - qx.x, dw2 = fx ? qx.y - p.z : p.z - qx.y;
-  const float dh0 = fy ? qy.x - p.x : p.x - qy.x, dh2 = fy ? qy.z - p.z : p.z - qy.z;
-  const float dd0 = fz ? qz.x - p.x : p.x - qz.x, dd1 = fz ? qz.y - p.y : p.y - qz.y;
-  return F3u{dw1 - dh0, dd0 - dw2, dh2 - dd1};
-}
-
-// Potential velocity of voxel (z, h, w): forward differences of a potential phi [D,H,W] (grad_fwd_kernel, warp2d.hip, its
-// channels reversed), vel_k along array axis k:
-//   vel0 = D_D phi,  vel1 = D_H phi,  vel2 = D_W phi
-// -- the voxel's own phi and one neighbour per axis: the upper one, or the lower one on the last slice of the axis.
-__device__ __forceinline__ F3u potential_velocity(const float* __restrict__ phi, int z, int h, int w, int D, int H, int W) {
-  const size_t own = (size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w;
-  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
-  const size_t sy = (size_t)W, sz = (size_t)H * W;
-  const float p = phi[own];
-  const float qx = phi[fx ? own + 1 : own - 1], qy = phi[fy ? own + sy : own - sy], qz = phi[fz ? own + sz : own - sz];
-  return F3u{fz ? qz - p : p - qz, fy ? qy - p : p - qy, fx ? qx - p : p - qx};
-}
-
-// Helmholtz velocity of voxel (z, h, w): a [D,H,W,4] = (psi0, psi1, psi2, phi), one 16-byte vector per voxel;
-//   vel_k = fl(stream_velocity(psi)_k + potential_velocity(phi)_k)
-// -- each summand formed exactly as in its own function, then added once (differences and sums only: nothing to contract).
-// The voxel's own vector and one neighbour's per axis, four 16-byte vectors (of which the compiler loads only the components
-// used), hold every difference both parts need.  a is 16-byte aligned (the entry points check).
-__device__ __forceinline__ F3u helmholtz_velocity(const float* __restrict__ a, int z, int h, int w, int D, int H, int W) {
-  const size_t own = (size_t)(unsigned)(z * H + h) * (unsigned)W + (unsigned)w;
-  const bool fx = fd_lo(w, W) == w, fy = fd_lo(h, H) == h, fz = fd_lo(z, D) == z;   // own sample is the lower end
-  const size_t sy = (size_t)W, sz = (size_t)H * W;
-  const float4* a4 = reinterpret_cast<const float4*>(a);
-  const float4 p = a4[own], qx = a4[fx ? own + 1 : own - 1], qy = a4[fy ? own + sy : own - sy],
-               qz = a4[fz ? own + sz : own - sz];
-  const float dw1 = fx ? qx.y - p.y : p.y - qx.y, dw2 = fx ? qx.z - p.z : p.z - qx.z, dw3 = fx ? qx.w - p.w : p.w - qx.w;
-  const float dh0 = fy ? qy.x - p.x : p.x - qy.x, dh2 = fy ? qy.z - p.z : p.z - qy.z, dh3 = fy ? qy.w - p.w : p.w - qy.w;
-  const float dd0 = fz ? qz.x - p.x : p.x - qz.x, dd1 = fz ? qz.y - p.y : p.y - qz.y, dd3 = fz ? qz.w - p.w : p.w - qz.w;
-  return F3u{(dw1 - dh0) + dd3, (dd0 - dw2) + dh3, (dh2 - dd1) + dw3};
-}
-
-// where advect1_kernel's velocity comes from: the stored field, or one of the three variables it is a function of
-enum { SRC_VEL = 0, SRC_STREAM = 1, SRC_POTENTIAL = 2, SRC_HELMHOLTZ = 3 };
-
 // MODE 0: forward; 1: velocity gradient -> out; 2: velocity gradient consumed on the spot by the TF-Adam update of
 // the velocity itself (vel, m, v updated in place: every thread reads and writes only its own 4 voxels of them;
 // the 96 MB gradient never goes to HBM)
@@ -316,8 +258,8 @@ enum { SRC_VEL = 0, SRC_STREAM = 1, SRC_POTENTIAL = 2, SRC_HELMHOLTZ = 3 };
 // planes, d is the WHOLE density (the back-traced points leave the slab); zoff = 0, Dfull = D is the whole volume.
 // EVER (MODE 2 + LIVE, volumes below 2^31 / 12 voxels): ad.ever is set and the streamed accesses are predicated per lane
 // SRC (other than SRC_VEL: MODE 0 / 1, whole volumes): vel is a stream function [D,H,W,3], a potential [D,H,W] or a
-// Helmholtz variable [D,H,W,4] and the velocity is stream_velocity() / potential_velocity() / helmholtz_velocity() of it,
-// formed in registers and never stored; everything after the fetch is the same code
+// Helmholtz variable [D,H,W,4] and the velocity is source_velocity<SRC>() of it (source_ops.h), formed in registers and never
+// stored; everything after the fetch is the same code
 template <int MODE, bool LIVE = false, bool EVER = false, int SRC = SRC_VEL>   // LIVE: ad.live is set (a compile-time switch: the mask code out of the plain kernels)
 __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ d, const float* vel,
                                                       const float* __restrict__ g_out, float* out,
@@ -388,9 +330,7 @@ __global__ void __launch_bounds__(256) advect1_kernel(const float* __restrict__ 
     const int ic = ok[j] ? idx : n - 1;
     if constexpr (SRC != SRC_VEL) {
       static_assert(SRC == SRC_VEL || MODE != 2, "the updates are nfs_stream_bwd_adam / nfs_potential_bwd_adam / nfs_helmholtz_bwd_adam");
-      if constexpr (SRC == SRC_STREAM) vv[j] = stream_velocity(vel, zs, hs, ws, D, H, W);
-      else if constexpr (SRC == SRC_POTENTIAL) vv[j] = potential_velocity(vel, zs, hs, ws, D, H, W);
-      else vv[j] = helmholtz_velocity(vel, zs, hs, ws, D, H, W);
+      vv[j] = source_velocity<SRC>(vel, (size_t)(unsigned)(zs * H + hs) * (unsigned)W + (unsigned)ws, zs, hs, ws, D, H, W);
       if (BWD) gg[j] = g_out[ic];
       walk64(ws, hs, zs, W, H, D - 1);
       continue;
@@ -1594,44 +1534,37 @@ int nfs_advect_bwd(const float* d, const float* vel, const float* g_out, float* 
   return check_launch("nfs_advect_bwd");
 }
 
-// advect along the stream velocity of s (stream_velocity(): the channel-reversed curl), the velocity never stored; live
-// (nullable): the mask nfs_advect_fwd_live writes.  Bit-identical to nfs_advect_fwd / _live on the stored velocity.
-int nfs_advect_stream_fwd(const float* d, const float* s, float* out, unsigned long long* live, int D, int H, int W,
-                          nfs_stream_t stream) {
-  NFS_REQUIRE(d && s && out, "nfs_advect_stream_fwd: null pointer");
-  NFS_REQUIRE(out != d && out != s, "nfs_advect_stream_fwd: out must not alias d or s");
-  AdamFused ad{};
-  ad.live = live;
-  return advect1_launch("nfs_advect_stream_fwd", 0, d, s, nullptr, out, D, H, W, 0, D, ad, stream, SRC_STREAM);
-}
-
-// ... and its velocity gradient g_vel [D,H,W,3] (advect's channel order), the velocity recomputed from s
-int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, float* g_vel, int D, int H, int W,
-                          nfs_stream_t stream) {
-  NFS_REQUIRE(d && s && g_out && g_vel, "nfs_advect_stream_bwd: null pointer");
-  NFS_REQUIRE(g_vel != d && g_vel != s && g_vel != g_out, "nfs_advect_stream_bwd: g_vel must not alias d, s or g_out");
-  return advect1_launch("nfs_advect_stream_bwd", 1, d, s, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, SRC_STREAM);
-}
-
-// the same pair along the potential velocity of phi [D,H,W] (potential_velocity()) and along the Helmholtz velocity of
-// a [D,H,W,4] (helmholtz_velocity()): bit-identical to nfs_grad_fwd (reversed; for a: + nfs_curl_fwd reversed, added once)
-// followed by nfs_advect_fwd / _live / nfs_advect_bwd (g_vel only)
+// advect along the velocity a variable stands for (source_velocity<SRC>(), source_ops.h: s [D,H,W,3], phi [D,H,W] or
+// a [D,H,W,4]), the velocity never stored; live (nullable): the mask nfs_advect_fwd_live writes.  Bit-identical to
+// nfs_curl_fwd / nfs_grad_fwd (reversed; for a: both, added once) followed by nfs_advect_fwd / _live on the stored velocity
 static int advect_from_fwd(const char* who, int src, const float* d, const float* var, float* out, unsigned long long* live,
                            int D, int H, int W, nfs_stream_t stream) {
   NFS_REQUIRE(d && var && out, "%s: null pointer", who);
-  NFS_REQUIRE(out != d && out != var, "%s: out must not alias d or the variable", who);
+  NFS_REQUIRE(out != d && out != var, "%s: out must not alias d or %s", who, source_name(src));
   NFS_REQUIRE(src != SRC_HELMHOLTZ || aligned16(var), "%s: the Helmholtz variable must be 16-byte aligned", who);
   AdamFused ad{};
   ad.live = live;
   return advect1_launch(who, 0, d, var, nullptr, out, D, H, W, 0, D, ad, stream, src);
 }
 
+// ... and its velocity gradient g_vel [D,H,W,3] (advect's channel order), the velocity recomputed from the variable:
+// bit-identical to nfs_advect_bwd (g_vel only) on the stored velocity
 static int advect_from_bwd(const char* who, int src, const float* d, const float* var, const float* g_out, float* g_vel,
                            int D, int H, int W, nfs_stream_t stream) {
   NFS_REQUIRE(d && var && g_out && g_vel, "%s: null pointer", who);
-  NFS_REQUIRE(g_vel != d && g_vel != var && g_vel != g_out, "%s: g_vel must not alias d, the variable or g_out", who);
+  NFS_REQUIRE(g_vel != d && g_vel != var && g_vel != g_out, "%s: g_vel must not alias d, %s or g_out", who, source_name(src));
   NFS_REQUIRE(src != SRC_HELMHOLTZ || aligned16(var), "%s: the Helmholtz variable must be 16-byte aligned", who);
   return advect1_launch(who, 1, d, var, g_out, g_vel, D, H, W, 0, D, AdamFused{}, stream, src);
+}
+
+int nfs_advect_stream_fwd(const float* d, const float* s, float* out, unsigned long long* live, int D, int H, int W,
+                          nfs_stream_t stream) {
+  return advect_from_fwd("nfs_advect_stream_fwd", SRC_STREAM, d, s, out, live, D, H, W, stream);
+}
+
+int nfs_advect_stream_bwd(const float* d, const float* s, const float* g_out, float* g_vel, int D, int H, int W,
+                          nfs_stream_t stream) {
+  return advect_from_bwd("nfs_advect_stream_bwd", SRC_STREAM, d, s, g_out, g_vel, D, H, W, stream);
 }
 
 int nfs_advect_potential_fwd(const float* d, const float* phi, float* out, unsigned long long* live, int D, int H, int W,

@@ -1,9 +1,8 @@
-// 2-D twins of the resampling family and the remaining TNST grid operators:
+// 2-D twins of the resampling family and the remaining TNST grid operators (the curl and the gradient: source.hip):
 //   batch_warp2d / _interpolate2d      transform.py:206-236, 280-341   (A2, 2-D; pins the reference's only KAT)
 //   advect, 2-D branch, order 1        transform.py:583-588            (A11, 2-D)
 //   advect order 2 (MacCormack)        transform.py:570-582 / 590-607  (the reference's clamp is broken
 //                                      -- tf.to_int32 of [-1,1] coordinates, d_max[grids] -- here done as intended)
-//   curl of a stream function          transform.py:517-555            (SURVEY 8(f)-4), forward and adjoint
 // Images are small (128^2 ... 512 x 1024) next to the volumes: one thread per output element, exact reference stencil
 // (x0 = floor, x1 = x0 + 1, both clipped to [0, n-1], weight dx = x - float(clipped x0)).
 #include "common.h"
@@ -157,186 +156,6 @@ __global__ void __launch_bounds__(256) maccormack_kernel(const float* __restrict
   }
 }
 
-// ---- curl of a stream function (forward differences, last slice replicated; transform.py:517-555) ------------------
-// 2-D: s [H,W] -> [H,W,2]: u = ds/dy (axis 0), v = -ds/dx (axis 1).  3-D: s [D,H,W,3] -> [D,H,W,3]:
-//   u = dw/dy - dv/dz, v = du/dz - dw/dx, w = dv/dx - du/dy   with x = axis W, y = axis H, z = axis D.
-__global__ void __launch_bounds__(256) curl_fwd_kernel(const float* __restrict__ s, float* __restrict__ out, int D, int H,
-                                                       int W, int nd) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  const int xl = fd_lo(x, W), yl = fd_lo(y, H), zl = fd_lo(z, D);
-  const int dxs = W >= 2, dys = H >= 2, dzs = D >= 2;
-  if (nd == 2) {
-    // u = s[y+1,x] - s[y,x] at row yl;  v = s[y,x] - s[y,x+1] at column xl
-    const float u = dys ? s[(int64_t)(yl + 1) * W + x] - s[(int64_t)yl * W + x] : 0.f;
-    const float v = dxs ? s[(int64_t)y * W + xl] - s[(int64_t)y * W + xl + 1] : 0.f;
-    out[vox * 2] = u;
-    out[vox * 2 + 1] = v;
-    return;
-  }
-  auto at = [&](int zz, int yy, int xx, int c) { return s[(((int64_t)zz * H + yy) * W + xx) * 3 + c]; };
-  const float dvdx = dxs ? at(z, y, xl + 1, 1) - at(z, y, xl, 1) : 0.f, dwdx = dxs ? at(z, y, xl + 1, 2) - at(z, y, xl, 2) : 0.f;
-  const float dudy = dys ? at(z, yl + 1, x, 0) - at(z, yl, x, 0) : 0.f, dwdy = dys ? at(z, yl + 1, x, 2) - at(z, yl, x, 2) : 0.f;
-  const float dudz = dzs ? at(zl + 1, y, x, 0) - at(zl, y, x, 0) : 0.f, dvdz = dzs ? at(zl + 1, y, x, 1) - at(zl, y, x, 1) : 0.f;
-  out[vox * 3] = dwdy - dvdz;
-  out[vox * 3 + 1] = dudz - dwdx;
-  out[vox * 3 + 2] = dvdx - dudy;
-}
-
-// adjoint: g_s = curl^T g.  A forward difference taken at cell l = fd_lo(i) contributes +g to s[l+1] and -g to s[l];
-// cell i receives from the outputs whose l equals i (outputs i, and n-1 as well when i == n-2) and whose l+1 equals i.
-// Written as a gather over the (at most three) contributing outputs per axis: no atomics, deterministic.
-__device__ __forceinline__ float fd_adj(const float* __restrict__ g, int64_t base, int64_t stride, int i, int n, int ch,
-                                        int nch) {
-  // sum over outputs o along this axis: coefficient of s[i] in (s[lo(o)+1] - s[lo(o)])
-  if (n < 2) return 0.f;
-  float r = 0.f;
-  if (i >= 1) {                       // s[i] is the upper sample of outputs with lo == i-1
-    r += g[(base + (int64_t)(i - 1) * stride) * nch + ch];
-    if (i == n - 1) r += g[(base + (int64_t)(n - 1) * stride) * nch + ch];   // replicated last slice (lo = n-2)
-  }
-  if (i <= n - 2) {                   // s[i] is the lower sample of outputs with lo == i
-    r -= g[(base + (int64_t)i * stride) * nch + ch];
-    if (i == n - 2) r -= g[(base + (int64_t)(n - 1) * stride) * nch + ch];
-  }
-  return r;
-}
-
-__global__ void __launch_bounds__(256) curl_bwd_kernel(const float* __restrict__ g, float* __restrict__ gs, int D, int H,
-                                                       int W, int nd) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  const int64_t bx = (int64_t)z * H * W + (int64_t)y * W;     // base with x = 0, stride 1
-  const int64_t by = (int64_t)z * H * W + x;                  // base with y = 0, stride W
-  const int64_t bz = (int64_t)y * W + x;                      // base with z = 0, stride H*W
-  if (nd == 2) {
-    // u = +d/dy s, v = -d/dx s
-    gs[vox] = fd_adj(g, by, W, y, H, 0, 2) - fd_adj(g, bx, 1, x, W, 1, 2);
-    return;
-  }
-  // u = dw/dy - dv/dz ; v = du/dz - dw/dx ; w = dv/dx - du/dy      (channels of s: 0 = u-, 1 = v-, 2 = w-potential)
-  // d/ds0: +d/dz (into v) - d/dy (into w);  d/ds1: -d/dz (into u) + d/dx (into w);  d/ds2: +d/dy (into u) - d/dx (into v)
-  gs[vox * 3] = fd_adj(g, bz, (int64_t)H * W, z, D, 1, 3) - fd_adj(g, by, W, y, H, 2, 3);
-  gs[vox * 3 + 1] = fd_adj(g, bx, 1, x, W, 2, 3) - fd_adj(g, bz, (int64_t)H * W, z, D, 0, 3);
-  gs[vox * 3 + 2] = fd_adj(g, by, W, y, H, 0, 3) - fd_adj(g, bx, 1, x, W, 1, 3);
-}
-
-// ---- stream-function update: g_s = curl^T(reverse(g_vel)) consumed on the spot by TF ApplyAdam on s -------------------
-// g_vel [D,H,W,3] is a velocity gradient in advect's channel order (component k along array axis k): channel c of the
-// curl's output is channel 2 - c of g_vel, folded into fd_adj's channel argument.  The gather and its summation order are
-// curl_bwd_kernel's, the update is adam_tf() below.  A thread reads g_vel at its neighbours and its
-// own s, m, v only: in place.  84 B per voxel (12 g_vel + 3 x 12 read + 3 x 12 written); 12-byte vectors, lanes contiguous.
-struct __attribute__((packed, aligned(4))) F3s { float c[3]; };
-
-// TF ApplyAdam of one element (adam_kernel's expression, field.hip)
-__device__ __forceinline__ void adam_tf(float& x, float& m, float& u, float g, float lr_t, float b1, float b2, float eps) {
-  m = b1 * m + (1.f - b1) * g;
-  u = b2 * u + (1.f - b2) * g * g;
-  x -= lr_t * m / (sqrtf(u) + eps);
-}
-
-__global__ void __launch_bounds__(256) stream_bwd_adam_kernel(const float* __restrict__ g, float* __restrict__ s,
-                                                              float* __restrict__ m, float* __restrict__ v, int D, int H,
-                                                              int W, float lr_t, float b1, float b2, float eps) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  F3s xs = reinterpret_cast<const F3s*>(s)[vox], ms = reinterpret_cast<const F3s*>(m)[vox],
-      us = reinterpret_cast<const F3s*>(v)[vox];
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  const int64_t bx = (int64_t)z * H * W + (int64_t)y * W, by = (int64_t)z * H * W + x, bz = (int64_t)y * W + x;
-  const int64_t sz = (int64_t)H * W;
-  // curl_bwd_kernel's three lines with channel c -> 2 - c
-  const float gs[3] = {fd_adj(g, bz, sz, z, D, 1, 3) - fd_adj(g, by, W, y, H, 0, 3),
-                       fd_adj(g, bx, 1, x, W, 0, 3) - fd_adj(g, bz, sz, z, D, 2, 3),
-                       fd_adj(g, by, W, y, H, 2, 3) - fd_adj(g, bx, 1, x, W, 1, 3)};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) adam_tf(xs.c[c], ms.c[c], us.c[c], gs[c], lr_t, b1, b2, eps);
-  reinterpret_cast<F3s*>(s)[vox] = xs;
-  reinterpret_cast<F3s*>(m)[vox] = ms;
-  reinterpret_cast<F3s*>(v)[vox] = us;
-}
-
-// ---- gradient of a potential (forward differences, last slice replicated; transform.py:508-515) ---------------------------
-// p [D,H,W] -> [D,H,W,3] = (dx, dy, dz) with x = axis W, y = axis H, z = axis D (the reference's channel order; zero along
-// an axis of length 1).  Reversed, it is the potential velocity vel_k = D_k p that advect moves along array axis k.
-__global__ void __launch_bounds__(256) grad_fwd_kernel(const float* __restrict__ p, float* __restrict__ out, int D, int H,
-                                                       int W) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  const int64_t lx = ((int64_t)z * H + y) * W + fd_lo(x, W), ly = ((int64_t)z * H + fd_lo(y, H)) * W + x,
-                lz = ((int64_t)fd_lo(z, D) * H + y) * W + x;
-  out[vox * 3] = W >= 2 ? p[lx + 1] - p[lx] : 0.f;
-  out[vox * 3 + 1] = H >= 2 ? p[ly + W] - p[ly] : 0.f;
-  out[vox * 3 + 2] = D >= 2 ? p[lz + (int64_t)H * W] - p[lz] : 0.f;
-}
-
-// The transpose g_p = D_D^T g[cd] + D_H^T g[ch] + D_W^T g[cw] at voxel (z, y, x): fd_adj per axis (a gather: no atomics,
-// deterministic), summed in THIS order -- D, then H, then W -- wherever it is formed, so that the stand-alone adjoints and
-// the fused updates give the same bits.  cd, ch, cw: the channels of g [D,H,W,3] that hold the D-, H- and W-difference
-// (2, 1, 0 in the reference's order, 0, 1, 2 in advect's).
-__device__ __forceinline__ float grad_adj(const float* __restrict__ g, int z, int y, int x, int D, int H, int W, int cd, int ch,
-                                          int cw) {
-  const int64_t bx = (int64_t)z * H * W + (int64_t)y * W, by = (int64_t)z * H * W + x, bz = (int64_t)y * W + x;
-  return fd_adj(g, bz, (int64_t)H * W, z, D, cd, 3) + fd_adj(g, by, W, y, H, ch, 3) + fd_adj(g, bx, 1, x, W, cw, 3);
-}
-
-__global__ void __launch_bounds__(256) grad_bwd_kernel(const float* __restrict__ g, float* __restrict__ gp, int D, int H,
-                                                       int W) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  gp[vox] = grad_adj(g, z, y, x, D, H, W, 2, 1, 0);
-}
-
-// ---- potential update: g_phi = grad^T(reverse(g_vel)) consumed on the spot by TF ApplyAdam on phi ---------------------------
-// g_vel [D,H,W,3] is a velocity gradient in advect's channel order.  A thread reads g_vel at its neighbours and its own phi,
-// m, v only: in place.  36 B per voxel (12 g_vel + 3 x 4 read + 3 x 4 written) against 44 for nfs_grad_bwd +
-// nfs_adam_tf_step; g_phi is never stored.
-__global__ void __launch_bounds__(256) potential_bwd_adam_kernel(const float* __restrict__ g, float* __restrict__ phi,
-                                                                 float* __restrict__ m, float* __restrict__ v, int D, int H,
-                                                                 int W, float lr_t, float b1, float b2, float eps) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  float xs = phi[vox], ms = m[vox], us = v[vox];
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  adam_tf(xs, ms, us, grad_adj(g, z, y, x, D, H, W, 0, 1, 2), lr_t, b1, b2, eps);
-  phi[vox] = xs;
-  m[vox] = ms;
-  v[vox] = us;
-}
-
-// ---- Helmholtz update: a [D,H,W,4] = (psi0, psi1, psi2, phi); channels 0-2 stream_bwd_adam_kernel's three lines, channel
-// 3 the potential transpose above; one 16-byte vector of a, m, v per thread, read and written in place.
-// 108 B per voxel (12 g_vel + 3 x 16 read + 3 x 16 written) against 152 for nfs_curl_bwd + nfs_grad_bwd + nfs_adam_tf_step.
-__global__ void __launch_bounds__(256) helmholtz_bwd_adam_kernel(const float* __restrict__ g, float* __restrict__ a,
-                                                                 float* __restrict__ m, float* __restrict__ v, int D, int H,
-                                                                 int W, float lr_t, float b1, float b2, float eps) {
-  const int64_t n = (int64_t)D * H * W;
-  const int64_t vox = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vox >= n) return;
-  float4 xs = reinterpret_cast<const float4*>(a)[vox], ms = reinterpret_cast<const float4*>(m)[vox],
-         us = reinterpret_cast<const float4*>(v)[vox];
-  const int x = (int)(vox % W), y = (int)((vox / W) % H), z = (int)(vox / ((int64_t)W * H));
-  const int64_t bx = (int64_t)z * H * W + (int64_t)y * W, by = (int64_t)z * H * W + x, bz = (int64_t)y * W + x;
-  const int64_t sz = (int64_t)H * W;
-  adam_tf(xs.x, ms.x, us.x, fd_adj(g, bz, sz, z, D, 1, 3) - fd_adj(g, by, W, y, H, 0, 3), lr_t, b1, b2, eps);
-  adam_tf(xs.y, ms.y, us.y, fd_adj(g, bx, 1, x, W, 0, 3) - fd_adj(g, bz, sz, z, D, 2, 3), lr_t, b1, b2, eps);
-  adam_tf(xs.z, ms.z, us.z, fd_adj(g, by, W, y, H, 2, 3) - fd_adj(g, bx, 1, x, W, 1, 3), lr_t, b1, b2, eps);
-  adam_tf(xs.w, ms.w, us.w, grad_adj(g, z, y, x, D, H, W, 0, 1, 2), lr_t, b1, b2, eps);
-  reinterpret_cast<float4*>(a)[vox] = xs;
-  reinterpret_cast<float4*>(m)[vox] = ms;
-  reinterpret_cast<float4*>(v)[vox] = us;
-}
-
 static int check_dims2(int B, int X, int Y, int C) {
   NFS_REQUIRE(B > 0 && X > 0 && Y > 0 && C > 0, "warp2d: non-positive dimension");
   NFS_REQUIRE((int64_t)B * X * Y * C < (int64_t)1 << 40, "warp2d: tensor too large");
@@ -424,79 +243,6 @@ int nfs_advect_maccormack_keep(const float* d, const float* vel, const float* d_
   hipLaunchKernelGGL(maccormack_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), d,
                      vel, d_fwd, out, D, H, W, C, nd, keep);
   return check_launch("nfs_advect_maccormack_keep");
-}
-
-int nfs_curl_fwd(const float* s, float* out, int D, int H, int W, int nd, nfs_stream_t stream) {
-  NFS_REQUIRE(s && out, "nfs_curl_fwd: null pointer");
-  NFS_REQUIRE(nd == 2 || nd == 3, "nfs_curl_fwd: nd must be 2 or 3");
-  NFS_REQUIRE(nd == 3 || D == 1, "nfs_curl_fwd: a 2-D stream function has D == 1");
-  if (int e = check_dims2(D, H, W, 1)) return e;
-  hipLaunchKernelGGL(curl_fwd_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), s, out, D,
-                     H, W, nd);
-  return check_launch("nfs_curl_fwd");
-}
-
-int nfs_curl_bwd(const float* g_out, float* g_s, int D, int H, int W, int nd, nfs_stream_t stream) {
-  NFS_REQUIRE(g_out && g_s, "nfs_curl_bwd: null pointer");
-  NFS_REQUIRE(nd == 2 || nd == 3, "nfs_curl_bwd: nd must be 2 or 3");
-  NFS_REQUIRE(nd == 3 || D == 1, "nfs_curl_bwd: a 2-D stream function has D == 1");
-  if (int e = check_dims2(D, H, W, 1)) return e;
-  hipLaunchKernelGGL(curl_bwd_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), g_out,
-                     g_s, D, H, W, nd);
-  return check_launch("nfs_curl_bwd");
-}
-
-int nfs_stream_bwd_adam(const float* g_vel, float* s, float* m, float* v, int D, int H, int W, float lr_t, float beta1,
-                        float beta2, float eps, nfs_stream_t stream) {
-  NFS_REQUIRE(g_vel && s && m && v, "nfs_stream_bwd_adam: null pointer");
-  NFS_REQUIRE(g_vel != s && g_vel != m && g_vel != v, "nfs_stream_bwd_adam: g_vel must not alias s, m or v (it is a gather)");
-  NFS_REQUIRE(D > 0 && H > 0 && W > 0, "nfs_stream_bwd_adam: non-positive dimension");
-  NFS_REQUIRE((int64_t)D * H * W * 3 < (int64_t)1 << 40, "nfs_stream_bwd_adam: tensor too large");
-  hipLaunchKernelGGL(stream_bwd_adam_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream),
-                     g_vel, s, m, v, D, H, W, lr_t, beta1, beta2, eps);
-  return check_launch("nfs_stream_bwd_adam");
-}
-
-int nfs_grad_fwd(const float* p, float* out, int D, int H, int W, nfs_stream_t stream) {
-  NFS_REQUIRE(p && out, "nfs_grad_fwd: null pointer");
-  NFS_REQUIRE(out != p, "nfs_grad_fwd: out must not alias p");
-  if (int e = check_dims2(D, H, W, 3)) return e;
-  hipLaunchKernelGGL(grad_fwd_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), p, out, D,
-                     H, W);
-  return check_launch("nfs_grad_fwd");
-}
-
-int nfs_grad_bwd(const float* g_out, float* g_p, int D, int H, int W, nfs_stream_t stream) {
-  NFS_REQUIRE(g_out && g_p, "nfs_grad_bwd: null pointer");
-  NFS_REQUIRE(g_p != g_out, "nfs_grad_bwd: g_p must not alias g_out (it is a gather)");
-  if (int e = check_dims2(D, H, W, 3)) return e;
-  hipLaunchKernelGGL(grad_bwd_kernel, dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), g_out,
-                     g_p, D, H, W);
-  return check_launch("nfs_grad_bwd");
-}
-
-// the two updates beside nfs_stream_bwd_adam: the variable is phi [D,H,W] / a [D,H,W,4], m and v of its shape
-static int bwd_adam_launch(const char* who, bool helmholtz, const float* g_vel, float* x, float* m, float* v, int D, int H,
-                           int W, float lr_t, float beta1, float beta2, float eps, nfs_stream_t stream) {
-  NFS_REQUIRE(g_vel && x && m && v, "%s: null pointer", who);
-  NFS_REQUIRE(g_vel != x && g_vel != m && g_vel != v, "%s: g_vel must not alias the variable, m or v (it is a gather)", who);
-  NFS_REQUIRE(!helmholtz || (aligned16(x) && aligned16(m) && aligned16(v)), "%s: a, m and v must be 16-byte aligned", who);
-  NFS_REQUIRE(D > 0 && H > 0 && W > 0, "%s: non-positive dimension", who);
-  NFS_REQUIRE((int64_t)D * H * W * 4 < (int64_t)1 << 40, "%s: tensor too large", who);
-  hipLaunchKernelGGL(helmholtz ? helmholtz_bwd_adam_kernel : potential_bwd_adam_kernel,
-                     dim3(blocks_for((int64_t)D * H * W, 256)), dim3(256), 0, as_stream(stream), g_vel, x, m, v, D, H, W,
-                     lr_t, beta1, beta2, eps);
-  return check_launch(who);
-}
-
-int nfs_potential_bwd_adam(const float* g_vel, float* phi, float* m, float* v, int D, int H, int W, float lr_t, float beta1,
-                           float beta2, float eps, nfs_stream_t stream) {
-  return bwd_adam_launch("nfs_potential_bwd_adam", false, g_vel, phi, m, v, D, H, W, lr_t, beta1, beta2, eps, stream);
-}
-
-int nfs_helmholtz_bwd_adam(const float* g_vel, float* a, float* m, float* v, int D, int H, int W, float lr_t, float beta1,
-                           float beta2, float eps, nfs_stream_t stream) {
-  return bwd_adam_launch("nfs_helmholtz_bwd_adam", true, g_vel, a, m, v, D, H, W, lr_t, beta1, beta2, eps, stream);
 }
 
 }  // extern "C"

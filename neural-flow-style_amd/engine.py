@@ -640,27 +640,29 @@ class TFAdamState(object):
             return None
         return self._ever
 
-    def step(self, x, g, lr):
-        if self.m is None or self.m.shape != x.shape:
+    def _begin_step(self, x, lr):
+        """the scalar half of ApplyAdam for a variable of ``x``'s shape: m and v zeroed when missing or of another shape, the
+        beta powers advanced.  -> (fresh: m and v are new, (lr_t, beta1, beta2, eps) as the kernels take them)"""
+        fresh = self.m is None or self.m.shape != x.shape
+        if fresh:
             self.m = torch.zeros_like(x)
             self.v = torch.zeros_like(x)
         # beta powers are float32 variables multiplied once per step in TF
         self.b1p = np.float32(self.b1p * self.b1)
         self.b2p = np.float32(self.b2p * self.b2)
         lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
-        ops.adam_tf_step(x, self.m, self.v, g, float(lr_t), float(self.b1), float(self.b2), float(self.eps))
+        return fresh, (float(lr_t), float(self.b1), float(self.b2), float(self.eps))
+
+    def step(self, x, g, lr):
+        _, hyper = self._begin_step(x, lr)
+        ops.adam_tf_step(x, self.m, self.v, g, *hyper)
 
     def step_through_source(self, kind, x, g_vel, lr):
         """the same update for a variable ``x`` the velocity is a function of -- ``kind`` 's': a stream function [D,H,W,3],
         'p': a potential [D,H,W], 'sp': the Helmholtz pair [D,H,W,4] -- given the gradient ``g_vel`` of that velocity
         (``ops.source_velocity``): g_x = ``ops.source_velocity_bwd(kind, g_vel)`` is gathered and consumed inside one kernel"""
-        if self.m is None or self.m.shape != x.shape:
-            self.m = torch.zeros_like(x)
-            self.v = torch.zeros_like(x)
-        self.b1p = np.float32(self.b1p * self.b1)
-        self.b2p = np.float32(self.b2p * self.b2)
-        lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
-        ops.source_bwd_adam(kind, g_vel, x, self.m, self.v, float(lr_t), float(self.b1), float(self.b2), float(self.eps))
+        _, hyper = self._begin_step(x, lr)
+        ops.source_bwd_adam(kind, g_vel, x, self.m, self.v, *hyper)
 
     def step_through_advect(self, vel, d0, g_adv, lr, adv_next=None, live_next=None, live_current=False):
         """the same update for the velocity variable of ``advect(d0, vel)`` given dL/d(advected density): the
@@ -668,38 +670,25 @@ class TFAdamState(object):
         (optional) receives advect(d0, updated vel) -- the next iteration's forward sample -- in the same pass, ``live_next``
         its live mask.  ``live_current``: ``live_next`` holds the mask of the CURRENT sample on entry (and ``adv_next`` that
         sample) -- the waves whose voxels never were live are then left out (``ever_mask``)"""
-        fresh = self.m is None or self.m.shape != vel.shape
+        fresh, hyper = self._begin_step(vel, lr)
         if fresh:
-            self.m = torch.zeros_like(vel)
-            self.v = torch.zeros_like(vel)
             self._ever = None
         if fresh and live_next is not None:
             self._ever = torch.zeros_like(live_next)
             self._ever_key = (self.m._version, self.v._version)
         ever = self.ever_mask() if (live_current and live_next is not None and adv_next is not None) else None
-        self.b1p = np.float32(self.b1p * self.b1)
-        self.b2p = np.float32(self.b2p * self.b2)
-        lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
         tracked = self._ever is not None and self._ever_key == (self.m._version, self.v._version)
-        ops.advect_bwd_adam(d0, vel, g_adv, self.m, self.v, float(lr_t), float(self.b1), float(self.b2),
-                            float(self.eps), adv_next=adv_next, live_next=live_next, ever=ever)
+        ops.advect_bwd_adam(d0, vel, g_adv, self.m, self.v, *hyper, adv_next=adv_next, live_next=live_next, ever=ever)
         if ever is not None:
             self._ever_key = (self.m._version, self.v._version)      # (our own write: the mask stays usable)
         elif tracked:
             self._ever = None                                        # (a step without the mask update: it no longer covers m, v)
 
-
     def step_through_advect_slab(self, vel_slab, d0, g_adv_slab, z0, lr, adv_next=None):
         """``step_through_advect`` on the planes [z0, z0 + nz) only: the moments exist for these planes alone (the Adam
         state of a D-slab-sharded run is sharded with the variable)"""
-        if self.m is None or self.m.shape != vel_slab.shape:
-            self.m = torch.zeros_like(vel_slab)
-            self.v = torch.zeros_like(vel_slab)
-        self.b1p = np.float32(self.b1p * self.b1)
-        self.b2p = np.float32(self.b2p * self.b2)
-        lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
-        ops.advect_bwd_adam_slab(d0, vel_slab, g_adv_slab, self.m, self.v, z0, float(lr_t), float(self.b1),
-                                 float(self.b2), float(self.eps), adv_next=adv_next)
+        _, hyper = self._begin_step(vel_slab, lr)
+        ops.advect_bwd_adam_slab(d0, vel_slab, g_adv_slab, self.m, self.v, z0, *hyper, adv_next=adv_next)
 
 
 class LBFGSState(object):
