@@ -17,7 +17,11 @@
  *   - return value 0 = ok, <0 = error (NFS_E*), message via nfs_last_error()
  *     (thread-local); no exceptions cross the ABI;
  *   - "accumulate" outputs (g_d of the scatter adjoints) are += targets: the
- *     caller zeroes them once per iteration, which is what lets views accumulate.
+ *     caller zeroes them once per iteration, which is what lets views accumulate;
+ *   - this file is the only declaration of the ABI and is READ by the Python binding (neural-flow-style_amd/_lib.py,
+ *     read_header), which derives its argtypes, structs and constants from it: declarations stay within that reader's
+ *     vocabulary (int, float, double, int64_t, nfs_stream_t; pointers to float, int, double, uint8_t, uint32_t,
+ *     long long, unsigned long long or a struct typedef'd above; one `type name` per parameter), or it refuses to load.
  */
 #ifndef NFS_HIP_H
 #define NFS_HIP_H
@@ -31,6 +35,10 @@ extern "C" {
 #define NFS_OK 0
 #define NFS_EINVAL (-1)  /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define NFS_ELAUNCH (-2) /* HIP launch/runtime error */
+
+/* what nfs_version() returns, as 100 major + 10 minor + patch (the changelog is at its definition, csrc/api.hip); the
+ * Python binding refuses a library that reports another number than the header it reads */
+#define NFS_ABI_VERSION 157
 
 typedef void* nfs_stream_t;
 

@@ -1,4 +1,7 @@
-"""ctypes loader for libnfs_hip.so (the C ABI declared in include/nfs_hip.h).
+"""ctypes loader for libnfs_hip.so.
+
+include/nfs_hip.h is the only declaration of the C ABI: ``read_header`` derives the argtypes, the return types, the
+struct layouts, the NFS_E* codes and the ABI version from it at import time (no compiler, no library, no GPU).
 
 The HIP library is the product path: there is NO CPU fallback.  If the shared
 object is missing, importing an op raises immediately (``NfsLibraryError``).
@@ -7,19 +10,18 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NFS_LIB_PATH: load another build of the same library (measurement builds made with -DNFS_ABLATE; never the product)
 LIB_PATH = os.environ.get("NFS_LIB_PATH") or os.path.join(_HERE, "libnfs_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_hip.h"))    # as csrc/common.h includes it
 
 
 class NfsLibraryError(RuntimeError):
     pass
-
-
-NFS_EINVAL, NFS_ELAUNCH = -1, -2            # include/nfs_hip.h
 
 
 class NfsError(RuntimeError):
@@ -30,173 +32,81 @@ class NfsError(RuntimeError):
         self.name, self.code = name, int(code)
 
 
-class SplatCfg(C.Structure):
-    _fields_ = [("nd", C.c_int), ("res", C.c_int * 3), ("domain", C.c_float * 3),
-                ("radius", C.c_float), ("support", C.c_float), ("rest_density", C.c_float),
-                ("nsize", C.c_int), ("clip", C.c_int), ("mode", C.c_int)]
+# The closed type vocabulary of the header.  A new type is one line here.
+_VALUE = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "int64_t": C.c_int64, "nfs_stream_t": C.c_void_p}
+# tensors cross as data_ptr() integers: a pointer to one of these (const or not) is a c_void_p
+_POINTEE = {"float", "int", "double", "uint8_t", "uint32_t", "long long", "unsigned long long"}
 
 
-class GramLayer(C.Structure):
-    """nfs_gram_layer_t (include/nfs_hip.h): one style layer of the grouped Gram / style-loss entry points"""
-    _fields_ = [("F", C.c_void_p), ("Gs", C.c_void_p), ("G", C.c_void_p), ("Dmat", C.c_void_p), ("dF", C.c_void_p),
-                ("B", C.c_int), ("Bs", C.c_int), ("HW", C.c_int), ("C", C.c_int),
-                ("scale", C.c_float), ("weight", C.c_float), ("relu_mask", C.c_int)]
+def read_header(text):
+    """(signatures, restypes, structs, constants) of a header in the shape of include/nfs_hip.h: name -> argtypes list,
+    name -> return type, typedef name -> ctypes.Structure class, NFS_* macro -> int.  Not a C parser: every statement is
+    the stream typedef, a ``typedef struct``, or an ``nfs_*`` declaration over the vocabulary above, or it raises."""
+    signatures, restypes, structs, constants = {}, {}, {}, {}
+
+    def ctype(spelling, where, returned=False):
+        words = spelling.replace("*", " * ").split()
+        if words[-1:] != ["*"]:
+            if " ".join(words) in _VALUE:
+                return _VALUE[" ".join(words)]
+        else:
+            base = " ".join(w for w in words[:-1] if w != "const")
+            if base in _POINTEE:
+                return C.c_void_p
+            if base in structs:
+                return C.POINTER(structs[base])
+            if returned and words == ["const", "char", "*"]:
+                return C.c_char_p
+        raise NfsLibraryError("nfs_hip.h: type '%s' in '%s' is outside the binding's vocabulary (_lib.read_header)"
+                              % (" ".join(words), where))
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(NFS_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M):
+        constants[name] = int(value)
+    text = re.sub(r'^[ \t]*(#.*|extern[ \t]+"C"[ \t]*\{[ \t]*|\}[ \t]*)$', "", text, flags=re.M)
+    statement = r"((?:[^;{}]|\{[^{}]*\})*);"
+    rest = re.sub(statement, "", text).strip()
+    if rest:
+        raise NfsLibraryError("nfs_hip.h: not a statement: '%s'" % rest)
+    for st in re.findall(statement, text):
+        st = " ".join(st.split())
+        m = re.fullmatch(r"typedef struct \{((?:[^;]*;)*) ?\} ?(\w+)", st)
+        if m:
+            fields = []
+            for decl in m.group(1).split(";")[:-1]:
+                f = re.fullmatch(r"(.*?)(\w+(?: ?\[\d+\])?(?: ?, ?\w+(?: ?\[\d+\])?)*)", decl.strip())
+                if not f:
+                    raise NfsLibraryError("nfs_hip.h: not a field: '%s' in '%s'" % (decl.strip(), st))
+                t = ctype(f.group(1), st)
+                for name, n in re.findall(r"(\w+)(?: ?\[(\d+)\])?", f.group(2)):
+                    fields.append((name, t * int(n) if n else t))
+            structs[m.group(2)] = type(m.group(2), (C.Structure,), {"_fields_": fields})
+            continue
+        m = re.fullmatch(r"(.*?)\b(nfs_\w+) ?\((.*)\)", st)
+        if m:
+            args = []
+            for param in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+                p = re.fullmatch(r"(.*\W)\w+", param.strip())
+                if not p:
+                    raise NfsLibraryError("nfs_hip.h: not a parameter: '%s' in '%s'" % (param.strip(), st))
+                args.append(ctype(p.group(1), st))
+            signatures[m.group(2)], restypes[m.group(2)] = args, ctype(m.group(1), st, returned=True)
+            continue
+        if st != "typedef void* nfs_stream_t":
+            raise NfsLibraryError("nfs_hip.h: neither the stream typedef, a struct nor an nfs_* declaration: '%s'" % st)
+    return signatures, restypes, structs, constants
 
 
-class ConvDesc(C.Structure):
-    """nfs_conv2d_desc_t (include/nfs_hip.h): one convolution of a grouped launch"""
-    _fields_ = [("x", C.c_void_p), ("x_mask", C.c_void_p), ("packed", C.c_void_p), ("bias", C.c_void_p),
-                ("y", C.c_void_p), ("y_pre", C.c_void_p),
-                ("ldx", C.c_int), ("ldm", C.c_int), ("ldy", C.c_int), ("ldp", C.c_int),
-                ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("kh", C.c_int), ("kw", C.c_int),
-                ("relu", C.c_int), ("accumulate", C.c_int), ("sum_with_prev", C.c_int)]
-
-
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
-
-# name -> argtypes (all return int unless listed in _RESTYPE)
-SIGNATURES = {
-    "nfs_version": [],
-    "nfs_last_error": [],
-    "nfs_device_cus": [],
-    "nfs_gemm_timer": [_I],
-    "nfs_gemm_mode": [_I],
-    "nfs_gemm_force": [_I, _I, _I, _I, _I],
-    "nfs_gemm_last": [_P],
-    "nfs_gemm_timer_read": [_P, _P, _P],
-    "nfs_gemm_timer_read_kind": [_I, _P, _P, _P, _P],
-    "nfs_warp3d_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_warp3d_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_rotate_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_rotate_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
-    "nfs_advect_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "nfs_advect_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "nfs_advect_bwd_adam": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_advect_fwd_slab": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_advect_bwd_adam_slab": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_advect_bwd_adam_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_advect_bwd_adam_fwd_slab": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_warp2d_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "nfs_warp2d_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "nfs_advect2d_fwd": [_P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect2d_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_maccormack": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_maccormack_mask_words": [_I, _I, _I, _I],
-    "nfs_advect_maccormack_keep": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_advect_maccormack_bwd_workspace_floats": [_I, _I, _I, _I, _I],
-    "nfs_advect_maccormack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],
-    "nfs_curl_fwd": [_P, _P, _I, _I, _I, _I, _P],
-    "nfs_curl_bwd": [_P, _P, _I, _I, _I, _I, _P],
-    "nfs_advect_stream_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_stream_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_stream_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_grad_fwd": [_P, _P, _I, _I, _I, _P],
-    "nfs_grad_bwd": [_P, _P, _I, _I, _I, _P],
-    "nfs_advect_potential_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_potential_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_helmholtz_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_helmholtz_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_potential_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_helmholtz_bwd_adam": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_lap_down": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_lap_up": [_P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_lap_up_rms_parts": [_I, _I, _I, _I, _I],
-    "nfs_lap_up_rms": [_P, _P, _F, _P, _P, _I, _L, _F, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_normalize_mean": [_P, _P, _L, _I, _F, _P, _I, _P],
-    "nfs_transport_step": [_P, _P, _F, _F, _P, _F, _P, _I, _I, _I, _I, _P],
-    "nfs_smooth3d_relu_fwd": [_P, _P, _I, _I, _I, _F, _P],
-    "nfs_smooth3d_relu_bwd": [_P, _P, _P, _I, _I, _I, _F, _P],
-    "nfs_render_fwd": [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_render_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P],
-    "nfs_rotate_render_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_render_coef_layout": [_I, _I, _I, _I, _P, _P],
-    "nfs_rotate_render_fwd_coef": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "nfs_render_ray_coef": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
-    "nfs_render_ray_coef_bounds": [_I, _I, _I],
-    "nfs_rotate_bwd_coef": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
-    "nfs_live_mask_words": [_I, _I, _I],
-    "nfs_advect_fwd_live": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_advect_bwd_adam_fwd_live": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_advect_bwd_adam_fwd_live_ever": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P],
-    "nfs_rotate_bwd_coef_live": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P],
-    "nfs_rotate_live_workspace_ints": [_I, _I, _I],
-    "nfs_rotate_render_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_maxnorm_workspace_floats": [_I],
-    "nfs_maxnorm_fwd": [_P, _P, _P, _I, _I, _P],
-    "nfs_maxnorm_bwd": [_P, _P, _P, _P, _I, _I, _P, _P],
-    "nfs_maxnorm_input_fwd": [_P, _P, _P, _I, _I, _P],
-    "nfs_maxnorm_input_bwd": [_P, _P, _P, _P, _I, _I, _P, _P],
-    "nfs_loss_net_input_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "nfs_loss_net_input_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "nfs_conv3x3_packed_floats": [_I, _I, _I],
-    "nfs_conv3x3_pack": [_P, _P, _I, _I, _I, _P],
-    "nfs_conv3x3_workspace_floats": [_I, _I, _I, _I, _I],
-    "nfs_conv3x3_relu_bits_words": [_I, _I, _I, _I, _I, _I],
-    "nfs_conv3x3_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P],
-    "nfs_conv3x3_dgrad": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P],
-    "nfs_conv3x3_fwd_pool": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P],
-    "nfs_conv3x3_dgrad_pool": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P],
-    "nfs_avgpool2_fwd": [_P, _P, _I, _I, _I, _I, _P],
-    "nfs_avgpool2_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "nfs_gram_workspace_floats": [_I, _I, _I],
-    "nfs_gram_fwd": [_P, _P, _I, _I, _I, _P, _F, _P, _L, _P],
-    "nfs_style_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
-    "nfs_content_loss": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],
-    "nfs_content_loss_signed": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],
-    "nfs_gram_bwd": [_P, _P, _P, _I, _I, _I, _P, _F, _I, _P],
-    "nfs_hist_loss": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_conv3x3_executed_flops": [_I, _I, _I, _I, _I, _I],
-    "nfs_conv2d_packed_floats": [_I, _I, _I, _I, _I],
-    "nfs_conv2d_pack": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_conv2d_workspace_floats": [_I, _I, _I, _I, _I, _I, _I, _I],
-    "nfs_conv2d_fwd": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
-    "nfs_conv2d_group_workspace_floats": [_P, _I, _I],
-    "nfs_conv2d_group": [_P, _I, _I, _P, _L, _P],
-    "nfs_conv2d_dgrad_small": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "nfs_maxpool3_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_maxpool3_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "nfs_lrn_fwd": [_P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _P],
-    "nfs_lrn_bwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _F, _F, _I, _P],
-    "nfs_avgpool_valid_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "nfs_avgpool_valid_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "nfs_relu_mask_add": [_P, _I, _P, _I, _P, _I, _P, _I, _L, _I, _P],
-    "nfs_gram_style_group_workspace_floats": [_P, _I],
-    "nfs_gram_style_group_parts": [_P, _I],
-    "nfs_gram_style_group_fwd": [_P, _I, _P, _P, _L, _P],
-    "nfs_gram_group_bwd": [_P, _I, _P],
-    "nfs_hist_loss_masked": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_hist_loss_wide_workspace_floats": [_I, _I, _I, _I],
-    "nfs_hist_loss_wide": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
-    "nfs_resize_bicubic_tf1": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "nfs_resize3d": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
-    "nfs_style_mask_apply": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_style_mask_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "nfs_tv_loss": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "nfs_p2g_fwd": [_P, _P, _P, _P, _P, _I, _I, C.POINTER(SplatCfg), _P],
-    "nfs_p2g_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(SplatCfg), _P],
-    "nfs_p2g_wavg_finish": [_P, _P, _P, _L, _I, _F, _P],
-    "nfs_p2g_wavg_finish_bwd": [_P, _P, _P, _P, _P, _L, _I, _F, _P],
-    "nfs_p2g_has_instance": [C.POINTER(SplatCfg)],
-    "nfs_p2g_wavg_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, C.POINTER(SplatCfg), _P],
-    "nfs_g2p_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P],
-    "nfs_adam_tf_step": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P],
-    "nfs_fill": [_P, _F, _L, _P],
-    "nfs_axpy": [_P, _P, _F, _L, _P],
-    "nfs_slab_pack": [_P, _P, _I, _L, _I, _I, _P],
-    "nfs_colour_clamp_gather": [_P, _P, _P, _L, _I, _P],
-    "nfs_clamp01_bwd": [_P, _P, _P, _L, _P],
-    "nfs_colour_clamp_scatter_bwd": [_P, _P, _P, _P, _L, _I, _P],
-    "nfs_iterate_update": [_P, _P, _L, _P],
-}
-_RESTYPE = {"nfs_last_error": C.c_char_p, "nfs_conv3x3_packed_floats": C.c_int64,
-            "nfs_conv3x3_workspace_floats": C.c_int64, "nfs_gram_workspace_floats": C.c_int64,
-            "nfs_conv3x3_relu_bits_words": C.c_int64, "nfs_gram_style_group_workspace_floats": C.c_int64, "nfs_hist_loss_wide_workspace_floats": C.c_int64,
-            "nfs_advect_maccormack_bwd_workspace_floats": C.c_int64,
-            "nfs_conv3x3_executed_flops": C.c_double, "nfs_conv2d_packed_floats": C.c_int64,
-            "nfs_conv2d_workspace_floats": C.c_int64, "nfs_conv2d_group_workspace_floats": C.c_int64}
+try:
+    with open(HEADER_PATH) as _f:
+        SIGNATURES, RESTYPES, _structs, _constants = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (HEADER_PATH, e))
+SplatCfg, GramLayer, ConvDesc = _structs["nfs_splat_cfg"], _structs["nfs_gram_layer_t"], _structs["nfs_conv2d_desc_t"]
+NFS_EINVAL, NFS_ELAUNCH = _constants["NFS_EINVAL"], _constants["NFS_ELAUNCH"]
+ABI_VERSION = _constants["NFS_ABI_VERSION"]          # what nfs_version() of a library built from this header returns
 
 _lib = None
-ABI_VERSION = 157          # nfs_version() this table was written against (include/nfs_hip.h)
 
 
 def build(verbose=False):
@@ -233,12 +143,14 @@ def lib():
             except AttributeError:
                 raise NfsLibraryError("libnfs_hip.so does not export %s (stale build?)" % name)
             f.argtypes = argt
-            f.restype = _RESTYPE.get(name, C.c_int)
-        # the binding and the library move together (entry points, packed-filter sizes, the default GEMM arithmetic): a
-        # stale .so with every symbol of an older minor present must not be driven by this table
-        if L.nfs_version() < ABI_VERSION:
-            raise NfsLibraryError("libnfs_hip.so reports ABI %d, this binding needs >= %d: rebuild (make -C %s)"
-                                  % (L.nfs_version(), ABI_VERSION, CSRC_DIR))
+            f.restype = RESTYPES[name]
+        # the binding is the header at hand, and the library moves with it (entry points, packed-filter sizes, the default
+        # GEMM arithmetic): a .so built from another header, with every symbol present, must not be driven by this one
+        if L.nfs_version() != ABI_VERSION:
+            stale = ("the library is stale: rebuild (make -C %s)" % CSRC_DIR if L.nfs_version() < ABI_VERSION else
+                     "the header is stale: %s is older than the library" % HEADER_PATH)
+            raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d; %s"
+                                  % (LIB_PATH, L.nfs_version(), ABI_VERSION, stale))
         _lib = L
     return _lib
 

@@ -884,7 +884,6 @@ def gram_style_group(Fs, Gss, weights, relu_masks, want_G=False, channels=None):
     1/(2 h w C) like G), ``weights`` w_layer * w_style, ``relu_masks`` whether dF carries the layer's ReLU mask.
     Returns (loss_parts [P,B] -- the style loss of image b is loss_parts[:, b].sum(), every entry written, no atomics --,
     list of dF, list of G or None)."""
-    import ctypes
     n = len(Fs)
     if n > 8:                                          # the descriptor table of one launch holds 8 layers
         a = gram_style_group(Fs[:8], Gss[:8], weights[:8], relu_masks[:8], want_G, channels and channels[:8])
@@ -906,15 +905,14 @@ def gram_style_group(Fs, Gss, weights, relu_masks, want_G=False, channels=None):
         # (rows padded with zero channels -- Inception module outputs --: the denominator counts the logical ones)
         y.scale, y.weight, y.relu_mask = 1.0 / (2.0 * HW * (channels[l] if channels else Cn)), float(w), int(bool(rm))
     L = _lib.lib()
-    ap = ctypes.cast(arr, ctypes.c_void_p)
-    P = L.nfs_gram_style_group_parts(ap, n)
-    nws = L.nfs_gram_style_group_workspace_floats(ap, n)
+    P = L.nfs_gram_style_group_parts(arr, n)
+    nws = L.nfs_gram_style_group_workspace_floats(arr, n)
     if P < 0 or nws < 0:
         raise ValueError("gram_style_group: 1..8 layers of one batch size with C a multiple of 64")
     ws = conv_workspace(Fs[0].device, max(nws, 1))      # shared scratch (calls on one stream are ordered)
     parts = _empty((P, B), Fs[0])
-    _lib.call("nfs_gram_style_group_fwd", ap, n, _ptr(parts), _ptr(ws), ws.numel(), _stream())
-    _lib.call("nfs_gram_group_bwd", ap, n, _stream())
+    _lib.call("nfs_gram_style_group_fwd", arr, n, _ptr(parts), _ptr(ws), ws.numel(), _stream())
+    _lib.call("nfs_gram_group_bwd", arr, n, _stream())
     return parts, [k[1] for k in keep], ([k[2] for k in keep] if want_G else None)
 
 
@@ -1243,7 +1241,6 @@ def conv2d_group(problems):
     """Several stride-1 SAME convolutions of one batch in one launch.  ``problems``: dicts with the arguments of
     ``conv2d_fwd`` (x, cx, Cin, packed, bias, y, cy, Cout, k, relu, y_pre, cp, x_mask, cm, accumulate) and
     ``sum_with_prev`` (added to the previous problem's result: same pixels, Cout and output range)"""
-    import ctypes
     n = len(problems)
     arr = (_lib.ConvDesc * n)()
     B = problems[0]["x"].shape[0]
@@ -1261,19 +1258,18 @@ def conv2d_group(problems):
         q.H, q.W, q.Cin, q.Cout, q.kh, q.kw = x.shape[1], x.shape[2], Cin, Cout, pr["k"], pr["k"]
         q.relu, q.accumulate = int(bool(pr.get("relu", True))), int(bool(pr.get("accumulate", False)))
         q.sum_with_prev = int(bool(pr.get("sum_with_prev", False)))
-    ap = ctypes.cast(arr, ctypes.c_void_p)
     key = (B,) + tuple((q.H, q.W, q.Cin, q.Cout, q.kh, q.sum_with_prev) for q in arr)
     nws = _group_ws.get(key)
     if nws is None:
-        nws = _lib.lib().nfs_conv2d_group_workspace_floats(ap, n, B)
+        nws = _lib.lib().nfs_conv2d_group_workspace_floats(arr, n, B)
         if nws < 0:
-            _lib.call("nfs_conv2d_group", ap, n, B, None, 0, _stream())     # raises with the planner's message
+            _lib.call("nfs_conv2d_group", arr, n, B, None, 0, _stream())     # raises with the planner's message
         _group_ws[key] = nws
     ws = conv_workspace(x.device, nws) if nws > 0 else None
     if _lib.PROFILE is not None:                          # (bench: the shapes behind this call's event pair)
         _lib.PROFILE.setdefault("shapes:nfs_conv2d_group", []).append(
             [(B, q.H, q.W, q.Cin, q.Cout, q.kh, q.kw) for q in arr])
-    _lib.call("nfs_conv2d_group", ap, n, B, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    _lib.call("nfs_conv2d_group", arr, n, B, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
 
 
 def conv2d_dgrad_small(gy, cg, Co, w_hwio, in_hw, stride, y_act=None, ca=0):

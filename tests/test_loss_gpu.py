@@ -11,7 +11,6 @@ every such check prints the largest err / bound it saw (pytest -s).
 
 The plan a shape takes depends on the chip's CU count; it is read back from nfs_gram_workspace_floats (B * npair *
 nslab * 4096 + 16384), and a case whose shape is planned onto another path than the one it is named for skips."""
-import ctypes
 import functools
 import math
 
@@ -220,14 +219,13 @@ def run_group(layers, B, Bs):
         a.B, a.Bs, a.HW, a.C = B, Bs, HW, C
         a.scale, a.weight, a.relu_mask = y["s"], y["w"], l % 2
     L = _lib.lib()
-    ap = ctypes.cast(arr, ctypes.c_void_p)
-    P, nws = int(L.nfs_gram_style_group_parts(ap, n)), int(L.nfs_gram_style_group_workspace_floats(ap, n))
+    P, nws = int(L.nfs_gram_style_group_parts(arr, n)), int(L.nfs_gram_style_group_workspace_floats(arr, n))
     # slab layers and one-slab layers in one call, as planned (the grouped plan does not depend on the chip)
     assert (nws, P) == LR.group_plan([(y["HW"], y["C"]) for y in layers], B), (nws, P)
     ws = nans(max(nws, 1))
     parts = nans(P, B)
-    _lib.call("nfs_gram_style_group_fwd", ap, n, ops._ptr(parts), ops._ptr(ws), ws.numel(), ops._stream())
-    _lib.call("nfs_gram_group_bwd", ap, n, ops._stream())
+    _lib.call("nfs_gram_style_group_fwd", arr, n, ops._ptr(parts), ops._ptr(ws), ws.numel(), ops._stream())
+    _lib.call("nfs_gram_group_bwd", arr, n, ops._stream())
     torch.cuda.synchronize()
     return N(parts), [(N(k[2]), N(k[3]), N(k[4]), k[5]) for k in keep]
 

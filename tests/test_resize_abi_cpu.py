@@ -42,3 +42,4 @@ def test_binding_is_in_the_table_at_this_abi():
     _lib = _ensure_built()
     assert "nfs_resize3d" in _lib.SIGNATURES and len(_lib.SIGNATURES["nfs_resize3d"]) == 13
     assert _lib.ABI_VERSION >= 157 and _lib.lib().nfs_version() >= 157
+    assert _lib.ABI_VERSION == _lib.lib().nfs_version()
