@@ -1069,7 +1069,9 @@ __global__ void __launch_bounds__(256) winograd_pack_limbs16_kernel(const float4
   ub[(3 * grp + 2) * 64 + lane] = __builtin_bit_cast(uint4, L);
 }
 
-template <int MT16, int NW16, bool PRE>
+// NCH: the number of K chunks per part as a compile-time constant (the K loop is then written out NCH times, see the
+// loop), 0 any number (the rolled loop).
+template <int MT16, int NW16, bool PRE, int NCH>
 __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, unsigned char* smem, int comp, int64_t m0,
                                                           int n0, int split) {
   constexpr int BM = 16 * MT16, BN = 64 * NW16;
@@ -1078,7 +1080,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
   constexpr int G = MT16 <= 5 ? MT16 : (MT16 == 7 ? 4 : 5);   // row tiles whose A fragments are live together
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int nchunks = a.K / WG_KC / a.ksplit, c0 = split * nchunks;
+  const int nchunks = NCH > 0 ? NCH : a.K / WG_KC / a.ksplit, c0 = split * nchunks;
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.V + (int64_t)comp * a.T * a.K), 0, (uint32_t)(a.T * a.K * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t b_rsrc =
@@ -1107,6 +1109,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
   // distance) every chunk waited for its operands (measured: 40 us where the MFMAs need 12)
   constexpr int PF = NFS_RB16S_PF;                // register sets = chunks in flight per wave
   static_assert(PF >= 2 && PF <= 4, "the K loop below is written for 2-4 register sets");
+  static_assert(NCH == 0 || NCH >= PF, "an unrolled K loop fills every register set in its prologue");
   float4 av[PF][AJ], bq[PF][NW16][NB];
 #pragma unroll
   for (int st = 0; st < PF; ++st) {
@@ -1126,7 +1129,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
 #pragma unroll
     for (int nt = 0; nt < NW16; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#define NFS_RB16S_STEP(ST, C)                                                                                      \
+#define NFS_RB16S_STEP(ST, C, LD)                                                                                  \
   {                                                                                                                \
     unsigned char* Ac = smem + ((C) & 1) * BUF;                                                                    \
     if (!(NFS_RB16S_ABL & 4)) _Pragma("unroll") for (int j = 0; j < AJ; ++j) {                                     \
@@ -1145,7 +1148,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
     }                                                                                                              \
     __syncthreads();       /* buffer (C & 1) visible; the other one was last read in the step before */            \
     const int cn = c0 + ((C) + PF < nchunks ? (C) + PF : nchunks - 1);   /* (past the end: a harmless re-fetch) */  \
-    if (!(NFS_RB16S_ABL & 8))                                                                                      \
+    if ((LD) && !(NFS_RB16S_ABL & 8))                                                                              \
       _Pragma("unroll") for (int j = 0; j < AJ; ++j) av[ST][j] = wg_ld4(a_rsrc, ao[j], (uint32_t)cn * (WG_KC * 4)); \
     bf16x8s bf[NW16][3];                                                                                           \
     _Pragma("unroll") for (int nt = 0; nt < NW16; ++nt) {                                                          \
@@ -1156,7 +1159,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
         _Pragma("unroll") for (int p = 0; p < 3; ++p) bf[nt][p] = __builtin_bit_cast(bf16x8s, bq[ST][nt][p % NB]);  \
       } else rb16s_split8(bq[ST][nt][0], bq[ST][nt][1], bf[nt][0], bf[nt][1], bf[nt][2]);                          \
     }                                                                                                              \
-    if (!(NFS_RB16S_ABL & 8))                                                                                      \
+    if ((LD) && !(NFS_RB16S_ABL & 8))                                                                              \
       _Pragma("unroll") for (int nt = 0; nt < NW16; ++nt)                                                          \
         _Pragma("unroll") for (int g = 0; g < NB; ++g)                                                             \
           bq[ST][nt][g] = wg_ld4(b_rsrc, bo, bt0 + nt * kgs + (uint32_t)(NB * cn + g) * 1024u);                    \
@@ -1179,12 +1182,28 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
       }                                                                                                            \
     }                                                                                                              \
   }
+  // The rolled loop carries its in-flight register sets across the back edge, and hipcc 7.2 then drains every load at the
+  // loop header (s_waitcnt vmcnt(0)) and waits at the latch for the loads the last step has just issued (the phi copies
+  // read them): the prefetch distance of every other chunk is under one chunk, whatever PF is.  With the chunk count a
+  // compile-time constant the same steps stand in one basic block, every wait counts exactly the loads that may stay in
+  // flight, and the last PF steps fetch nothing (the rolled form re-fetches the last chunk there).  The arithmetic and
+  // its order are the rolled loop's: bit-identical results (tests/test_gemm_unrolled_gpu.py).
+  if constexpr (NCH > 0) {
+#pragma unroll
+    for (int c = 0; c < NCH; c += PF) {
+      NFS_RB16S_STEP(0, c, c + PF < NCH)
+      if (c + 1 < NCH) NFS_RB16S_STEP(1, c + 1, c + 1 + PF < NCH)
+      if (PF > 2 && c + 2 < NCH) NFS_RB16S_STEP(PF > 2 ? 2 : 0, c + 2, c + 2 + PF < NCH)
+      if (PF > 3 && c + 3 < NCH) NFS_RB16S_STEP(PF > 3 ? 3 : 0, c + 3, c + 3 + PF < NCH)
+    }
+  } else {
 #pragma unroll 1
-  for (int c = 0; c < nchunks; c += PF) {
-    NFS_RB16S_STEP(0, c)
-    if (c + 1 < nchunks) NFS_RB16S_STEP(1, c + 1)
-    if (PF > 2 && c + 2 < nchunks) NFS_RB16S_STEP(PF > 2 ? 2 : 0, c + 2)
-    if (PF > 3 && c + 3 < nchunks) NFS_RB16S_STEP(PF > 3 ? 3 : 0, c + 3)
+    for (int c = 0; c < nchunks; c += PF) {
+      NFS_RB16S_STEP(0, c, true)
+      if (c + 1 < nchunks) NFS_RB16S_STEP(1, c + 1, true)
+      if (PF > 2 && c + 2 < nchunks) NFS_RB16S_STEP(PF > 2 ? 2 : 0, c + 2, true)
+      if (PF > 3 && c + 3 < nchunks) NFS_RB16S_STEP(PF > 3 ? 3 : 0, c + 3, true)
+    }
   }
 #undef NFS_RB16S_STEP
 
@@ -1227,7 +1246,7 @@ __device__ __forceinline__ void winograd_gemm_rb16s_block(const WgGemmArgs& a, u
 #ifndef NFS_RB16S_OCC_TILES
 #define NFS_RB16S_OCC_TILES 14        // (10 -> 14, i.e. the 112 x 128 tile too: 486 -> 482 us)
 #endif
-template <int MT16, int NW16, bool PRE>
+template <int MT16, int NW16, bool PRE, int NCH>
 __global__ void __launch_bounds__(256, (MT16 * NW16 <= NFS_RB16S_OCC_TILES ? NFS_RB16S_OCC : 1)) winograd_gemm_rb16s_kernel(WgGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
   const int nblocks = (int)gridDim.x, block = (int)blockIdx.x;
@@ -1244,13 +1263,13 @@ __global__ void __launch_bounds__(256, (MT16 * NW16 <= NFS_RB16S_OCC_TILES ? NFS
   if constexpr (MT16 <= 5) {
     const int64_t left = (a.T - m0 + 15) / 16;
     const int live = left < MT16 ? (int)left : MT16;
-    if (live == MT16) winograd_gemm_rb16s_block<MT16, NW16, PRE>(a, smem_s, comp, m0, n0, split);
-    else if (live == 1) winograd_gemm_rb16s_block<1, NW16, PRE>(a, smem_s, comp, m0, n0, split);
-    else if (MT16 > 2 && live == 2) winograd_gemm_rb16s_block<(MT16 > 2 ? 2 : 1), NW16, PRE>(a, smem_s, comp, m0, n0, split);
-    else if (MT16 > 3 && live == 3) winograd_gemm_rb16s_block<(MT16 > 3 ? 3 : 1), NW16, PRE>(a, smem_s, comp, m0, n0, split);
-    else if (MT16 > 4 && live == 4) winograd_gemm_rb16s_block<(MT16 > 4 ? 4 : 1), NW16, PRE>(a, smem_s, comp, m0, n0, split);
+    if (live == MT16) winograd_gemm_rb16s_block<MT16, NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
+    else if (live == 1) winograd_gemm_rb16s_block<1, NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
+    else if (MT16 > 2 && live == 2) winograd_gemm_rb16s_block<(MT16 > 2 ? 2 : 1), NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
+    else if (MT16 > 3 && live == 3) winograd_gemm_rb16s_block<(MT16 > 3 ? 3 : 1), NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
+    else if (MT16 > 4 && live == 4) winograd_gemm_rb16s_block<(MT16 > 4 ? 4 : 1), NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
   } else {
-    winograd_gemm_rb16s_block<MT16, NW16, PRE>(a, smem_s, comp, m0, n0, split);
+    winograd_gemm_rb16s_block<MT16, NW16, PRE, NCH>(a, smem_s, comp, m0, n0, split);
   }
 }
 
@@ -1417,6 +1436,11 @@ static void pick_gemm_tile(int64_t T, int N, int Z, int cus, int* bm_out, int* b
 // winograd_gemm_split_kernel).  Process-wide setting (nfs_gemm_mode); NFS_GEMM_MODE presets it.
 static std::atomic<int> g_gemm_mode{[] { const char* e = getenv("NFS_GEMM_MODE"); return e ? (atoi(e) == 0 ? 0 : 1) : 1; }()};
 
+// 1: the split-limb kernel's K loop unrolled wherever an instance of the launch's chunk count is built (launch_gemm_inst);
+// 0: the rolled loop everywhere.  Bit-identical results.  An ablation switch like the ones above: NFS_RB16S_UNROLL=0
+// sets 0, read once per process (tests/test_gemm_unrolled_gpu.py runs both forms on one input in two processes).
+static const int g_gemm_unroll = [] { const char* e = getenv("NFS_RB16S_UNROLL"); return e && atoi(e) == 0 ? 0 : 1; }();
+
 // Which form of B a launch reads: the limb planes (6 bytes per filter value, no split in the kernel) from NFS_RB16S_PRE_ROWS
 // rows on, the float32 fragment pack split in registers (4 bytes per value) below -- a launch of a few dozen rows (one or
 // two views per GPU) is bound by its filter stream, 51 MB at conv4_x, and the planes would make that 77 (one view 0.958 ->
@@ -1485,7 +1509,22 @@ static void launch_gemm_inst(const WgGemmArgs& a, hipStream_t s) {
   } else {
     rec.split = 1;
     rec.bytes = a.Z * (4.0 * a.T * a.K + (PRE ? 6.0 : 4.0) * a.K * a.N + 4.0 * a.T * a.N * a.ksplit);   // V, filters, M
-    launch_gemm_kernel<winograd_gemm_rb16s_kernel<BM / 16, BN / 64, PRE>>(a, lds, blocks * a.ksplit, rec, s);
+    // the form of the K loop follows from the shape alone: the chunks per K part pick the unrolled kernel where one is
+    // built (K = 128 / 256 / 512 per part), every other count and NFS_RB16S_UNROLL=0 the rolled loop.  The same row of
+    // the instance table either way: the tuner times, and nfs_gemm_force pins, the form that runs.  Unrolled instances
+    // exist for the tiles of 48 | 80 rows x 64 | 128 columns (the same VGPRs as rolled, no spill); the taller and the
+    // 256-column tiles spill hundreds of VGPRs once the steps share a basic block and stay rolled
+    // (profiles/rb16s_unrolled_isa.txt).
+    auto launch = [&](auto nch) {
+      constexpr int NCH = BM <= 80 && BN <= 128 ? decltype(nch)::value : 0;
+      launch_gemm_kernel<winograd_gemm_rb16s_kernel<BM / 16, BN / 64, PRE, NCH>>(a, lds, blocks * a.ksplit, rec, s);
+    };
+    switch (g_gemm_unroll ? a.K / WG_KC / a.ksplit : 0) {
+      case 4: launch(std::integral_constant<int, 4>{}); break;
+      case 8: launch(std::integral_constant<int, 8>{}); break;
+      case 16: launch(std::integral_constant<int, 16>{}); break;
+      default: launch(std::integral_constant<int, 0>{});
+    }
   }
 }
 

@@ -53,8 +53,42 @@ def kernels(path):
     return out
 
 
+def matrix_span_table(path, pattern):
+    """`python tools/isa_streams.py --waits REGEX FILE.s`: one row per kernel whose demangled name matches REGEX -- VGPRs,
+    spilled VGPRs and scratch bytes (.vgpr_count / .vgpr_spill_count of the metadata, ScratchSize), code bytes
+    (codeLenInByte), and between the kernel's first and last MFMA the number of buffer loads and the histogram of the N
+    in `s_waitcnt vmcnt(N)`: how many global loads each wait leaves in flight.  A static count over every row-tile
+    variant the kernel holds (profiles/rb16s_unrolled_isa.txt)."""
+    text = open(path).read()
+    K = kernels(path)
+    names = demangle(list(K))
+    size = dict(re.findall(r"^([A-Za-z_][\w.$]*):.*?\n; codeLenInByte = (\d+)", text, re.M | re.S))
+    meta = {n: (int(v), int(sp)) for n, v, sp in
+            re.findall(r"\.name:\s+(\S+)\n(?:(?!\.name:).)*?\.vgpr_count:\s+(\d+)\n\s*\.vgpr_spill_count:\s+(\d+)", text, re.S)}
+    print("%-46s | VGPR | spill | scratch | code B | loads | vmcnt(N): count, between the first and the last MFMA" % "kernel")
+    for k in sorted(K, key=lambda k: names[k]):
+        short = re.sub(r"^(void )?nfs::", "", re.sub(r"\(.*$", "", names[k]))
+        if not re.search(pattern, short):
+            continue
+        body = K[k][0]
+        mf = [i for i, ln in enumerate(body) if ln.startswith("v_mfma")]
+        span = body[mf[0]:mf[-1] + 1] if mf else []
+        hist = {}
+        for ln in span:
+            m = re.match(r"s_waitcnt .*?vmcnt\((\d+)\)", ln)
+            if m:
+                hist[int(m.group(1))] = hist.get(int(m.group(1)), 0) + 1
+        loads = sum(ln.startswith("buffer_load") for ln in span)
+        print("%-46s | %4d | %5d | %7d | %6d | %5d | %s" % (
+            short, meta[k][0], meta[k][1], K[k][3], int(size[k]), loads,
+            " ".join("%d:%d" % (n, c) for n, c in sorted(hist.items()))))
+    return 0
+
+
 def main(argv):
-    maps = dict(a.split("=", 1) for i, a in enumerate(argv) if i and argv[i - 1] == "--map")
+    if len(argv) == 3 and argv[0] == "--waits":
+        return matrix_span_table(argv[2], argv[1])
+    maps =dict(a.split("=", 1) for i, a in enumerate(argv) if i and argv[i - 1] == "--map")
     files = [a for i, a in enumerate(argv) if a != "--map" and not (i and argv[i - 1] == "--map")]
     if len(files) != 2:
         sys.exit(__doc__)
