@@ -8,11 +8,83 @@ renderer and VGG as one batch, the field gradient accumulates over views in one 
 from __future__ import annotations
 
 import os
+import time
 
 import numpy as np
 import torch
 
 from . import ops, parallel
+
+HOST_BOUND = 0.85       # issue time over this share of the wall time: the GPU finished as soon as the host had issued the work
+
+
+class Stamp(object):
+    """what a stored result was computed from: the tensors' identities and their torch version counters.  An in-place
+    torch op on one of them (also through a ``detach()`` view, which shares the counter) or another tensor in its place
+    makes it stale; a write that bypasses the counter (``tensor.data``, a kernel called on ``data_ptr()``) is not seen."""
+    __slots__ = ("seen",)
+
+    def __init__(self, *tensors):
+        self.seen = tuple((t, t._version) for t in tensors)
+
+
+def holds(stamp, *tensors):
+    """do these same tensors, unmodified, still stand where ``stamp`` was taken?  (None or an empty stamp: never)"""
+    seen = stamp.seen if stamp is not None else ()
+    if not seen or len(seen) != len(tensors):
+        return False
+    for (t0, version), t in zip(seen, tensors):
+        if t0 is not t or version != t._version:
+            return False
+    return True
+
+
+class Replay(object):
+    """one captured hipGraph of ``body(*inputs)``, the key it was captured under and the static copies of its tensor
+    inputs (None entries pass through).  Called with ``(key, inputs, body)`` it drops a graph captured under another key,
+    captures where there is none, copies in the inputs that changed and replays; it returns what ``body`` returned under
+    capture (valid until the next replay).  Warm-up calls and the eager / graph choice are the caller's."""
+
+    def __init__(self):
+        self.graph = self.key = self.static = self.stamps = self.out = None
+
+    def stale(self, key):                # (a graph captured under ANOTHER key is held)
+        return self.graph is not None and key != self.key
+
+    def __call__(self, key, inputs, body):
+        if self.stale(key):
+            self.__init__()
+        if self.graph is None:
+            self.static = [None if t is None else t.clone() for t in inputs]
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self.out = body(*self.static)
+            self.graph, self.key = g, key
+            self.stamps = [None if t is None else Stamp(t) for t in inputs]
+        for i, t in enumerate(inputs):
+            # (the static buffer itself, or the same unmodified tensor as last time -- as just after a capture: no copy launch)
+            if t is not None and t is not self.static[i] and not holds(self.stamps[i], t):
+                self.static[i].copy_(t)
+                self.stamps[i] = Stamp(t)
+        self.graph.replay()
+        return self.out
+
+
+def issue_and_wall(fn):
+    """one call of ``fn`` between two synchronisations -> seconds (the host needed to issue it, until the GPU finished it)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    t_issue = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    return t_issue, time.perf_counter() - t0
+
+
+def graph_from_env():
+    """``NFS_GRAPH`` as True ('1': hipGraph replay forced on), None (unset: the choice is measured) or False (else: off)"""
+    env = os.environ.get("NFS_GRAPH")
+    return None if env is None else env == "1"
 
 
 def _channels(acts, name, F):
@@ -525,6 +597,20 @@ def loss_capture_key(L):
             None if cf is None else int(cf.data_ptr()), hist, id(getattr(L, "net", None)))
 
 
+def loss_gradient(loss, d, second, g_d=None, **kw):
+    """(losses, dL/dd) of ``loss`` at ``d``, the gradient in a buffer of its own (or in ``g_d``, which is overwritten).
+    ``second``: the view matrices of a RenderStyleLoss / the mask ``d_gray`` of an ImageStyleLoss; ``kw``: further
+    keywords of ``RenderStyleLoss.loss_and_grad``.  Where the loss can write the gradient without a zero fill
+    (``writes_gradient``) it gets the buffer as it is and ``overwrite=True``, otherwise a zeroed one to add into."""
+    if isinstance(loss, ImageStyleLoss):                 # (d, d_gray) -> (losses, gradient)
+        return loss.loss_and_grad(d, second)
+    if hasattr(loss, "writes_gradient") and loss.writes_gradient(1 if second is None else int(second.shape[0])):
+        g_d = torch.empty_like(d) if g_d is None else g_d
+        return loss.loss_and_grad(d, second, g_d, overwrite=True, **kw), g_d
+    g_d = torch.zeros_like(d) if g_d is None else g_d.zero_()
+    return loss.loss_and_grad(d, second, g_d, **kw), g_d
+
+
 class GraphedLoss(object):
     """``loss.loss_and_grad(d, rot, g_d)`` of a few views, replayed as ONE hipGraph where the host cannot keep up with
     it.  A one-view chain is 60-110 small launches: on a box with a slow host the host needs 1.1-1.4 ms to issue what
@@ -532,85 +618,57 @@ class GraphedLoss(object):
     smokegun configuration on Inception-v1 1.11 -> 0.97 ms); on a box whose host keeps up, eager submission is the
     faster of the two by ~10 % (graph nodes do not overlap their launch latencies the way back-to-back stream packets
     do).  Hosts differ by 2x between boxes of one pool, so the choice is MEASURED: call 1 runs eagerly (lazy state:
-    packed filters, tile tuner, workspaces); call 2 eagerly between two synchronisations, timing both what the host
-    needed to issue it and when the GPU finished -- if the GPU finished as soon as the host did (issue time > 85 % of the
-    wall time; calls 2-4 are timed this way and the MEDIAN ratio decides, so that one-off lazy work in one of them does
-    not) the chain is host-bound and calls 5.. are replays of a captured graph, otherwise it stays eager (``mode``
+    packed filters, tile tuner, workspaces); calls 2-4 eagerly too, each timed by ``issue_and_wall`` -- if the GPU
+    finished as soon as the host did (``HOST_BOUND``; the MEDIAN ratio decides, so that one-off lazy work in one of them
+    does not) the chain is host-bound and calls 5.. are replays of a captured graph, otherwise it stays eager (``mode``
     = 'graph' | 'eager'; ``force`` = True / False skips the trial: ``NFS_GRAPH=0/1`` is the reproducible setting, the
     measured choice can differ between hosts and runs).  A change of anything the capture bakes in
-    (``loss_capture_key``, shapes) starts over.  Inputs are copied into static buffers; the returned loss and gradient
-    tensors are valid until the next call."""
+    (``loss_capture_key``, shapes) starts over.  Changed inputs are copied into static buffers (``Replay``); the returned
+    loss and gradient tensors are valid until the next call."""
 
     def __init__(self, loss, force=None):
         self.loss = loss
         self.force = force
         self._reset()
 
+    @classmethod
+    def from_env(cls, loss):
+        """as ``NFS_GRAPH`` has it (``graph_from_env``): forced on, left to the trial, or False -- no replay at all"""
+        force = graph_from_env()
+        return False if force is False else cls(loss, force=force)
+
     def _reset(self):
-        self._graph = None
+        self._replay = Replay()
         self._key = None
         self._calls = 0
         self.mode = None if self.force is None else ("graph" if self.force else "eager")
         self.trial = None
         self._trials = []
 
-    def _eager(self, d, rot):
-        if isinstance(self.loss, ImageStyleLoss):        # (d, d_gray) -> (losses, gradient)
-            return self.loss.loss_and_grad(d, rot)
-        V = 1 if rot is None else int(rot.shape[0])
-        if hasattr(self.loss, "writes_gradient") and self.loss.writes_gradient(V):
-            g_d = torch.empty_like(d)
-            return self.loss.loss_and_grad(d, rot, g_d, overwrite=True), g_d
-        g_d = torch.zeros_like(d)
-        return self.loss.loss_and_grad(d, rot, g_d), g_d
+    @property
+    def _graph(self):
+        return self._replay.graph
 
     def __call__(self, d, rot):
-        import time
         key = (loss_capture_key(self.loss), tuple(d.shape), None if rot is None else tuple(rot.shape))
         if self._key is not None and key != self._key:
             self._reset()
         self._key = key
         self._calls += 1
         if self.mode == "eager" or self._calls == 1:
-            return self._eager(d, rot)
+            return loss_gradient(self.loss, d, rot)
         if self.mode is None:
             # three timed eager calls (2, 3, 4), the median ratio decides: one trial can catch one-off lazy work
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = self._eager(d, rot)
-            t_issue = time.perf_counter() - t0
-            torch.cuda.synchronize()
-            t_wall = time.perf_counter() - t0
-            self._trials.append((t_issue, t_wall))
+            out = []
+            self._trials.append(issue_and_wall(lambda: out.append(loss_gradient(self.loss, d, rot))))
             if len(self._trials) == 3:
                 self.trial = sorted(self._trials, key=lambda tw: tw[0] / tw[1])[1]
-                self.mode = "graph" if self.trial[0] > 0.85 * self.trial[1] else "eager"
+                self.mode = "graph" if self.trial[0] > HOST_BOUND * self.trial[1] else "eager"
                 if os.environ.get("NFS_VERBOSE"):
                     print("GraphedLoss: %s (issue %.3f ms of %.3f ms wall, median of 3; NFS_GRAPH=0/1 fixes the choice)"
                           % (self.mode, 1e3 * self.trial[0], 1e3 * self.trial[1]))
-            return out
-        if self._graph is None:
-            self._d = d.clone()
-            self._rot = None if rot is None else rot.clone()
-            self._gd = torch.zeros_like(d)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                if isinstance(self.loss, ImageStyleLoss):
-                    self._losses, self._gd = self.loss.loss_and_grad(self._d, self._rot)
-                elif hasattr(self.loss, "writes_gradient") and self.loss.writes_gradient(
-                        1 if self._rot is None else int(self._rot.shape[0])):
-                    self._losses = self.loss.loss_and_grad(self._d, self._rot, self._gd, overwrite=True)
-                else:
-                    self._gd.zero_()
-                    self._losses = self.loss.loss_and_grad(self._d, self._rot, self._gd)
-            self._graph = g
-        else:
-            self._d.copy_(d)
-            if rot is not None and rot.data_ptr() != self._rot.data_ptr():
-                self._rot.copy_(rot)
-        self._graph.replay()
-        return self._losses, self._gd
+            return out[0]
+        return self._replay(key, (d, rot), lambda d_, rot_: loss_gradient(self.loss, d_, rot_))
 
 
 class argparse_ns(object):
@@ -627,18 +685,21 @@ class TFAdamState(object):
         self.m = None
         self.v = None
         # OR of every live mask since m and v were zeroed (step_through_advect with a mask): voxels outside it still have
-        # m = v = +0.  Usable only while nothing but that kernel has written m or v (their version counters say)
+        # m = v = +0.  Usable only while nothing but that kernel has written m or v (their stamp, ``_ever_of``, says)
         self._ever = None
-        self._ever_key = None
+        self._ever_of = None
 
     def ever_mask(self):
-        """the mask above, or None when m or v have been written by anything else since they were zeroed (as seen by their
-        torch version counters: a write that bypasses them -- through ``.data``, or a kernel on ``m.data_ptr()`` -- is not
-        seen; set ``_ever = None`` after one)"""
-        if self._ever is None or self.m is None or self._ever_key != (self.m._version, self.v._version):
+        """the mask above, or None when m or v have been rebound or written by anything else since they were zeroed (a
+        write that bypasses their version counters, see ``Stamp``, is not seen: set ``_ever = None`` after one)"""
+        if self._ever is None or not holds(self._ever_of, self.m, self.v):
             self._ever = None
-            return None
         return self._ever
+
+    def advance(self):
+        """the beta powers of one more step (float32 variables multiplied once per step in TF), without an update"""
+        self.b1p = np.float32(self.b1p * self.b1)
+        self.b2p = np.float32(self.b2p * self.b2)
 
     def _begin_step(self, x, lr):
         """the scalar half of ApplyAdam for a variable of ``x``'s shape: m and v zeroed when missing or of another shape, the
@@ -647,9 +708,7 @@ class TFAdamState(object):
         if fresh:
             self.m = torch.zeros_like(x)
             self.v = torch.zeros_like(x)
-        # beta powers are float32 variables multiplied once per step in TF
-        self.b1p = np.float32(self.b1p * self.b1)
-        self.b2p = np.float32(self.b2p * self.b2)
+        self.advance()
         lr_t = np.float32(lr) * np.sqrt(np.float32(1.0) - self.b2p) / (np.float32(1.0) - self.b1p)
         return fresh, (float(lr_t), float(self.b1), float(self.b2), float(self.eps))
 
@@ -671,17 +730,14 @@ class TFAdamState(object):
         its live mask.  ``live_current``: ``live_next`` holds the mask of the CURRENT sample on entry (and ``adv_next`` that
         sample) -- the waves whose voxels never were live are then left out (``ever_mask``)"""
         fresh, hyper = self._begin_step(vel, lr)
-        if fresh:
-            self._ever = None
-        if fresh and live_next is not None:
-            self._ever = torch.zeros_like(live_next)
-            self._ever_key = (self.m._version, self.v._version)
+        if fresh:                            # (fresh state: m = v = +0 everywhere, the empty mask covers them)
+            self._ever = None if live_next is None else torch.zeros_like(live_next)
+            self._ever_of = Stamp(self.m, self.v)
         ever = self.ever_mask() if (live_current and live_next is not None and adv_next is not None) else None
-        tracked = self._ever is not None and self._ever_key == (self.m._version, self.v._version)
         ops.advect_bwd_adam(d0, vel, g_adv, self.m, self.v, *hyper, adv_next=adv_next, live_next=live_next, ever=ever)
         if ever is not None:
-            self._ever_key = (self.m._version, self.v._version)      # (our own write: the mask stays usable)
-        elif tracked:
+            self._ever_of = Stamp(self.m, self.v)                    # (our own write: the mask stays usable)
+        else:
             self._ever = None                                        # (a step without the mask update: it no longer covers m, v)
 
     def step_through_advect_slab(self, vel_slab, d0, g_adv_slab, z0, lr, adv_next=None):
@@ -827,18 +883,17 @@ class GridStylizer(object):
         # (measured: 200^3 x 8 views 3.98 -> 3.90 ms, 200^3 x 1 view 1.35 -> 1.41 ms, 100^3 x 1 view 1.20 -> 1.06 ms:
         # it pays where the step is shorter than the 1.15 ms the host needs to issue it).  None = decide at the first
         # step from the problem size; NFS_GRAPH=0/1 or the constructor argument override.
-        env = os.environ.get("NFS_GRAPH")
-        self.use_graph = (None if env is None else env == "1") if graph is None else bool(graph)
-        self._graph = None
-        self._graph_key = None
-        self._graph_rot = None
-        self._graph_total = None
-        self._graph_warm = 0
+        self.use_graph = graph_from_env() if graph is None else bool(graph)
+        self.graph_trial = None                      # (t_issue, t_wall) of the measured choice, once it has been made
+        self._steps_seen = 0
+        self._replay = None                          # (None: before the eager call that precedes a capture)
+        self.d_s = self.d_adv = None                 # the smoothed / advected density of the current forward
+        self._for_variable = target != "d"           # (step(), gradient(): see field_gradient)
         self._pending = None
         self._owns_buffers = False
         # advect(d0, var) of the NEXT iteration written by the Adam kernel of this one (ops.advect_bwd_adam(adv_next=...)):
-        # the buffer, and what it was computed from (tensor identities + torch version counters; any in-place torch op on
-        # the variable or the density, a bind() or a re-assignment makes it stale and the forward advect runs by itself)
+        # the buffer, and the stamp of what it was computed from (any in-place torch op on the variable or the density, a
+        # bind() or a re-assignment makes it stale and the forward advect runs by itself)
         self.fuse_advect = os.environ.get("NFS_FUSE_ADVECT", "1") != "0"
         self._adv_buf = None
         self._adv_src = None
@@ -848,7 +903,8 @@ class GridStylizer(object):
         # The update is bit-identical with it on and off (tests/test_dead_skip_gpu.py); NFS_DEAD_SKIP=0 turns it off.
         self.dead_skip = os.environ.get("NFS_DEAD_SKIP", "1") != "0"
         self._live_buf = None
-        self._live_mark = None
+        self._live_shape = None
+        self._live_mark = None                       # the stamp (``_adv_src`` itself) of the advect that wrote the mask
         D, H, W = d0.shape
         if target == "v":
             self.var = torch.zeros(D, H, W, 3, dtype=torch.float32, device=d0.device)
@@ -948,7 +1004,7 @@ class GridStylizer(object):
         D, H, W = self.d0.shape
         if self.use_graph:
             self._forward_field_slab()                                  # (holds a collective: outside the graph)
-            self._loss_gradient_graphed(rot_local)
+            self._field_gradient_graphed(rot_local, with_field=False)
         else:
             losses, _ = self.field_gradient(rot_local)
             torch.sum(losses, dim=0, keepdim=True, out=self._loss_slot)
@@ -968,8 +1024,7 @@ class GridStylizer(object):
             if adv is not None:
                 self._adv_mark()
         else:
-            self.adam.b1p = np.float32(self.adam.b1p * self.adam.b1)      # (an idle rank keeps the step count)
-            self.adam.b2p = np.float32(self.adam.b2p * self.adam.b2)
+            self.adam.advance()                                         # (an idle rank keeps the step count)
         return total
 
     def bind(self, d0, var=None, adam=None):
@@ -1032,7 +1087,7 @@ class GridStylizer(object):
         return self.var if self.target == "v" else ops.source_velocity(self.target, self.var)
 
     def _adv_mark(self, live=False):
-        self._adv_src = (self.var, self.var._version, self.d0, self.d0._version)
+        self._adv_src = Stamp(self.var, self.d0)
         self._live_mark = self._adv_src if live else None
 
     def _live_target(self):
@@ -1048,6 +1103,7 @@ class GridStylizer(object):
         return self._live_buf
 
     def _live_valid(self):
+        """the mask belongs to exactly the advect that wrote it, and that advect is still current"""
         return (self._live_buf is not None and self._live_mark is not None and self._live_mark is self._adv_src
                 and self._adv_valid())
 
@@ -1058,16 +1114,12 @@ class GridStylizer(object):
         return {"live": self._live_buf, "dilate": 1 if self.k > 0 else 0}
 
     def invalidate_forward(self):
-        """forget the stored forward advect.  In-place torch ops on ``var`` / ``d0`` (also through ``detach()`` views, which
-        share the version counter), ``bind()`` and re-assignment are noticed by themselves; a write that bypasses the
-        counter -- through ``tensor.data``, or by a kernel called on ``var.data_ptr()`` directly -- is not: call this
-        after one."""
+        """forget the stored forward advect.  In-place torch ops on ``var`` / ``d0``, ``bind()`` and re-assignment are
+        noticed by themselves; a write that bypasses the version counter (see ``Stamp``) is not: call this after one."""
         self._adv_src = None
 
     def _adv_valid(self):
-        a = self._adv_src
-        return (a is not None and self._adv_buf is not None and a[0] is self.var and a[1] == self.var._version
-                and a[2] is self.d0 and a[3] == self.d0._version)
+        return self._adv_buf is not None and holds(self._adv_src, self.var, self.d0)
 
     def _advect_now(self):
         """d_adv = advect(d0, var) -- from the previous step's Adam kernel when it is still current, else computed here
@@ -1108,10 +1160,7 @@ class GridStylizer(object):
         if self.slab is not None:
             return self._forward_field_slab()
         self._apply_binding()
-        if self.target != "d":
-            self.d_adv = self._advect_now()
-        else:
-            self.d_adv = self.var
+        self.d_adv = self._advect_now() if self._for_variable else self.var
         self.d_s = ops.smooth3d_relu_fwd(self.d_adv, self.k)
         return self.d_s
 
@@ -1125,17 +1174,10 @@ class GridStylizer(object):
     def _loss_gradient(self, d_s, rot_local, total=False, live_kw=None):
         """total: let the loss write the summed loss of the local views into the loss slot where it can (then None is
         returned instead of the per-view losses)"""
-        V = rot_local.shape[0]
-        fresh = hasattr(self.loss, "writes_gradient") and self.loss.writes_gradient(V)
-        if not fresh:
-            self.g_ds.zero_()
-        kw = {"overwrite": True} if fresh else {}
-        if live_kw:
-            kw.update(live_kw)
-        if total and hasattr(self.loss, "sums_total") and self.loss.sums_total(V):
+        kw = dict(live_kw or ())
+        if total and hasattr(self.loss, "sums_total") and self.loss.sums_total(rot_local.shape[0]):
             kw["total_out"] = self._loss_slot
-        losses = self.loss.loss_and_grad(d_s, rot_local, self.g_ds, **kw)
-        return losses, self.g_ds
+        return loss_gradient(self.loss, d_s, rot_local, g_d=self.g_ds, **kw)
 
     def variable_gradient(self, g_ds):
         """adjoint of smooth+max and advect: dL/d variable from dL/d d_s (deterministic kernels: every
@@ -1163,7 +1205,7 @@ class GridStylizer(object):
 
     def gradient(self, rot_local):
         """one forward+backward over the local views; returns (loss_per_view, grad wrt variable)"""
-        losses, g_ds = self.field_gradient(rot_local, for_variable=self.target != "d")
+        losses, g_ds = self.field_gradient(rot_local, for_variable=self._for_variable)
         return losses, self.variable_gradient(g_ds)
 
     def _capture_key(self, rot_local):
@@ -1173,68 +1215,35 @@ class GridStylizer(object):
         return loss_capture_key(self.loss) + (int(self.d0.data_ptr()), int(self.var.data_ptr()),
                                               tuple(rot_local.shape), self.k, self.target)
 
-    def _loss_gradient_graphed(self, rot_local):
-        """the graph without the field ops (slab mode: their all-gather stays outside the capture)"""
-        return self._field_gradient_graphed(rot_local, with_field=False)
-
     def _field_gradient_graphed(self, rot_local, with_field=True):
         """field_gradient as one hipGraph: the first call runs eagerly (lazy state: packed Winograd filters, side
-        streams, workspaces), the second is captured, later ones replay.  The capture is keyed on what it bakes in
+        streams, workspaces), the second is captured, later ones replay (``with_field=False``: the graph without the
+        field ops -- slab mode, their all-gather stays outside the capture).  The capture is keyed on what it bakes in
         (style / content targets, loss hyper-parameters, the addresses of d0 and the variable, the number of views):
-        when any of that changes the graph is dropped and captured again.  The view matrices are copied into a
-        static buffer."""
-        body = ((lambda r: self.field_gradient(r, total=True, for_variable=self.target != "d")) if with_field
-                else (lambda r: self._loss_gradient(self.d_s, r, total=True)))
-
-        def to_slot(losses):              # (None: the loss chain has written the total into the slot itself)
-            if losses is not None:
+        when any of that changes the graph is dropped and, after one more eager call, captured again.  The view matrices
+        are copied into a static buffer where they changed (``Replay``)."""
+        def body(r):
+            losses, _ = (self.field_gradient(r, total=True, for_variable=self._for_variable) if with_field
+                         else self._loss_gradient(self.d_s, r, total=True))
+            if losses is not None:        # (None: the loss chain has written the total into the slot itself)
                 torch.sum(losses, dim=0, keepdim=True, out=self._loss_slot)     # one kernel: reduce straight into the slot
-        if with_field and self.target != "d" and self._adv_target() is not None:
+        if with_field and self._for_variable and self._adv_target() is not None:
             # the captured forward starts from the advected density in its fixed buffer: bring it up to date eagerly when
             # the previous step's Adam kernel has not left it there (first step, a re-bound frame, a variable set by hand)
             self._apply_binding()
             self._advect_now()
         key = self._capture_key(rot_local) + (with_field, self._adv_target() is not None,
                                               with_field and bool(self._live_kw()))
-        if self._graph is not None and key != self._graph_key:
-            self._graph = None
-            self._graph_warm = 0
-        if self._graph is None:
-            if self._graph_warm < 1:
-                self._graph_warm += 1
-                losses, g_ds = body(rot_local)
-                to_slot(losses)
-                return self._loss_slot, g_ds
-            self._graph_rot = rot_local.clone()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                losses, _ = body(self._graph_rot)
-                to_slot(losses)
-            self._graph = g
-            self._graph_key = key
-            self._graph_rot_src = (rot_local, rot_local._version)
-        elif rot_local.data_ptr() != self._graph_rot.data_ptr():
-            # (the same tensor object, not modified in place since it was copied: nothing to copy -- a launch per step)
-            src = getattr(self, "_graph_rot_src", None)
-            if src is None or src[0] is not rot_local or src[1] != rot_local._version:
-                self._graph_rot.copy_(rot_local)
-                self._graph_rot_src = (rot_local, rot_local._version)
-        self._graph.replay()
+        if self._replay is None or self._replay.stale(key):
+            self._replay = Replay()       # (one eager call before the first capture and after every dropped graph)
+            body(rot_local)
+        else:
+            self._replay(key, (rot_local,), body)
         return self._loss_slot, self.g_ds
 
-    def _loss_chain_host_bound(self, rot_local):
-        """one extra evaluation of the loss chain between two synchronisations: True when the GPU finishes it as soon as
-        the host has issued it (issue time > 85 % of the wall time), i.e. when a hipGraph replay would be faster"""
-        import time
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        self._loss_gradient(self.d_s, rot_local)
-        t_issue = time.perf_counter() - t0
-        torch.cuda.synchronize()
-        t_wall = time.perf_counter() - t0
-        self.graph_trial = (t_issue, t_wall)
-        return t_issue > 0.85 * t_wall
+    @property
+    def _graph(self):
+        return None if self._replay is None else self._replay.graph
 
     def step(self, rot_local, loss_view=False):
         """one iteration: loss + gradient of the local views, the exchange, the update; returns the summed loss (a 0-d
@@ -1251,32 +1260,30 @@ class GridStylizer(object):
                 # bound, but a host of the same pool that is 2x slower (measured: 20 us per launch instead of 9) turns
                 # the very same step host-bound, at 8 views as at 1.  So the choice is measured at the second step (the
                 # first has built the lazy state); until then the step runs eagerly.
-                self._steps_seen = getattr(self, "_steps_seen", 0) + 1
-                if self._steps_seen == 2 and getattr(self, "d_s", None) is not None:
-                    self.use_graph = self._loss_chain_host_bound(rot_local)
+                # (by one extra evaluation of the loss chain: host-bound is where a hipGraph replay would be faster)
+                self._steps_seen += 1
+                if self._steps_seen == 2 and self.d_s is not None:
+                    t_issue, t_wall = self.graph_trial = issue_and_wall(lambda: self._loss_gradient(self.d_s, rot_local))
+                    self.use_graph = t_issue > HOST_BOUND * t_wall
         if self.slab is not None:
             return self._step_slab(rot_local)
         self._apply_binding()
+        total = None                      # (None: the total of the local views is in the loss slot)
         if self.use_graph:
-            total, g_ds = self._field_gradient_graphed(rot_local)
-        elif self.pg is None:
-            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target != "d")
-            total = self._loss_slot if losses is None else None
-            total_new = None if losses is None else losses.sum()             # (one kernel, a fresh tensor: no slot, no copy)
+            _, g_ds = self._field_gradient_graphed(rot_local)
         else:
-            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self.target != "d")
-            if losses is not None:
+            losses, g_ds = self.field_gradient(rot_local, total=True, for_variable=self._for_variable)
+            if losses is not None and self.pg is None:
+                total = losses.sum()                                         # (one kernel, a fresh tensor: no slot, no copy)
+            elif losses is not None:
                 torch.sum(losses, dim=0, keepdim=True, out=self._loss_slot)  # (one kernel: reduce straight into the slot)
-            total = self._loss_slot
         if self.pg is not None:
             # The one exchange step (RCCL over xGMI): ONE all-reduce of gradient + loss.  The reduction is placed on
             # the 4*G^3-byte density gradient, not on the 12*G^3-byte velocity gradient: everything below it is
             # linear and replicated, so reducing early moves 3x fewer bytes over the links.
             parallel.all_reduce_sum_([self._gbuf], group=self.pg)
-        if total is not None:
-            total = total[0] if (loss_view and self.pg is None) else total[0].clone()
-        else:
-            total = total_new
+        if total is None:
+            total = self._loss_slot[0] if (loss_view and self.pg is None) else self._loss_slot[0].clone()
         if self._fused_step_ok():
             g_adv = ops.smooth3d_relu_bwd(self.d_s, g_ds, self.k)
             adv = self._adv_target()

@@ -177,9 +177,7 @@ class Styler(StylerBase):
                     if self._graph_loss is None:
                         # the loss chain of one colour image is ~40 small launches: hipGraph replay where a measured
                         # trial finds the host cannot keep up with it (engine.GraphedLoss; NFS_GRAPH=0 / 1 forces)
-                        env = os.environ.get("NFS_GRAPH")
-                        self._graph_loss = (engine.GraphedLoss(self.loss, force=True) if env == "1" else
-                                            engine.GraphedLoss(self.loss) if env is None else False)
+                        self._graph_loss = engine.GraphedLoss.from_env(self.loss)
                     if self._graph_loss:
                         losses, g_d = self._graph_loss(d.detach().contiguous(), d_gray)
                     else:

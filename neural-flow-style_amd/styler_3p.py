@@ -23,8 +23,6 @@ Differences from the reference, all deliberate and documented:
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -156,18 +154,12 @@ class Styler(StylerBase):
             # submission) with one or two views per call; NFS_GRAPH=0 / 1 forces it off / on.  The GraphedLoss object is
             # made once; whether THIS call goes through it depends on this call's view count (it keys its capture on
             # the shapes and starts over when they change)
-            env = os.environ.get("NFS_GRAPH")
-            self._graph_loss = (engine.GraphedLoss(self.loss, force=True) if env == "1" else
-                                engine.GraphedLoss(self.loss) if env is None else False)
+            self._graph_loss = engine.GraphedLoss.from_env(self.loss)
         if self._graph_loss and (self._graph_loss.force or nviews <= 2):
             losses, g_d = self._graph_loss(d3, rot)
             losses = losses.clone()
-        elif self.loss.writes_gradient(nviews):
-            g_d = torch.empty_like(d3)                       # (written, not accumulated into: no zero fill)
-            losses = self.loss.loss_and_grad(d3, rot, g_d, overwrite=True)
         else:
-            g_d = torch.zeros_like(d3)
-            losses = self.loss.loss_and_grad(d3, rot, g_d)
+            losses, g_d = engine.loss_gradient(self.loss, d3, rot)
         # view-independent terms (pressure / density preservation) belong to the iteration, not to a view: with the
         # views sharded over ranks (views=sum) only rank 0 adds them, so that the all-reduced loss and gradient
         # contain them ONCE (every rank would otherwise contribute a copy: world x the single-rank weight)

@@ -261,3 +261,15 @@ def test_never_live_waves_are_left_out_of_the_adam_kernel_only_while_the_moments
         gs.step(rot); ref.step(rot)
     assert gs.adam.ever_mask() is not None
     assert torch.equal(gs.var, ref.var) and torch.equal(gs.adam.m, ref.adam.m) and torch.equal(gs.adam.v, ref.adam.v)
+    # the moments re-bound to ANOTHER tensor (non-zero also where no voxel ever was live) whose version counter happens
+    # to equal the old one's: the mask is the old tensor's, not this one's
+    for s in (gs, ref):
+        old = s.adam.m
+        s.adam.m = old + 1e-3
+        while s.adam.m._version < old._version:
+            torch.autograd.graph.increment_version(s.adam.m)
+        assert s.adam.m._version == old._version and s.adam.m is not old
+    assert gs.adam.ever_mask() is None
+    for _ in range(2):
+        gs.step(rot); ref.step(rot)
+    assert torch.equal(gs.var, ref.var) and torch.equal(gs.adam.m, ref.adam.m) and torch.equal(gs.adam.v, ref.adam.v)

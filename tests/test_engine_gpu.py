@@ -682,3 +682,68 @@ def test_graphed_loss_replays_equal_eager_calls_with_several_graphs_alive():
         l_a, g_a = auto(d, rot)
     assert auto.mode in ("graph", "eager") and auto.trial is not None
     assert rel(l_a, l_e) < 1e-5 and rel(g_a, g_e) < 1e-5
+
+
+@pytest.mark.parametrize("user", ["grid_stylizer", "graphed_loss"])
+def test_replay_takes_the_views_it_is_given_however_they_arrive(user):
+    """the two users of engine.Replay -- GridStylizer(graph=True) stepping, GraphedLoss(force=True) called -- against an
+    eager twin given the same views: warm-up and capture, a replay with the same unmodified view tensor (no copy), the
+    same tensor overwritten in place, another tensor of equal shape, and the first one again.  Loss and gradient (for
+    the stylizer: the variable after the step) are bit-equal at every stage, and no stage captures again"""
+    layers = ["conv1_1", "conv2_1", "conv3_1"]
+    G = 24 if user == "grid_stylizer" else 20
+    d0, vel0, mats, loss, cfg, w_or, sfe, T, eng = _setup(G, 2, layers)
+    a, b, c = (T.rot_to_device(uniform_views(6)[i:i + 2], "cuda") for i in (0, 2, 4))
+    # (the three view sets matter: a stage replayed on stale matrices cannot equal its twin by accident)
+    probe = []
+    for views in (a, b, c):
+        g = torch.zeros(G, G, G, device="cuda")
+        loss.loss_and_grad(torch.tensor(d0).cuda(), views, g)
+        probe.append(g)
+    assert not torch.equal(probe[0], probe[1]) and not torch.equal(probe[1], probe[2]) and not torch.equal(probe[0], probe[2])
+    rot = a.clone()
+    if user == "grid_stylizer":
+        twins = []
+        for graph in (True, False):
+            gs = eng.GridStylizer(loss, torch.tensor(d0).cuda(), k=3, target="v", lr=1e-3, graph=graph)
+            gs.var.copy_(torch.tensor(vel0))
+            twins.append(gs)
+        replayed = twins[0]
+
+        def both(views, it):
+            out = [(gs.step(views).clone(), gs.var.clone()) for gs in twins]
+            return out[0], out[1]
+    else:
+        replayed = eng.GraphedLoss(loss, force=True)
+        eager = eng.GraphedLoss(loss, force=False)
+        rng = np.random.RandomState(5)
+        base = blob_density(G, rng)
+
+        def both(views, it):
+            d = torch.tensor(base * (1 + 0.1 * it), device="cuda")              # (the density changes with every call)
+            out = []
+            for fn in (replayed, eager):
+                l, g = fn(d, views)
+                out.append((l.clone(), g.clone()))
+            return out[0], out[1]
+    stages = [("warm-up", rot), ("capture", rot), ("same tensor, unmodified", rot), ("overwritten in place", b),
+              ("another tensor", c), ("the first tensor again", rot), ("same tensor, unmodified", rot)]
+    graph = None
+    for it, (stage, views) in enumerate(stages):
+        if stage == "overwritten in place":
+            rot.copy_(views)
+            views = rot
+        got, want = both(views, it)
+        for x, y in zip(got, want):
+            assert torch.equal(x, y), (user, stage)
+        if stage == "warm-up":
+            assert replayed._graph is None
+        elif stage == "capture":
+            graph = replayed._graph
+            assert graph is not None
+        else:
+            assert replayed._graph is graph, (user, stage)
+            # the views' stamp is taken anew exactly when they were copied into the static buffer
+            assert (replayed._replay.stamps[-1] is stamp) == (stage == "same tensor, unmodified"), (user, stage)
+        stamp = None if graph is None else replayed._replay.stamps[-1]
+    assert (eager if user == "graphed_loss" else twins[1])._graph is None
