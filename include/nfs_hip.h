@@ -38,7 +38,7 @@ extern "C" {
 
 /* what nfs_version() returns, as 100 major + 10 minor + patch (the changelog is at its definition, csrc/api.hip); the
  * Python binding refuses a library that reports another number than the header it reads */
-#define NFS_ABI_VERSION 157
+#define NFS_ABI_VERSION 158
 
 typedef void* nfs_stream_t;
 
@@ -494,6 +494,23 @@ int64_t nfs_conv3x3_relu_bits_words(int B, int H, int W, int Ci, int Co, int poo
  * gradient: K = Co, N = Ci; pooled != 0: the fused-pool forms): 2*36*T4*K*N for F(4x4,3x3), 2*49*T5*K*N for F(5x5,3x3),
  * the direct 2*B*H*W*9*K*N otherwise.  The path is a function of the shapes alone, so this is too (measurement aid). */
 double nfs_conv3x3_executed_flops(int B, int H, int W, int K, int N, int pooled);
+/* Which kernels the conv call for K input / N output channels of its kernel runs (forward: K = Ci, N = Co; data
+ * gradient: K = Co, N = Ci; pooled: 0 the plain call, 1 a fused-pool form, 2 the pooled data gradient that masks from the
+ * float output x_out instead of the ReLU bit cache) when it is given a workspace of
+ * nfs_conv3x3_workspace_floats.  Launches nothing; computed by the helpers the launch itself calls.  out[0..11]:
+ *   0 family: 0 generic 3-channel kernel, 1 conv1_1 MFMA kernel (3 <-> 64 channels), 2 direct implicit GEMM,
+ *             3 F(4x4) Winograd in three kernels, 4 F(4x4) in the single kernel, 5 F(5x5)
+ *   1 ragged: H or W is no multiple of the family's tile (4 x 4, 5 x 5; conv1_1: 8 x 16 forward, 14 x 14 gradient; direct:
+ *             the pixel tile chosen for the row-stacked batch)
+ *   2, 3 schedule of the input / output transform: 1 six (F(5x5): seven) waves per block, 0 a thread per item, -1 none
+ *   4 K parts (Winograd: of the batched GEMM; direct: split-K)
+ *   5 tiles (Winograd tiles, conv1_1 tiles, direct pixel tiles)
+ *   6 blocks: conv1_1: blocks that walk the tiles (fewer than tiles: the walk wraps); single kernel: runs of 16 tiles x
+ *             64-channel groups; direct: the grid; 0 otherwise
+ *   7 Winograd: batches Z of the GEMM (36, 49; 0 on the single kernel); direct: the column tile (64 | 128)
+ *   8..11 the direct implicit GEMM the same call runs WITHOUT a workspace (K, N >= 32): column tile, K parts (1), ragged
+ *             pixel tile, pixel tiles; zeros with 3 channels */
+int nfs_conv3x3_plan(int B, int H, int W, int K, int N, int pooled, int* out);
 /* y = relu?(conv(x) + bias); x [B,H,W,Ci], y [B,H,W,Co]; bias nullable; relu_bits nullable (written) */
 int nfs_conv3x3_fwd(const float* x, const float* packed_fwd, const float* bias, float* y,
                     int B, int H, int W, int Ci, int Co, int relu,

@@ -17,6 +17,7 @@
 //   k order inside a chunk is permuted identically for A and B, which a sum permits.
 // Weights are frozen, so they are packed once on the device into [chunk][tap][N][32].
 #include "common.h"
+#include "winograd_gemm.h"
 
 #include <mutex>
 #include <stdlib.h>
@@ -617,6 +618,41 @@ static bool takes_fused_pool(const ConvArgs& a, const float* ws, int64_t ws_floa
   return tile4 && !off && takes_winograd(a, ws, ws_floats);
 }
 
+// the direct implicit GEMM of a call: its pixel tile, column tile and K parts (launch_conv runs it, nfs_conv3x3_plan reports it)
+struct DirectPlan { int TH, TW, tiles_r, tiles_c, bn, ksplit; };
+static DirectPlan plan_direct(int B, int H, int W, int Kc, int Nc, int64_t ws_floats) {
+  DirectPlan d{0, 0, 0, 0, 64, 1};
+  pick_tile(B, H, W, d.TH, d.TW, d.tiles_r, d.tiles_c);
+  if (d.TH <= 0) return d;
+  const ConvPlan plan = plan_conv(d.tiles_r * d.tiles_c, Nc, Kc / KC, (int64_t)B * H * W * Nc, ws_floats);
+  d.bn = plan.bn;
+  d.ksplit = plan.ksplit;
+  return d;
+}
+
+// conv1_1 (3 <-> 64 channels) on the MFMA kernels: the tiles of a launch and the blocks that walk them (per_cu blocks per
+// CU once there are more tiles than that; 0: one block per tile).  NFS_C3_OLD: the generic kernels (timing comparisons).
+struct C3Grid { int tiles_x, tiles_y; int64_t ntiles; unsigned blocks; };
+static C3Grid c3_grid(int B, int H, int W, int tw, int th, int per_cu) {
+  C3Grid g{(W + tw - 1) / tw, (H + th - 1) / th, 0, 0};
+  g.ntiles = (int64_t)B * g.tiles_x * g.tiles_y;
+  const int64_t cap = 256 * (int64_t)per_cu;
+  g.blocks = (unsigned)(per_cu > 0 && g.ntiles > cap ? cap : g.ntiles);
+  return g;
+}
+static bool c3_old() { static const bool old_c3 = getenv("NFS_C3_OLD") != nullptr; return old_c3; }
+static C3Grid c3_fwd_grid(int B, int H, int W) {
+  static const int per_cu = [] { const char* e = getenv("NFS_C3F_BLOCKS"); return e ? atoi(e) : 4; }();   // (27.1 us with 0, 25.2 with 4)
+  return c3_grid(B, H, W, C3F_TW, C3F_TH, per_cu);
+}
+static C3Grid c3_dgrad_grid(int B, int H, int W) {
+  // blocks per CU of the tile-walking form (0: one block per tile, as before round 4).  8 x 200 x 200, 8 x 16 tiles:
+  // 44.3 us with 0, 38.6 / 38.2 / 38.8 / 40.5 / 41.1 with 2 / 3 / 4 / 6 / 8; 14 x 14 tiles: 38.5 with 0, 34.1 / 36.5 /
+  // 36.9 with 2 / 3 / 4 (tools/conv11_bench.py)
+  static const int per_cu = [] { const char* e = getenv("NFS_C3D_BLOCKS"); return e ? atoi(e) : 2; }();
+  return c3_grid(B, H, W, C3D_TW, C3D_TH, per_cu);
+}
+
 template <int MODE>
 static int launch_conv(const ConvArgs& base, float* ws, int64_t ws_floats, hipStream_t s, float* ypool = nullptr,
                        const float* xmask = nullptr, uint32_t* in_bits = nullptr, uint32_t* out_bits = nullptr,
@@ -629,13 +665,13 @@ static int launch_conv(const ConvArgs& base, float* ws, int64_t ws_floats, hipSt
                          ypool, xmask, cache ? in_bits : nullptr, cache ? out_bits : nullptr, pooled_grad);
   }
   NFS_REQUIRE(!ypool && !xmask && !pooled_grad, "conv3x3: fused pooling needs the Winograd path");
-  int tiles_r = 0;
-  a.TH = 0;
-  pick_tile(a.B, a.H, a.W, a.TH, a.TW, tiles_r, a.tiles_c);
+  const DirectPlan plan = plan_direct(a.B, a.H, a.W, a.Kc, a.Nc, ws ? ws_floats : 0);
+  a.TH = plan.TH;
+  a.TW = plan.TW;
+  a.tiles_c = plan.tiles_c;
   NFS_REQUIRE(a.TH > 0, "conv3x3: no valid tile for %dx%dx%d", a.B, a.H, a.W);
-  const int mtiles = tiles_r * a.tiles_c;
+  const int mtiles = plan.tiles_r * a.tiles_c;
   const int64_t mn = (int64_t)a.B * a.H * a.W * a.Nc;
-  const ConvPlan plan = plan_conv(mtiles, a.Nc, a.Kc / KC, mn, ws ? ws_floats : 0);
   a.ksplit = plan.ksplit;
   a.ws = ws;
 #ifdef NFS_ABLATE
@@ -730,6 +766,62 @@ double nfs_conv3x3_executed_flops(int B, int H, int W, int K, int N, int pooled)
   return 2.0 * (m + 2) * (m + 2) * B * ((H + m - 1) / m) * ((W + m - 1) / m) * (double)K * N;
 }
 
+// What the conv call for K input / N output channels of its kernel runs when it is given a full workspace
+// (nfs_conv3x3_workspace_floats); launches nothing.  Every field comes from the helper the launch itself calls.
+int nfs_conv3x3_plan(int B, int H, int W, int K, int N, int pooled, int* out) {
+  NFS_REQUIRE(out, "nfs_conv3x3_plan: null pointer");
+  NFS_REQUIRE(B > 0 && H > 0 && W > 0 && K > 0 && N > 0, "nfs_conv3x3_plan: non-positive dimension");
+  for (int i = 0; i < 12; ++i) out[i] = 0;
+  out[2] = out[3] = -1;
+  out[4] = 1;
+  if (K == 3 || N == 3) {
+    NFS_REQUIRE(!pooled, "nfs_conv3x3_plan: no pooled form with 3 channels");
+    NFS_REQUIRE(K == 3 ? N % 64 == 0 : K % 32 == 0, "nfs_conv3x3_plan: 3 channels against a multiple of 64 (32 for the gradient)");
+    if ((K == 64 || N == 64) && !c3_old()) {
+      const C3Grid g = K == 3 ? c3_fwd_grid(B, H, W) : c3_dgrad_grid(B, H, W);
+      const int tw = K == 3 ? C3F_TW : C3D_TW, th = K == 3 ? C3F_TH : C3D_TH;
+      out[0] = 1;
+      out[1] = (H % th) != 0 || (W % tw) != 0;
+      out[5] = (int)g.ntiles;
+      out[6] = (int)g.blocks;
+    }
+    return NFS_OK;
+  }
+  NFS_REQUIRE(K % 32 == 0 && N % 64 == 0, "nfs_conv3x3_plan: K %% 32, N %% 64 required");
+  NFS_REQUIRE(!pooled || (H > 1 && W > 1), "nfs_conv3x3_plan: the pooled forms need H, W >= 2");
+  // the direct implicit GEMM: what the call runs without a workspace (out[8..11]) ...
+  const DirectPlan d0 = plan_direct(B, H, W, K, N, 0);
+  NFS_REQUIRE(d0.TH > 0, "nfs_conv3x3_plan: no valid tile for %dx%dx%d", B, H, W);
+  out[8] = d0.bn;
+  out[9] = d0.ksplit;
+  out[10] = ((int64_t)B * H) % d0.TH != 0 || W % d0.TW != 0;
+  out[11] = d0.tiles_r * d0.tiles_c;
+  ConvArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, K, N, 0, 0, 0, 1, 1, 0};
+  float dummy = 0.f;
+  if (!takes_winograd(a, &dummy, INT64_MAX)) {
+    // ... and with one, where Winograd does not take the shape (the same tile, K parts by plan_conv)
+    const DirectPlan d = plan_direct(B, H, W, K, N, nfs_conv3x3_workspace_floats(B, H, W, K, N));
+    out[0] = 2;
+    out[1] = out[10];
+    out[4] = d.ksplit;
+    out[5] = d.tiles_r * d.tiles_c;
+    out[6] = out[5] * (N / d.bn) * d.ksplit;
+    out[7] = d.bn;
+    return NFS_OK;
+  }
+  // (a pooled call that is not fused runs the plain conv and the separate pool kernels)
+  const WgPlan p = winograd_plan(B, H, W, K, N, pooled && takes_fused_pool(a, &dummy, INT64_MAX) ? (pooled == 2 ? 2 : 1) : 0);
+  out[0] = p.family == 1 ? 4 : p.family == 2 ? 5 : 3;
+  out[1] = p.ragged;
+  out[2] = p.in_waves;
+  out[3] = p.out_waves;
+  out[4] = p.kparts;
+  out[5] = (int)p.T;
+  out[6] = (int)p.blocks;
+  out[7] = p.Z;
+  return NFS_OK;
+}
+
 static inline uint32_t* out_bits_of(uint32_t* relu_bits, int B, int H, int W, int Ci) {
   return relu_bits ? relu_bits + (int64_t)B * ((H + 3) / 4) * ((W + 3) / 4) * (Ci / 2) : nullptr;
 }
@@ -741,13 +833,10 @@ int nfs_conv3x3_fwd(const float* x, const float* packed_fwd, const float* bias, 
   NFS_REQUIRE(B > 0 && H > 0 && W > 0, "nfs_conv3x3_fwd: non-positive dimension");
   NFS_REQUIRE((int64_t)B * H * W < ((int64_t)1 << 31) / 4, "nfs_conv3x3_fwd: too many pixels");
   NFS_REQUIRE(Co > 0 && Co % 64 == 0, "nfs_conv3x3_fwd: Co must be a multiple of 64");
-  static const bool old_c3 = getenv("NFS_C3_OLD") != nullptr;        // timing comparisons only
-  if (Ci == 3 && Co == 64 && !old_c3) {
-    const int tiles_x = (W + C3F_TW - 1) / C3F_TW, tiles_y = (H + C3F_TH - 1) / C3F_TH;
-    static const int per_cu = [] { const char* e = getenv("NFS_C3F_BLOCKS"); return e ? atoi(e) : 4; }();   // (27.1 us with 0, 25.2 with 4)
-    const int64_t ntiles = (int64_t)B * tiles_x * tiles_y, cap = 256 * (int64_t)per_cu;
-    hipLaunchKernelGGL(conv3x3_c3co64_fwd_kernel, dim3((unsigned)(per_cu > 0 && ntiles > cap ? cap : ntiles)), dim3(256), 0,
-                       as_stream(stream), x, packed_fwd, bias, y, B, H, W, relu, tiles_x, tiles_y);
+  if (Ci == 3 && Co == 64 && !c3_old()) {
+    const C3Grid g = c3_fwd_grid(B, H, W);
+    hipLaunchKernelGGL(conv3x3_c3co64_fwd_kernel, dim3(g.blocks), dim3(256), 0, as_stream(stream), x, packed_fwd, bias, y,
+                       B, H, W, relu, g.tiles_x, g.tiles_y);
     return check_launch("nfs_conv3x3_fwd(c3, Co=64, MFMA)");
   }
   if (Ci == 3) {
@@ -770,16 +859,10 @@ int nfs_conv3x3_dgrad(const float* gy, const float* packed_dgrad, const float* x
   NFS_REQUIRE(Co > 0 && Co % 32 == 0, "nfs_conv3x3_dgrad: Co must be a multiple of 32");
   if (Ci == 3) {
     NFS_REQUIRE(!x_in && !addend, "nfs_conv3x3_dgrad: Ci=3 takes no mask/addend");
-    static const bool old_c3 = getenv("NFS_C3_OLD") != nullptr;      // timing comparisons only
-    if (Co == 64 && !old_c3) {
-      const int tiles_x = (W + C3D_TW - 1) / C3D_TW, tiles_y = (H + C3D_TH - 1) / C3D_TH;
-      // blocks per CU of the tile-walking form (0: one block per tile, as before round 4).  8 x 200 x 200, 8 x 16 tiles:
-      // 44.3 us with 0, 38.6 / 38.2 / 38.8 / 40.5 / 41.1 with 2 / 3 / 4 / 6 / 8; 14 x 14 tiles: 38.5 with 0, 34.1 / 36.5 /
-      // 36.9 with 2 / 3 / 4 (tools/conv11_bench.py)
-      static const int per_cu = [] { const char* e = getenv("NFS_C3D_BLOCKS"); return e ? atoi(e) : 2; }();
-      const int64_t ntiles = (int64_t)B * tiles_x * tiles_y, cap = 256 * (int64_t)per_cu;
-      hipLaunchKernelGGL(conv3x3_c3co64_dgrad_kernel, dim3((unsigned)(per_cu > 0 && ntiles > cap ? cap : ntiles)),
-                         dim3(256), 0, as_stream(stream), gy, packed_dgrad, gx, B, H, W, tiles_x, tiles_y);
+    if (Co == 64 && !c3_old()) {
+      const C3Grid g = c3_dgrad_grid(B, H, W);
+      hipLaunchKernelGGL(conv3x3_c3co64_dgrad_kernel, dim3(g.blocks), dim3(256), 0, as_stream(stream), gy, packed_dgrad,
+                         gx, B, H, W, g.tiles_x, g.tiles_y);
       return check_launch("nfs_conv3x3_dgrad(c3, Co=64, MFMA)");
     }
     const int64_t n = (int64_t)B * H * W;

@@ -45,6 +45,7 @@ int64_t winograd5_packed_floats(int Ci, int Co);
 int64_t winograd5_workspace_floats(int B, int H, int W, int K, int N);
 int winograd5_pack(const float* w_hwio, float* up5, int Ci, int Co, int kind, hipStream_t s);
 int64_t winograd5_bits_words(int B, int H, int W, int C);
+bool winograd5_waves7(int64_t items);
 int winograd5_conv(const float* x, const float* U5, const float* aux0, const float* aux1, float* y, float* ws, int B,
                    int H, int W, int K, int N, int mode, int relu, int cus, hipStream_t s, uint32_t* in_bits);
 
@@ -1457,9 +1458,10 @@ static bool gemm_rb_applies(const WgGemmArgs& a) {
          (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
 }
 // ... the 16-row form also scales and masks (the Gram gradient runs on it, its symmetric D read in place)
-static bool gemm_rb16_applies(const WgGemmArgs& a) {
-  return a.Uq16 && a.T * a.K * 4 < ((int64_t)1 << 31) && (int64_t)a.K * a.N * 4 < ((int64_t)1 << 31);
+static bool gemm_rb16_shape(int64_t T, int K, int N) {
+  return T * K * 4 < ((int64_t)1 << 31) && (int64_t)K * N * 4 < ((int64_t)1 << 31);
 }
+static bool gemm_rb16_applies(const WgGemmArgs& a) { return a.Uq16 && gemm_rb16_shape(a.T, a.K, a.N); }
 
 void winograd_pack_frag16(const float* up, float* uq, int K, int N, int64_t total, hipStream_t s) {
   hipLaunchKernelGGL(winograd_pack_frag16_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, up, uq, K, N, total);
@@ -1669,23 +1671,33 @@ int winograd_ksplit(int64_t T, int K) {
   return T <= 64 && K >= 512 && (K / WG_KC) % 2 == 0 ? 2 : 1;    // (the output transforms sum 1 or 2)
 }
 
+// Which MFMA a GEMM of this shape runs on is decided by the shape alone (never by a measurement: the two instructions sum
+// k in different groupings, so their results differ in the last bit): the 16-row form wherever its offsets fit and it
+// executes no more rows than the best 32-row tiling (at equal rows it measured 3-5 % faster).  bm16: its row tile.
+static bool gemm_rows16_shape(int64_t T, int K, int N, int* bm16) {
+  const int64_t pad32 = (T + 63) / 64 * 64, pad16 = rb16_best_rows(T, bm16);
+  return gemm_rb16_shape(T, K, N) && pad16 <= pad32;
+}
+int winograd_conv_kparts(int64_t T, int K, int N) {
+  int bm16 = 80;
+  return gemm_rows16_shape(T, K, N, &bm16) ? winograd_ksplit(T, K) : 1;
+}
+
 static int launch_batched_gemm(WgGemmArgs a, int Z, int cus, hipStream_t s) {
   static const bool tune = [] { const char* e = getenv("NFS_GEMM_TUNE"); return !(e && atoi(e) == 0); }();
   int bm, bn, variant = 0;
   pick_gemm_tile(a.T, a.N, Z, cus, &bm, &bn);
   const int bm32 = bm, bn32 = bn;
-  // Which MFMA the GEMM runs on is decided by the shape alone (never by a measurement: the two instructions sum k in
-  // different groupings, so their results differ in the last bit): the 16-row form wherever it executes no more rows
-  // than the best 32-row tiling (at equal rows it measured 3-5 % faster).  Within a family every candidate computes the
-  // identical result, and the tuner measures.
+  // The family is gemm_rows16_shape's.  Within a family every candidate computes the identical result, and the tuner
+  // measures.
   int bm16 = 80;
-  const int64_t pad32 = (a.T + 63) / 64 * 64, pad16 = rb16_best_rows(a.T, &bm16);
+  const bool rows16 = gemm_rows16_shape(a.T, a.K, a.N, &bm16) && a.Uq16;
+  const int64_t pad16 = rb16_rows_executed(a.T, bm16);              // (rows of the best 16-row tiling)
   // mode 1: a plain product takes the split-limb instance of the 16-row form (variant 3); the Gram gradient (mask /
   // scale / symmetric B) stays on the f32-input MFMA
   const bool plain = !a.mask && !a.alpha_dev && a.alpha == 1.f && !a.symb;
   const int mode = g_gemm_mode;
   const int v16 = (mode == 1 && plain) ? 3 : 2;
-  const bool rows16 = gemm_rb16_applies(a) && pad16 <= pad32;
   // K parts (winograd_ksplit: by shape alone) only on the 16-row register-B form of a plain product (no mask / scale in
   // the epilogue: those apply to the complete sum)
   a.ksplit = rows16 && plain ? winograd_ksplit(a.T, a.K) : 1;
@@ -1861,6 +1873,47 @@ int winograd_pack(const float* w_hwio, float* up, int Ci, int Co, int kind, hipS
   return check_launch("winograd_pack");
 }
 
+// the six-wave F(4x4) transforms: few tiles, C % 128 == 0 (NFS_W4_WAVES6_MAX (tile, channel) items per launch; 0: never)
+static bool winograd4_waves6(int64_t T, int C) {
+  static const int64_t waves6_max = [] { const char* e = getenv("NFS_W4_WAVES6_MAX"); return e ? atoll(e) : (int64_t)65536; }();
+  return C % 128 == 0 && T * C <= waves6_max;
+}
+
+WgPlan winograd_plan(int B, int H, int W, int K, int N, int pooled) {
+  const int m = winograd_tile();
+  WgPlan p{};
+  // narrow layers: one kernel, no V / M round trip
+  if (m == 4 && winograd_fusable(K, N) && winograd_fused_takes(B, H, W, K, N)) {
+    p.family = 1;
+    p.ragged = wg_ragged(H, W, 4);
+    p.in_waves = p.out_waves = -1;
+    p.kparts = 1;
+    p.T = (int64_t)B * ((H + 3) / 4) * ((W + 3) / 4);
+    p.blocks = (p.T + 15) / 16 * (N / 64);
+    return p;
+  }
+  // deep layers with heavily padded F(4x4) tilings: F(5x5) (no pooling fused there; its ReLU bit cache has its own
+  // layout, sized by nfs_conv3x3_relu_bits_words for exactly the layers that come here)
+  if (m == 4 && !pooled && winograd5_takes(H, W, K, N)) {
+    p.family = 2;
+    p.ragged = wg_ragged(H, W, 5);
+    p.Z = 49;
+    p.T = (int64_t)B * ((H + 4) / 5) * ((W + 4) / 5);
+    p.in_waves = winograd5_waves7(p.T * K);
+    p.out_waves = winograd5_waves7(p.T * N);
+    p.kparts = winograd_conv_kparts(p.T, K, N);
+    return p;
+  }
+  p.family = 0;
+  p.ragged = wg_ragged(H, W, m);
+  p.Z = (m + 2) * (m + 2);
+  p.T = (int64_t)B * ((H + m - 1) / m) * ((W + m - 1) / m);
+  p.in_waves = m == 4 && pooled != 2 && winograd4_waves6(p.T, K);
+  p.out_waves = m == 4 && winograd4_waves6(p.T, N);
+  p.kparts = m == 4 ? winograd_conv_kparts(p.T, K, N) : 1;
+  return p;
+}
+
 // x [B,H,W,K] -> y [B,H,W,N]; U packed by winograd_pack; ws >= winograd_workspace_floats
 // ypool (mode 0, nullable): also write the 2x2 average pool of y (y itself is then optional).  pooled_grad (mode 1): x is a POOLED gradient
 // [B,H/2,W/2,K] that reaches the conv through the ReLU of xmask [B,H,W,K] (see winograd_input4_kernel<true>).
@@ -1870,13 +1923,13 @@ int winograd_conv(const float* x, const float* U, const float* aux0, const float
                   int H, int W, int K, int N, int mode, int relu, int cus, hipStream_t s, float* ypool,
                   const float* xmask, uint32_t* in_bits, uint32_t* out_bits, bool pooled_grad) {
   const int m = winograd_tile(), comps = (m + 2) * (m + 2);
-  // narrow layers: one kernel, no V / M round trip
-  if (m == 4 && winograd_fusable(K, N) && winograd_fused_takes(B, H, W, K, N) && (!pooled_grad || mode == 1))
+  // (which of the paths below, and which schedule of the transforms: winograd_plan, which nfs_conv3x3_plan reports)
+  const int form = pooled_grad && !out_bits ? 2 : (pooled_grad || ypool || out_bits || !y) ? 1 : 0;
+  const WgPlan plan = winograd_plan(B, H, W, K, N, form);
+  if (plan.family == 1)
     return winograd_fused_conv(x, U + (int64_t)108 * K * N, aux0, aux1, y, B, H, W, K, N, mode, relu, s, ypool, xmask,
                                in_bits, out_bits, pooled_grad);
-  // deep layers with heavily padded F(4x4) tilings: F(5x5) (no pooling fused there; its ReLU bit cache has its own
-  // layout, sized by nfs_conv3x3_relu_bits_words for exactly the layers that come here)
-  if (m == 4 && !pooled_grad && !ypool && !out_bits && y && winograd5_takes(H, W, K, N))
+  if (plan.family == 2)
     return winograd5_conv(x, U + (int64_t)108 * K * N + winograd_fused_packed_floats(K, N), aux0, aux1, y, ws, B, H, W, K, N,
                           mode, relu, cus, s, in_bits);
   const int TH = (H + m - 1) / m, TW = (W + m - 1) / m;
@@ -1884,9 +1937,7 @@ int winograd_conv(const float* x, const float* U, const float* aux0, const float
   float* V = ws;
   float* M = ws + comps * T * K;
   const dim3 ig((blocks_for(T * (K / 2), 256) + 7) / 8 * 8);
-  // few tiles: the six-wave transforms (NFS_W4_WAVES6_MAX (tile, channel) items per launch; 0: never)
-  static const int64_t waves6_max = [] { const char* e = getenv("NFS_W4_WAVES6_MAX"); return e ? atoll(e) : (int64_t)65536; }();
-  const bool in6 = m == 4 && K % 128 == 0 && T * K <= waves6_max, out6 = m == 4 && N % 128 == 0 && T * N <= waves6_max;
+  const bool in6 = plan.in_waves == 1, out6 = plan.out_waves == 1;
   const dim3 ig6((unsigned)((T * (K / 128) + 7) / 8 * 8));
   // the pooled data gradient masks from the bit cache of the layer's own output (POOLED 1) or from its float output (2)
   const bool pool_bits = pooled_grad && mode == 1 && out_bits;

@@ -288,16 +288,20 @@ int winograd5_pack(const float* w_hwio, float* up5, int Ci, int Co, int kind, hi
 // x [B,H,W,K] -> y [B,H,W,N]; U5 from winograd5_pack; ws >= winograd5_workspace_floats.  mode / relu / aux as winograd_conv.
 int64_t winograd5_bits_words(int B, int H, int W, int C) { return (int64_t)B * ((H + 4) / 5) * ((W + 4) / 5) * C; }
 
+// the seven-wave transforms where a launch has at most this many (tile, channel) items (NFS_W5_WAVES7_MAX; 0: never)
+bool winograd5_waves7(int64_t items) {
+  static const int64_t waves7_max = [] { const char* e = getenv("NFS_W5_WAVES7_MAX"); return e ? atoll(e) : (int64_t)65536; }();
+  return items <= waves7_max;
+}
+
 int winograd5_conv(const float* x, const float* U5, const float* aux0, const float* aux1, float* y, float* ws, int B,
                    int H, int W, int K, int N, int mode, int relu, int cus, hipStream_t s, uint32_t* in_bits) {
   const int TH = (H + 4) / 5, TW = (W + 4) / 5;
   const int64_t T = (int64_t)B * TH * TW;
   float* V = ws;
   float* M = ws + 49 * T * K;
-  // the seven-wave transforms where a launch has at most this many (tile, channel) items (NFS_W5_WAVES7_MAX; 0: never)
-  static const int64_t waves7_max = [] { const char* e = getenv("NFS_W5_WAVES7_MAX"); return e ? atoll(e) : (int64_t)65536; }();
   // forward: record the mask of x (the layer's own data gradient reads it); data gradient: read the mask of x_in
-  if (T * K <= waves7_max) {
+  if (winograd5_waves7(T * K)) {
     const dim3 ig((unsigned)((T * (K / 64) + 7) / 8 * 8));
     hipLaunchKernelGGL(winograd5_input7_kernel, ig, dim3(64, 7), 0, s, x, V, B, H, W, K, TH, TW, mode == 0 ? in_bits : nullptr);
   } else {
@@ -316,7 +320,7 @@ int winograd5_conv(const float* x, const float* U5, const float* aux0, const flo
   }
   const uint32_t* ib = (mode != 0 && aux0) ? in_bits : nullptr;         // a mask only where the caller asks for one
   wg_with_mode_nsplit(mode, nsplit, [&](auto MODE, auto NSPLIT) {
-    if (T * N <= waves7_max)
+    if (winograd5_waves7(T * N))
       hipLaunchKernelGGL((winograd5_output7_kernel<decltype(MODE)::value, decltype(NSPLIT)::value>), dim3((unsigned)(T * (N / 64))),
                          dim3(64, 7), 0, s, M, aux0, aux1, y, B, H, W, N, TH, TW, relu, ib);
     else

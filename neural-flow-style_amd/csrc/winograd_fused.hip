@@ -22,6 +22,7 @@
 #include "common.h"
 
 #include <mutex>
+#include "winograd_gemm.h"
 #include "winograd_math.h"
 
 namespace nfs {
@@ -528,7 +529,7 @@ static void launch_fused_knr(const WfArgs& a, int mode, bool pooled, hipStream_t
 
 template <int K, int N>
 static void launch_fused_kn(const WfArgs& a, int mode, bool pooled, hipStream_t s) {
-  if ((a.H & 3) || (a.W & 3)) launch_fused_knr<K, N, true>(a, mode, pooled, s);
+  if (wg_ragged(a.H, a.W, 4)) launch_fused_knr<K, N, true>(a, mode, pooled, s);
   else launch_fused_knr<K, N, false>(a, mode, pooled, s);
 }
 

@@ -37,6 +37,27 @@ int winograd_launch_batched_gemm(const WgGemmArgs& a, int Z, int cus, hipStream_
 // K parts by shape alone (never by a measurement: the parts change the order of a tile's sums): 2 when a launch has at
 // most 64 rows and K >= 512 (conv4_x / conv5_1 at one view: 392 blocks of 16 chunks -> 784 of 8), else 1
 int winograd_ksplit(int64_t T, int K);
+// K parts of a conv's batched product (plain, with the 16 x 16 fragment pack): winograd_ksplit where the 16-row form takes
+// the launch, else 1.  The rule launch_batched_gemm itself applies.
+int winograd_conv_kparts(int64_t T, int K, int N);
+
+// What a Winograd conv call runs -- a function of the shapes alone.  winograd_conv dispatches on it and nfs_conv3x3_plan
+// reports it, so the two cannot disagree.  `pooled`: 0 the plain conv; 1 a fused-pool form (pooled output, mask of y, the
+// pooled gradient masked from the bit cache); 2 the pooled gradient masked from the float output, whose input transform has
+// no six-wave schedule.
+struct WgPlan {
+  int family;       // 0 the three kernels of F(4x4) (or F(2x2)), 1 the single F(4x4) kernel, 2 F(5x5)  (as winograd_path)
+  int ragged;       // H or W is no multiple of the tile
+  int in_waves;     // input transform: 1 six / seven waves per block, 0 a thread per (tile, channel group), -1 no such kernel
+  int out_waves;    // the same for the output transform
+  int kparts;       // K parts of the batched GEMM (1 on the single kernel)
+  int Z;            // transform components = GEMM batches (36 / 49 / 16; 0 on the single kernel)
+  int64_t T;        // tiles
+  int64_t blocks;   // single kernel: runs of 16 tiles x 64-channel groups; 0 otherwise
+};
+WgPlan winograd_plan(int B, int H, int W, int K, int N, int pooled);
+inline bool wg_ragged(int H, int W, int m) { return (H % m) != 0 || (W % m) != 0; }
+
 // filters U [Z][K/32][N][32] -> the 16x16x4 fragment order [Z][N/16][K/16][64][4] (total = Z*K*N elements)
 void winograd_pack_frag16(const float* up, float* uq, int K, int N, int64_t total, hipStream_t s);
 // Uq16 [Z][N/16][K/16][64][4] floats -> the limb planes [Z][N/16][K/32][3][64][8 bf16] (1.5 x the floats); Z K N / 8 threads

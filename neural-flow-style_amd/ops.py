@@ -782,6 +782,22 @@ def conv3x3_relu_bits(B, H, W, Ci, Co, pooled, device):
     return torch.empty(n, dtype=torch.float32, device=device) if n > 0 else None
 
 
+CONV_FAMILIES = ("c3_generic", "c3_mfma", "direct", "wg4_three", "wg4_single", "wg5")
+
+
+def conv3x3_plan(B, H, W, K, N, pooled=False):
+    """which kernels the conv call for K input / N output channels of its kernel runs with a full workspace (forward:
+    K = Ci, N = Co; data gradient: K = Co, N = Ci; pooled: 0 plain, 1 a fused-pool form, 2 the pooled gradient masked
+    from the float output), by the launch code's own rules; launches nothing.  ``no_ws``: the
+    direct implicit GEMM the same call runs without one (splitk=False)."""
+    buf = (C.c_int * 12)()
+    _lib.call("nfs_conv3x3_plan", B, H, W, K, N, int(pooled), C.addressof(buf))
+    v = list(buf)
+    return dict(family=CONV_FAMILIES[v[0]], ragged=bool(v[1]), in_waves=v[2], out_waves=v[3], kparts=v[4], tiles=v[5],
+                blocks=v[6], Z=v[7] if v[0] >= 3 else 0, bn=v[7] if v[0] == 2 else 0,
+                no_ws=dict(bn=v[8], kparts=v[9], ragged=bool(v[10]), tiles=v[11]))
+
+
 def conv3x3_fwd(x, packed, bias, Co, relu=True, out=None, splitk=True, relu_bits=None):
     B, H, W, Ci = x.shape
     if out is None:
@@ -804,12 +820,15 @@ def conv3x3_dgrad(gy, packed, Ci, x_in=None, addend=None, out=None, splitk=True,
     return out
 
 
-def conv3x3_fwd_pool(x, packed, bias, Co, relu=True, relu_bits=None, want_y=True):
+def conv3x3_fwd_pool(x, packed, bias, Co, relu=True, relu_bits=None, want_y=True, out=None, out_pool=None):
     """conv + bias + ReLU and its 2x2 VALID average pool in one pass -> (y [B,H,W,Co], y_pool [B,H/2,W/2,Co]);
     with a ReLU bit cache and want_y=False the full-resolution output is not written at all (y = None)"""
     B, H, W, Ci = x.shape
-    out = _empty((B, H, W, Co), x) if (want_y or relu_bits is None) else None
-    pooled = _empty((B, H // 2, W // 2, Co), x)
+    if not (want_y or relu_bits is None):
+        out = None
+    elif out is None:
+        out = _empty((B, H, W, Co), x)
+    pooled = _empty((B, H // 2, W // 2, Co), x) if out_pool is None else out_pool
     ws, nws = _conv_ws_for(B, H, W, Ci, Co, x.device, True)
     _lib.call("nfs_conv3x3_fwd_pool", _ptr(x), _ptr(packed), _ptr(bias), _ptr(out), _ptr(pooled), B, H, W, Ci, Co,
               int(relu), _ptr(ws), nws, _ptr(relu_bits), _stream())
@@ -817,7 +836,7 @@ def conv3x3_fwd_pool(x, packed, bias, Co, relu=True, relu_bits=None, want_y=True
 
 
 def conv3x3_dgrad_pool(gy_pool, x_out, packed, Ci, x_in=None, addend=None, relu_bits=None, hw=None,
-                       addend_unmasked=False):
+                       addend_unmasked=False, out=None):
     """data gradient of a conv followed by ReLU + 2x2 average pool, from the gradient at the POOLED resolution
     gy_pool [B,H/2,W/2,Co] and the conv's own output x_out [B,H,W,Co] -> gx [B,H,W,Ci]; x_out may be None when the
     layer's ReLU bit cache is given (``hw`` = its (H, W) then)"""
@@ -827,7 +846,8 @@ def conv3x3_dgrad_pool(gy_pool, x_out, packed, Ci, x_in=None, addend=None, relu_
         assert relu_bits is not None and hw is not None
         B, Co = gy_pool.shape[0], gy_pool.shape[-1]
         H, W = hw
-    out = _empty((B, H, W, Ci), gy_pool)
+    if out is None:
+        out = _empty((B, H, W, Ci), gy_pool)
     ws, nws = _conv_ws_for(B, H, W, Ci, Co, gy_pool.device, True)
     _lib.call("nfs_conv3x3_dgrad_pool", _ptr(gy_pool), _ptr(x_out), _ptr(packed), _ptr(x_in), _ptr(addend), _ptr(out),
               B, H, W, Ci, Co, _ptr(ws), nws, _ptr(relu_bits), int(bool(addend_unmasked)), _stream())

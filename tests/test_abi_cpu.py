@@ -59,6 +59,7 @@ def test_derived_binding_equals_the_rows_typed_by_hand():
         "nfs_gemm_last": ([_P], C.c_int),
         "nfs_gemm_timer_read_kind": ([_I, _P, _P, _P, _P], C.c_int),
         "nfs_conv3x3_executed_flops": ([_I, _I, _I, _I, _I, _I], C.c_double),
+        "nfs_conv3x3_plan": ([_I, _I, _I, _I, _I, _I, _P], C.c_int),
         "nfs_conv3x3_workspace_floats": ([_I, _I, _I, _I, _I], C.c_int64),
         "nfs_lap_up_rms": ([_P, _P, _F, _P, _P, _I, _L, _F, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
         "nfs_maxpool3_fwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _P], C.c_int),
@@ -75,7 +76,7 @@ def test_derived_binding_equals_the_rows_typed_by_hand():
     for name, (argtypes, restype) in rows.items():
         assert _lib.SIGNATURES[name] == argtypes, name
         assert _lib.RESTYPES[name] is restype, name
-    assert set(_lib.RESTYPES) == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 131
+    assert set(_lib.RESTYPES) == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 132
     assert (_lib.NFS_EINVAL, _lib.NFS_ELAUNCH) == (-1, -2)
 
 

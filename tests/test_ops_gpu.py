@@ -424,13 +424,27 @@ def _conv_ref(x, w, b, relu=True):
 @pytest.mark.parametrize("B,H,W,Ci,Co", [(2, 13, 11, 3, 64), (2, 13, 11, 64, 64), (3, 25, 25, 64, 128),
                                           (1, 12, 12, 128, 256), (2, 7, 50, 128, 128), (8, 6, 6, 256, 128),
                                           (1, 25, 25, 512, 512), (1, 12, 12, 512, 512),    # these two: K-split GEMMs
-                                          # the single-kernel Winograd path (64 / 128 channels, whole 4x4 tiles): runs of
-                                          # 16 tiles that wrap rows and images, a ragged last run, both channel groups
-                                          # (with 128 input channels it is taken from 128 blocks of 16 tiles x 64 channels on)
+                                          # (F(5x5) and F(4x4) in three kernels)
+                                          # The paths below are what nfs_conv3x3_plan reports (tests/test_conv_gpu.py
+                                          # asserts a path per case).  The single-kernel Winograd path, whole 4x4 tiles:
+                                          # taken at K = 64 input channels of the GEMM at any size, at K = 128 from 128
+                                          # blocks of 16 tiles x 64 output channels on.  So (3, 20, 28, 64, 64),
+                                          # (4, 64, 64, 128, 128) and (8, 64, 64, 128, 64) run it both ways (runs of 16
+                                          # tiles that wrap rows and images, a last run of 9 tiles, both channel groups);
+                                          # (5, 8, 8, 128, 64) only in its data gradient and (1, 4, 4, 64, 128) only
+                                          # forward (K = 64 there), their other pass and both of (2, 12, 16, 128, 128)
+                                          # run the three kernels with the six-wave transforms
                                           (3, 20, 28, 64, 64), (2, 12, 16, 128, 128), (5, 8, 8, 128, 64),
                                           (1, 4, 4, 64, 128), (4, 64, 64, 128, 128), (8, 64, 64, 128, 64),
                                           # ... and its ragged instance (H or W off a multiple of 4: the last tile row /
-                                          # column hangs over the image; per-pixel validity in the epilogue)
+                                          # column hangs over the image; per-pixel validity in the epilogue): the K = 64
+                                          # passes, that is both of (2, 30, 45, 64, 64) and (1, 5, 6, 64, 64), the forward
+                                          # pass of (2, 30, 45, 64, 128) and the gradient of (4, 61, 67, 128, 64).  A ragged
+                                          # K = 128 pass needs 300 blocks; these shapes give 136 and 68, so both passes of
+                                          # (4, 62, 66, 128, 128), the forward pass of (4, 61, 67, 128, 64) and the
+                                          # gradient of (2, 30, 45, 64, 128) run the three kernels (thread-per-tile
+                                          # transforms above 65536 items); test_conv_gpu.py holds the ragged K = 128
+                                          # single-kernel instances
                                           (2, 30, 45, 64, 64), (2, 30, 45, 64, 128), (4, 62, 66, 128, 128),
                                           (4, 61, 67, 128, 64), (1, 5, 6, 64, 64)])
 def test_conv3x3_fwd_and_dgrad(ops, B, H, W, Ci, Co):
@@ -482,8 +496,13 @@ def test_winograd_f5_error_budget(ops, B, H, W, Ci, Co):
                                           (3, 20, 28, 64, 64), (2, 12, 16, 128, 128), (5, 8, 8, 128, 64),
                                           (4, 64, 64, 128, 128),
                                           (1, 24, 24, 512, 512),      # 36 tiles, K = 512: the GEMM runs in two K parts
-                                          # ragged single-kernel instances: odd sides floor in the pool (a window exists
-                                          # when its lower right pixel does), the pooled gradient is zero beyond them
+                                          # odd sides floor in the pool (a window exists when its lower right pixel does),
+                                          # the pooled gradient is zero beyond them.  By nfs_conv3x3_plan: (2, 13, 11, 64, 64),
+                                          # (2, 30, 45, 64, 64) and (2, 150, 225, 128, 128) (4332 tiles, 542 blocks) run the
+                                          # ragged single-kernel instance both ways;
+                                          # (4, 61, 66, 128, 128) gives 136 blocks of the 300 a ragged K = 128 layer needs
+                                          # and runs the three kernels, as do (1, 25, 25, 128, 128), (2, 12, 16, 128, 128),
+                                          # the forward pass of (5, 8, 8, 128, 64) and the gradient of (2, 8, 12, 64, 128)
                                           (2, 30, 45, 64, 64), (4, 61, 66, 128, 128), (2, 150, 225, 128, 128)])
 def test_conv3x3_fused_pool(ops, B, H, W, Ci, Co):
     """conv + ReLU + 2x2 VALID average pool in one pass, and the data gradient taken from the POOLED gradient
