@@ -38,7 +38,7 @@ extern "C" {
 
 /* what nfs_version() returns, as 100 major + 10 minor + patch (the changelog is at its definition, csrc/api.hip); the
  * Python binding refuses a library that reports another number than the header it reads */
-#define NFS_ABI_VERSION 158
+#define NFS_ABI_VERSION 159
 
 typedef void* nfs_stream_t;
 
@@ -640,6 +640,17 @@ int64_t nfs_conv2d_packed_floats(int kh, int kw, int Ci, int Co, int transpose);
 int nfs_conv2d_pack(const float* w_hwio, float* packed, int kh, int kw, int Ci, int Co, int transpose,
                     nfs_stream_t stream);
 int64_t nfs_conv2d_workspace_floats(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride);
+/* Which instance of the implicit GEMM nfs_conv2d_fwd runs for these shapes and how it cuts K.  Launches nothing;
+ * computed by the helper the launch itself calls.  out[0..7]:
+ *   0 rows of a block's tile (64 | 128)
+ *   1 chunk mode: 0 a K chunk is 16 input channels of one tap; 1 (Cin <= 4) a chunk is 4 taps x 4 channels
+ *   2 K splits WHEN a workspace of nfs_conv2d_workspace_floats is given (without one the call runs 1 split of all chunks)
+ *   3 K chunks per split (the last split holds what is left)
+ *   4 K chunks in all
+ *   5 chunks per tap (ceil(Cin / 16); a partial last chunk is zero-filled)
+ *   6 row tiles (ceil(B Ho Wo / out[0]))
+ *   7 column tiles of 64 output channels */
+int nfs_conv2d_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int* out);
 int nfs_conv2d_fwd(const float* x, int ldx, const float* x_mask, int ldm, const float* packed, const float* bias,
                    float* y, int ldy, float* y_pre, int ldp, int B, int H, int W, int Cin, int Cout, int kh, int kw,
                    int stride, int relu, int accumulate, float* workspace, int64_t workspace_floats,
@@ -648,7 +659,10 @@ int nfs_conv2d_fwd(const float* x, int ldx, const float* x_mask, int ldm, const 
  * module are a few hundred pixels each and would leave most of the chip idle one by one.  Fields as the arguments of
  * nfs_conv2d_fwd.  sum_with_prev: the result is added to the previous problem's (same pixels, Cout and y) -- the data
  * gradients of a module's three 1x1 branches meet in one tensor; they leave as partial sums and one fixed-order
- * reduction writes y (no race, deterministic).  K is split over blocks until the launch fills the chip.  n <= 6. */
+ * reduction writes y (no race, deterministic).  K is split over blocks until the launch fills the chip.  n <= 6.
+ * A run (a problem and the sum_with_prev problems behind it) is finished by ONE epilogue, and that is the FIRST
+ * problem's: its bias, relu, y_pre and accumulate hold for the whole sum.  A follower that carries bias, y_pre or relu is
+ * refused (NFS_EINVAL): they would be dropped.  A follower's accumulate is ignored. */
 typedef struct {
   const float* x;
   const float* x_mask;
@@ -661,6 +675,13 @@ typedef struct {
   int relu, accumulate, sum_with_prev;
 } nfs_conv2d_desc_t;
 int64_t nfs_conv2d_group_workspace_floats(const nfs_conv2d_desc_t* descs, int n, int B);
+/* How nfs_conv2d_group lays these problems out (every tile is 64 rows x 64 columns).  Launches nothing and touches no
+ * pointer (they are only checked as the launch checks them); computed by the planner the launch itself calls.
+ * out[6 j .. 6 j + 5] for problem j:
+ *   0 K splits   1 K chunks per split   2 partial: its tiles leave as partial sums and the reduction finishes them
+ *   3 zbase: its first partial sum within its run   4 ztotal: the partial sums of the whole run
+ *   5 its position in the launch order (the blocks of position 0 come first: most chunks per block first) */
+int nfs_conv2d_group_plan(const nfs_conv2d_desc_t* descs, int n, int B, int* out);
 int nfs_conv2d_group(const nfs_conv2d_desc_t* descs, int n, int B, float* workspace, int64_t workspace_floats,
                      nfs_stream_t stream);
 int nfs_conv2d_dgrad_small(const float* gy, int ldg, const float* y_act, int lda, const float* w_hwio, float* gx,

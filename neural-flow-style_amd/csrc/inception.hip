@@ -702,6 +702,29 @@ int64_t nfs_conv2d_workspace_floats(int B, int H, int W, int Cin, int Cout, int 
   return p.ksplit > 1 ? (int64_t)p.ksplit * M * conv2d_npad(Cout) : 0;
 }
 
+int nfs_conv2d_plan(int B, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int* out) {
+  NFS_REQUIRE(out, "nfs_conv2d_plan: null pointer");
+  NFS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "nfs_conv2d_plan: non-positive dimension");
+  NFS_REQUIRE(kh > 0 && kw > 0 && kh <= 7 && kw <= 7 && (stride == 1 || stride == 2),
+              "nfs_conv2d_plan: filter up to 7x7, stride 1 or 2");
+  int Ho, Wo, pt, pl;
+  same_pad(H, kh, stride, Ho, pt);
+  same_pad(W, kw, stride, Wo, pl);
+  const int64_t M = (int64_t)B * Ho * Wo;
+  NFS_REQUIRE(M < ((int64_t)1 << 31), "nfs_conv2d_plan: too many pixels");
+  const int nchunks = conv2d_nchunks(kh, kw, Cin), Npad = conv2d_npad(Cout);
+  const Conv2dPlan p = conv2d_plan(M, Npad, nchunks);
+  out[0] = p.bm;
+  out[1] = Cin <= 4 ? 1 : 0;
+  out[2] = p.ksplit;
+  out[3] = p.cps;
+  out[4] = nchunks;
+  out[5] = conv2d_cchunks(Cin);
+  out[6] = (int)((M + p.bm - 1) / p.bm);
+  out[7] = Npad / IC_BN;
+  return NFS_OK;
+}
+
 int nfs_conv2d_fwd(const float* x, int ldx, const float* x_mask, int ldm, const float* packed, const float* bias,
                    float* y, int ldy, float* y_pre, int ldp, int B, int H, int W, int Cin, int Cout, int kh, int kw,
                    int stride, int relu, int accumulate, float* workspace, int64_t workspace_floats,
@@ -770,6 +793,7 @@ namespace {
 struct GroupPlan {
   Conv2dGroupArgs conv, red;
   int64_t ws_floats;
+  int pos[IC_GMAX];   // position of problem j in the launch order: conv.p[pos[j]] is descs[j]
 };
 
 // fills plan (pointers into `workspace` when given); returns 0, or a message
@@ -812,6 +836,9 @@ const char* conv2d_group_plan(const nfs_conv2d_desc_t* d, int n, int B, float* w
       if (j == 0) return "the first problem cannot be summed with a previous one";
       const Conv2dArgs& f = a[j - 1];
       if (f.M != c.M || f.Cout != c.Cout || f.y != c.y || f.ldy != c.ldy) return "summed problems must share pixels, Cout and y";
+      // one reduction finishes a run with the epilogue of its FIRST problem: what a follower carried would be dropped
+      if (q.bias || q.y_pre || q.relu)
+        return "a summed run takes bias, relu and y_pre from its first problem: a problem with sum_with_prev must carry none";
     }
   }
   // K chunks per block: the largest T of the ladder that yields >= 512 blocks (>= 8 chunks per block, <= 16 splits)
@@ -870,6 +897,7 @@ const char* conv2d_group_plan(const nfs_conv2d_desc_t* d, int n, int B, float* w
   for (int i = 0; i < n; ++i) {
     const int j = order[i];
     P.conv.p[i] = a[j];
+    P.pos[j] = i;
     P.conv.bstart[i] = b0;
     b0 += mtiles[j] * ntiles[j] * a[j].ksplit;
   }
@@ -882,6 +910,19 @@ const char* conv2d_group_plan(const nfs_conv2d_desc_t* d, int n, int B, float* w
 int64_t nfs_conv2d_group_workspace_floats(const nfs_conv2d_desc_t* descs, int n, int B) {
   GroupPlan P;
   return conv2d_group_plan(descs, n, B, nullptr, P) ? -1 : P.ws_floats;
+}
+
+int nfs_conv2d_group_plan(const nfs_conv2d_desc_t* descs, int n, int B, int* out) {
+  NFS_REQUIRE(out, "nfs_conv2d_group_plan: null pointer");
+  GroupPlan P;
+  const char* err = conv2d_group_plan(descs, n, B, nullptr, P);
+  NFS_REQUIRE(!err, "nfs_conv2d_group_plan: %s", err);
+  for (int j = 0; j < n; ++j) {
+    const Conv2dArgs& a = P.conv.p[P.pos[j]];
+    int* o = out + 6 * j;
+    o[0] = a.ksplit; o[1] = a.cps; o[2] = a.partial; o[3] = a.zbase; o[4] = a.ztotal; o[5] = P.pos[j];
+  }
+  return NFS_OK;
 }
 
 int nfs_conv2d_group(const nfs_conv2d_desc_t* descs, int n, int B, float* workspace, int64_t workspace_floats,

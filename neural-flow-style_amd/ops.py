@@ -1261,6 +1261,24 @@ def conv2d_group(problems):
     """Several stride-1 SAME convolutions of one batch in one launch.  ``problems``: dicts with the arguments of
     ``conv2d_fwd`` (x, cx, Cin, packed, bias, y, cy, Cout, k, relu, y_pre, cp, x_mask, cm, accumulate) and
     ``sum_with_prev`` (added to the previous problem's result: same pixels, Cout and output range)"""
+    arr, n, B = conv2d_group_descs(problems)
+    x = problems[0]["x"]
+    key = (B,) + tuple((q.H, q.W, q.Cin, q.Cout, q.kh, q.sum_with_prev) for q in arr)
+    nws = _group_ws.get(key)
+    if nws is None:
+        nws = _lib.lib().nfs_conv2d_group_workspace_floats(arr, n, B)
+        if nws < 0:
+            _lib.call("nfs_conv2d_group", arr, n, B, None, 0, _stream())     # raises with the planner's message
+        _group_ws[key] = nws
+    ws = conv_workspace(x.device, nws) if nws > 0 else None
+    if _lib.PROFILE is not None:                          # (bench: the shapes behind this call's event pair)
+        _lib.PROFILE.setdefault("shapes:nfs_conv2d_group", []).append(
+            [(B, q.H, q.W, q.Cin, q.Cout, q.kh, q.kw) for q in arr])
+    _lib.call("nfs_conv2d_group", arr, n, B, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+
+
+def conv2d_group_descs(problems):
+    """(descriptor array, n, B) of the problems of ``conv2d_group``"""
     n = len(problems)
     arr = (_lib.ConvDesc * n)()
     B = problems[0]["x"].shape[0]
@@ -1278,18 +1296,24 @@ def conv2d_group(problems):
         q.H, q.W, q.Cin, q.Cout, q.kh, q.kw = x.shape[1], x.shape[2], Cin, Cout, pr["k"], pr["k"]
         q.relu, q.accumulate = int(bool(pr.get("relu", True))), int(bool(pr.get("accumulate", False)))
         q.sum_with_prev = int(bool(pr.get("sum_with_prev", False)))
-    key = (B,) + tuple((q.H, q.W, q.Cin, q.Cout, q.kh, q.sum_with_prev) for q in arr)
-    nws = _group_ws.get(key)
-    if nws is None:
-        nws = _lib.lib().nfs_conv2d_group_workspace_floats(arr, n, B)
-        if nws < 0:
-            _lib.call("nfs_conv2d_group", arr, n, B, None, 0, _stream())     # raises with the planner's message
-        _group_ws[key] = nws
-    ws = conv_workspace(x.device, nws) if nws > 0 else None
-    if _lib.PROFILE is not None:                          # (bench: the shapes behind this call's event pair)
-        _lib.PROFILE.setdefault("shapes:nfs_conv2d_group", []).append(
-            [(B, q.H, q.W, q.Cin, q.Cout, q.kh, q.kw) for q in arr])
-    _lib.call("nfs_conv2d_group", arr, n, B, _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    return arr, n, B
+
+
+def conv2d_plan(B, H, W, Cin, Cout, kh, kw, stride=1):
+    """which instance ``conv2d_fwd`` runs for these shapes and how it cuts K (``ksplit``: with the workspace that
+    ``conv2d_fwd`` passes), by the launch code's own rules; launches nothing"""
+    buf = (C.c_int * 8)()
+    _lib.call("nfs_conv2d_plan", B, H, W, Cin, Cout, kh, kw, stride, C.addressof(buf))
+    return dict(zip(("bm", "cmode", "ksplit", "cps", "nchunks", "cchunks", "mtiles", "ntiles"), buf))
+
+
+def conv2d_group_plan(descs, B):
+    """how ``conv2d_group`` lays out a descriptor array (``conv2d_group_descs``): per problem ksplit, cps, partial,
+    zbase, ztotal and its position in the launch order; launches nothing, raises with the planner's refusal"""
+    n = len(descs)
+    buf = (C.c_int * (6 * n))()
+    _lib.call("nfs_conv2d_group_plan", descs, n, B, C.addressof(buf))
+    return [dict(zip(("ksplit", "cps", "partial", "zbase", "ztotal", "position"), buf[6 * j:6 * j + 6])) for j in range(n)]
 
 
 def conv2d_dgrad_small(gy, cg, Co, w_hwio, in_hw, stride, y_act=None, ca=0):

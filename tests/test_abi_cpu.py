@@ -71,12 +71,14 @@ def test_derived_binding_equals_the_rows_typed_by_hand():
         # (the descriptor array was a _P in that table: the header says what it points to)
         "nfs_conv2d_group": ([C.POINTER(ConvDesc), _I, _I, _P, _L, _P], C.c_int),
         "nfs_render_coef_layout": ([_I, _I, _I, _I, _P, _P], C.c_int),
+        "nfs_conv2d_plan": ([_I, _I, _I, _I, _I, _I, _I, _I, _P], C.c_int),
+        "nfs_conv2d_group_plan": ([C.POINTER(ConvDesc), _I, _I, _P], C.c_int),
     }
     assert len(rows["nfs_conv2d_fwd"][0]) == 23 and len(rows["nfs_resize3d"][0]) == 13
     for name, (argtypes, restype) in rows.items():
         assert _lib.SIGNATURES[name] == argtypes, name
         assert _lib.RESTYPES[name] is restype, name
-    assert set(_lib.RESTYPES) == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 132
+    assert set(_lib.RESTYPES) == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 134
     assert (_lib.NFS_EINVAL, _lib.NFS_ELAUNCH) == (-1, -2)
 
 
