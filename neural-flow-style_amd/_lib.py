@@ -106,11 +106,22 @@ SplatCfg, GramLayer, ConvDesc = _structs["nfs_splat_cfg"], _structs["nfs_gram_la
 NFS_EINVAL, NFS_ELAUNCH = _constants["NFS_EINVAL"], _constants["NFS_ELAUNCH"]
 ABI_VERSION = _constants["NFS_ABI_VERSION"]          # what nfs_version() of a library built from this header returns
 
+# libnfs_grid2d.so (the 2-D grid stylizer's operators): a library and a header of its own, bound the same way
+GRID2D_LIB_PATH = os.path.join(_HERE, "libnfs_grid2d.so")
+GRID2D_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_grid2d.h"))
+try:
+    with open(GRID2D_HEADER_PATH) as _f:
+        GRID2D_SIGNATURES, GRID2D_RESTYPES, _, _c2 = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (GRID2D_HEADER_PATH, e))
+GRID2D_ABI_VERSION = _c2["NFS_GRID2D_ABI_VERSION"]
+
 _lib = None
+_lib2d = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so and libnfs_grid2d.so (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -155,6 +166,33 @@ def lib():
     return _lib
 
 
+def lib2d():
+    """libnfs_grid2d.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
+    global _lib2d
+    if _lib2d is None:
+        lib()
+        if not os.path.exists(GRID2D_LIB_PATH):
+            raise NfsLibraryError(
+                "libnfs_grid2d.so is missing (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
+                "-- there is no CPU fallback for the product path" % GRID2D_LIB_PATH)
+        try:
+            L = C.CDLL(GRID2D_LIB_PATH)
+        except OSError as e:  # pragma: no cover
+            raise NfsLibraryError("cannot load %s: %s" % (GRID2D_LIB_PATH, e))
+        for name, argt in GRID2D_SIGNATURES.items():
+            try:
+                f = getattr(L, name)
+            except AttributeError:
+                raise NfsLibraryError("libnfs_grid2d.so does not export %s (stale build?)" % name)
+            f.argtypes = argt
+            f.restype = GRID2D_RESTYPES[name]
+        if L.nfs_grid2d_version() != GRID2D_ABI_VERSION:
+            raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d: rebuild (make -C %s)"
+                                  % (GRID2D_LIB_PATH, L.nfs_grid2d_version(), GRID2D_ABI_VERSION, CSRC_DIR))
+        _lib2d = L
+    return _lib2d
+
+
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
 # two events recorded on the SAME stream the kernel is enqueued on; entries are
 # name -> [(start_event, end_event, args)].  Costs two event records per call, so it is off by
@@ -165,6 +203,10 @@ PROFILE = None
 def call(name, *args):
     """Call an int-returning entry point; raise with nfs_last_error() on failure."""
     L = lib()
+    if name in GRID2D_SIGNATURES:            # (the error text stays libnfs_hip.so's: the two share nfs::set_error)
+        L, L0 = lib2d(), L
+    else:
+        L0 = L
     if PROFILE is not None:
         import torch
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
@@ -175,5 +217,5 @@ def call(name, *args):
     else:
         rc = getattr(L, name)(*args)
     if rc != 0:
-        raise NfsError(name, rc, L.nfs_last_error().decode())
+        raise NfsError(name, rc, L0.nfs_last_error().decode())
     return rc

@@ -70,14 +70,7 @@ __global__ void __launch_bounds__(256) grad_bwd_kernel(const float* __restrict__
 // g_vel [D,H,W,3] is a velocity gradient in advect's channel order.  A thread reads g_vel at its neighbours and its own
 // variable, m, v only -- one vector of each (12 bytes, a float, a float4), lanes contiguous: in place.  g_var is never
 // stored: per voxel 12 B of g_vel + 6 x the variable (s 84 B, phi 36 B, a 108 B) against 108, 44 and 152 B for the
-// stand-alone adjoint(s) followed by nfs_adam_tf_step.
-// TF ApplyAdam of one element, as the plain expression (adam_kernel's, field.hip; fmaf here would choose bits)
-__device__ __forceinline__ void adam_tf(float& x, float& m, float& u, float g, float lr_t, float b1, float b2, float eps) {
-  m = b1 * m + (1.f - b1) * g;
-  u = b2 * u + (1.f - b2) * g * g;
-  x -= lr_t * m / (sqrtf(u) + eps);
-}
-
+// stand-alone adjoint(s) followed by nfs_adam_tf_step.  (adam_tf: source_ops.h)
 template <int SRC>
 __global__ void __launch_bounds__(256) source_bwd_adam_kernel(const float* __restrict__ g, float* __restrict__ var,
                                                               float* __restrict__ m, float* __restrict__ v, int D, int H,

@@ -83,6 +83,14 @@ __device__ __forceinline__ F3u source_velocity(const float* __restrict__ var, si
   }
 }
 
+// TF ApplyAdam of one element, as the plain expression (adam_kernel's, field.hip; fmaf here would choose bits): what the
+// fused updates of source.hip and grid2d.hip consume their gradient with
+__device__ __forceinline__ void adam_tf(float& x, float& m, float& u, float g, float lr_t, float b1, float b2, float eps) {
+  m = b1 * m + (1.f - b1) * g;
+  u = b2 * u + (1.f - b2) * g * g;
+  x -= lr_t * m / (sqrtf(u) + eps);
+}
+
 // ---- the transposes ------------------------------------------------------------------------------------------------------
 // A forward difference taken at cell l = fd_lo(i) contributes +g to s[l+1] and -g to s[l]; cell i receives from the outputs
 // whose l equals i (outputs i, and n-1 as well when i == n-2) and whose l+1 equals i.

@@ -1367,8 +1367,9 @@ class ImageStyleLoss(object):
         return dimg
 
     def loss_and_grad(self, d, d_gray=None):
-        """d [B,H,W,3]; d_gray [B,H,W,1] (mask, constant).  Returns (loss per image [B], dL/dd)."""
-        B, H, W, _ = d.shape
+        """d [B,H,W,3], or [B,H,W,1] (a grey image: the 2-D grid stylizer's clipped density); d_gray [B,H,W,1] (mask,
+        constant).  Returns (loss per image [B], dL/dd)."""
+        B, H, W, Cin = d.shape
         H2, W2 = self.out_hw(H, W)
         hist_in = any("input" in n for n in self.hist_layers)
         dimg, x = ops.loss_net_input_fwd(d.contiguous(), H2, W2, want_d_img=self.w_tv > 0 or hist_in)
@@ -1405,5 +1406,5 @@ class ImageStyleLoss(object):
             tv = torch.zeros(1, dtype=torch.float32, device=d.device)
             ops.tv_loss(dimg, self.w_tv, tv, g_x)
             loss = loss + tv / B
-        g_d = ops.loss_net_input_bwd(g_x, H, W, 3)
+        g_d = ops.loss_net_input_bwd(g_x, H, W, Cin)
         return loss, g_d

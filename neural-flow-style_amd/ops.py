@@ -531,6 +531,83 @@ def transport_step(g, u, scale=1.0, w_g=1.0, addend=None, w_addend=0.0, out=None
     return out
 
 
+# ---- stylising a 2-D grid (include/nfs_grid2d.h, libnfs_grid2d.so; engine: grid2d.py) -----------------------------------
+# the 2-D rows of the ``_SOURCES`` table: kind -> (``src`` of the entry points, channels of the variable; 0 = no channel axis)
+_SOURCES2D = {"v": (0, 2), "s": (1, 0), "p": (2, 0), "sp": (3, 2)}
+
+
+def source2d_shape(kind, H, W):
+    """shape of the 2-D variable of kind 'v' (velocity [H,W,2]), 's' (psi [H,W]), 'p' (phi [H,W]) or 'sp' ([H,W,2] =
+    (psi, phi)) on an [H,W] grid"""
+    ch = _SOURCES2D[kind][1]
+    return (H, W, ch) if ch else (H, W)
+
+
+def _var2d(kind, x, H, W):
+    assert tuple(x.shape) == source2d_shape(kind, H, W) and x.is_contiguous(), (kind, tuple(x.shape), (H, W))
+    return _SOURCES2D[kind][0]
+
+
+def source2d_velocity(kind, x, out=None):
+    """the velocity [H,W,2] (``advect2d_fwd``'s units and channel order) the 2-D variable ``x`` of that kind stands for"""
+    H, W = x.shape[:2]
+    src = _var2d(kind, x, H, W)
+    if out is None:
+        out = _empty((H, W, 2), x)
+    _lib.call("nfs_source2d_velocity_fwd", _ptr(x), src, _ptr(out), H, W, _stream())
+    _written(out)
+    return out
+
+
+def source2d_velocity_bwd(kind, g_vel):
+    """its adjoint: the gradient of the variable from the gradient g_vel [H,W,2] of the velocity (a gather: deterministic)"""
+    H, W, _ = g_vel.shape
+    g_x = _empty(source2d_shape(kind, H, W), g_vel)
+    _lib.call("nfs_source2d_velocity_bwd", _ptr(g_vel), _SOURCES2D[kind][0], _ptr(g_x), H, W, _stream())
+    return g_x
+
+
+def advect2d_source_fwd(kind, d, x, out=None):
+    """advect2d_fwd(d, source2d_velocity(kind, x)) for a density d [H,W], the velocity never stored (the same bits)"""
+    H, W = d.shape
+    src = _var2d(kind, x, H, W)
+    if out is None:
+        out = _empty((H, W), d)
+    _lib.call("nfs_advect2d_source_fwd", _ptr(d), _ptr(x), src, _ptr(out), H, W, _stream())
+    _written(out)
+    return out
+
+
+def advect2d_source_bwd(kind, d, x, g_out, g_vel=None):
+    """velocity gradient [H,W,2] of ``advect2d_source_fwd``: the bits of advect2d_bwd(d, velocity, g_out)'s g_vel"""
+    H, W = d.shape
+    src = _var2d(kind, x, H, W)
+    if g_vel is None:
+        g_vel = _empty((H, W, 2), d)
+    _lib.call("nfs_advect2d_source_bwd", _ptr(d), _ptr(x), src, _ptr(g_out), _ptr(g_vel), H, W, _stream())
+    return g_vel
+
+
+def advect2d_bwd_adam(d, vel, g_out, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, adv_next=None):
+    """the velocity gradient of advect2d(d [H,W], vel [H,W,2]) consumed by TF ApplyAdam on vel, m, v in place;
+    ``adv_next`` [H,W] (optional) receives advect2d(d, updated vel)"""
+    H, W = d.shape
+    assert tuple(vel.shape) == tuple(m.shape) == tuple(v.shape) == (H, W, 2)
+    _lib.call("nfs_advect2d_bwd_adam_fwd", _ptr(d), _ptr(vel), _ptr(g_out), _ptr(m), _ptr(v), _ptr(adv_next), H, W,
+              float(lr_t), float(beta1), float(beta2), float(eps), _stream())
+    _written(vel, m, v, adv_next)
+
+
+def transport_step2d(g, u, scale=1.0, w_g=1.0, addend=None, w_addend=0.0, out=None):
+    """``transport_step`` for a C-channel 2-D field g [H,W,C] and a simulation velocity u [H,W,2]"""
+    H, W, Cn = g.shape
+    if out is None:
+        out = _empty(g.shape, g)
+    _lib.call("nfs_transport_step2d", _ptr(g), _ptr(u), float(scale), float(w_g), _ptr(addend), float(w_addend), _ptr(out),
+              H, W, Cn, _stream())
+    return out
+
+
 # ---- A9 -----------------------------------------------------------------------------
 
 def smooth3d_relu_fwd(d, k, out=None):

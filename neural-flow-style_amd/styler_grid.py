@@ -46,7 +46,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import engine, ops, parallel
+from . import engine, grid2d, ops, parallel
 from . import transform as T
 from .styler_base import StylerBase
 from .util import temporal_weights
@@ -67,7 +67,16 @@ class Styler(StylerBase):
     the per-iteration rows of all octaves in order, ``'d_intm'`` per octave but the last the uint8 identity-rotation
     renders of the key frames this rank holds (concatenated along axis 0, styler_3p.py:365-390), ``'opt_octave'`` per
     octave {own key frame: the variable as the octave left it, at that octave's size}, ``'octave_sizes'`` the sizes;
-    everything else is at full resolution."""
+    everything else is at full resolution.
+
+    ``len(config.resolution) == 2`` selects the 2-D path (``grid2d.GridStylizer2D``): ``params['d']`` frames [H,W],
+    ``params['v']`` [H,W,2], ``v_init`` [H,W,2] / ``s_init`` [H,W] / ``p_init`` [H,W] / ``sp_init`` [H,W,2] = (psi, phi).  The
+    frame loop, sharding, temporal weights, ``interp``, ``frames_per_opt``, the 'd' mask and the octaves are the code
+    below unchanged (``ops.transport_step2d`` crosses frames, ``ops.resize3d`` resamples the depth-1 volume); the result
+    holds ``'d'`` float32 [F,H,W,1] (the clipped image), ``'r'`` uint8 [F,H,W,3], ``'v'`` [H,W,2], ``'s'`` / ``'phi'``
+    [H,W].  Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
+    sharding, a MacCormack transport between frames, ``batch_size > 1``, a root-level driver (the reference has none for
+    grids)."""
 
     def __init__(self, self_dict):
         StylerBase.__init__(self, self_dict)
@@ -82,6 +91,12 @@ class Styler(StylerBase):
                              % self.octave_n)
         if abs(getattr(self, "lr_scale", 1) - 1) > 1e-7 and not isinstance(self.lr, list):
             self.lr = [self.lr / self.lr_scale ** i for i in range(self.octave_n)]      # styler_3p.py:236-238
+        self.is2d = len(self.resolution) == 2                          # an [H,W] grid: the 2-D path (grid2d.py)
+        if self.is2d and self.rotate:
+            raise ValueError("rotate=True with a 2-D resolution %s: a 2-D density is its own image, there are no views"
+                             % (list(self.resolution),))
+        if self.is2d and getattr(self, "optimizer", "adam") == "lbfgs":
+            raise ValueError("optimizer='lbfgs' is not built for the 2-D grid path: use 'adam'")
         self.octave_sizes = octave_sizes(self.resolution, self.octave_n, self.octave_scale)
         if self.octave_n > 1 and min(self.octave_sizes[0]) < 2:
             raise ValueError("octave_n=%d at octave_scale=%g takes resolution %s down to %s: every octave needs at least "
@@ -93,7 +108,7 @@ class Styler(StylerBase):
                                                   nv=self.n_views)
             if self.n_views is None:
                 self.n_views = len(self.views)
-        self.loss = self._make_loss(rotate=self.rotate)
+        self.loss = self._make_image_loss() if self.is2d else self._make_loss(rotate=self.rotate)
         self._identity = T.rot_to_device([np.identity(3)], self.device)
         self.recursive = bool(getattr(self, "transport_recursive", True))
         self.pg = None          # set by the driver: frames shard over the ranks of this group
@@ -101,6 +116,20 @@ class Styler(StylerBase):
     # ---- helpers ---------------------------------------------------------------------------------------------------
     def _dev(self, a):
         return torch.as_tensor(np.asarray(a, np.float32)).to(self.device).contiguous()
+
+    def _make_image_loss(self):
+        """the 2-D path's loss: ``engine.ImageStyleLoss`` on the clipped density as a one-channel image"""
+        w_layers = list(self.w_style_layer)
+        if len(w_layers) == 1 and len(self.style_layer) > 1:
+            w_layers = w_layers * len(self.style_layer)
+        return engine.ImageStyleLoss(self.net, self.style_layer, w_layers, self.w_style, w_tv=self.w_tv,
+                                     resize_scale=self.resize_scale, style_mask=getattr(self, "style_mask", False),
+                                     w_content=getattr(self, "w_content", 0),
+                                     content_layer=getattr(self, "content_layer", None),
+                                     content_channel=getattr(self, "content_channel", 0),
+                                     w_content_amp=getattr(self, "w_content_amp", 100),
+                                     w_hist=getattr(self, "w_hist", 0), hist_layer=getattr(self, "hist_layer", ()),
+                                     w_hist_layer=getattr(self, "w_hist_layer", ()))
 
     def _rank_world(self):
         return (0, 1) if self.pg is None else parallel.rank_world(self.pg)
@@ -123,6 +152,7 @@ class Styler(StylerBase):
         ``StylerBase._transport`` (styler_base.py:59-74):
           recursive   a < b: g <- advect(g, +u_i), i = a..b-1;   a > b: g <- advect(g, -u_i), i = a-1..b   (Horner form)
           one-step    a < b: advect(g, +u_a (b-a));              a > b: advect(g, -u_{a-1} (a-b))          (direct sum)"""
+        step = ops.transport_step2d if self.is2d else ops.transport_step     # (2-D: upd [H,W,C], u [H,W,2])
         j = keys.index(t)
         out, w_out = upd[t], float(W[j, j])          # running result = w_out * out (scaled lazily by the next launch)
         if not self.recursive:
@@ -131,7 +161,7 @@ class Styler(StylerBase):
                 if jj == j or W[j, jj] == 0.0:
                     continue
                 a, scale = (s, float(t - s)) if s < t else (s - 1, -float(s - t))
-                out = ops.transport_step(upd[s], u[a], scale, float(W[j, jj]), out, w_out)
+                out = step(upd[s], u[a], scale, float(W[j, jj]), out, w_out)
                 w_out = 1.0
             return out if w_out == 1.0 else out * w_out
         for sign in (+1, -1):
@@ -152,7 +182,7 @@ class Styler(StylerBase):
                             add, w_add = out, w_out
                         elif W[j, nxt] != 0.0:
                             add, w_add = upd[s2], float(W[j, nxt])
-                    S = ops.transport_step(S, u[i], float(sign), w_S, add, w_add)
+                    S = step(S, u[i], float(sign), w_S, add, w_add)
                     w_S = 1.0
                 jj = nxt
             out, w_out = S, 1.0
@@ -220,7 +250,7 @@ class Styler(StylerBase):
         if st.Wt is not None and st.mine and not st.u_full:
             raise ValueError("params['v'] (simulation velocities) is needed to align the updates of a sequence")
         st.u_full = st.u_full or {}
-        st.C = {"v": 3, "s": 3, "sp": 4}.get(self.target, 1)
+        st.C = ({"v": 2, "sp": 2} if self.is2d else {"v": 3, "s": 3, "sp": 4}).get(self.target, 1)
         # the variable per key frame: stylisation velocity (zero, or params['v_init'][t]) / the density itself.
         # NOTE: at velocity == 0 every back-traced point sits exactly on a grid node, where the trilinear stencil has a
         # kink -- the first gradient is a one-sided derivative whose side depends on float rounding
@@ -233,8 +263,11 @@ class Styler(StylerBase):
     def _resample(self, x, size, factor=1.0):
         """a volume [D,H,W] or [D,H,W,C] at ``size``: the corner-aligned bilinear resample of the octaves (the very tensor
         where the size is its own: one octave issues no resize)"""
-        if tuple(x.shape[:3]) == tuple(size):
+        if tuple(x.shape[:len(size)]) == tuple(size):
             return x
+        if self.is2d:                      # the depth-1 volume: bilinear over (H, W), nothing to do over D
+            return ops.resize3d(x.contiguous().unsqueeze(0), (1,) + tuple(size), "bilinear", align_corners=True,
+                                scale=factor).squeeze(0)
         return ops.resize3d(x.contiguous(), size, "bilinear", align_corners=True, scale=factor)
 
     def _factor(self, n_in, n_out):
@@ -251,10 +284,11 @@ class Styler(StylerBase):
         resampled ``'_init'``; later: ``g_opt`` resampled from the size ``prev``), fresh optimiser state and stylizer"""
         st = self._st
         o = st.octave
-        D, H, W_ = size = tuple(int(n) for n in self.octave_sizes[o])
+        size = tuple(int(n) for n in self.octave_sizes[o])
+        H, W_ = size[-2:]
         st.d = {t: self._resample(x, size) for t, x in st.d_full.items()}
         st.u = {t: self._resample(x, size) for t, x in st.u_full.items()}
-        st.shape = (D, H, W_, st.C)
+        st.shape = size + (st.C,)
         if self.style_img is not None:
             self.loss.set_style_image(self._style_feature(self.style_img, [H, W_]))
             if getattr(self, "w_hist", 0) > 0:
@@ -271,8 +305,12 @@ class Styler(StylerBase):
         # (a rank beyond the number of optimiser groups owns no frame: it only takes part in the collectives)
         first = st.d[st.mine[0]] if st.mine else (next(iter(st.d.values())) if st.d else
                                                   torch.zeros(size, device=self.device))
-        st.gs = engine.GridStylizer(self.loss, first, k=self.k, target=self.target, lr=st.lr,
-                                    optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
+        if self.is2d:
+            st.gs = grid2d.GridStylizer2D(self.loss, first, target=self.target, lr=st.lr,
+                                          optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
+        else:
+            st.gs = engine.GridStylizer(self.loss, first, k=self.k, target=self.target, lr=st.lr,
+                                        optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
         st.opt_ = {}
         st.hist_octave.append([])
 
@@ -287,13 +325,15 @@ class Styler(StylerBase):
             if vi is not None:
                 full = tuple(int(n) for n in self.resolution)
                 vi = self._dev(vi).reshape(full + (st.C,))
-                return self._resample(vi, st.shape[:3], self._factor(full, st.shape[:3])).reshape(st.shape).clone()
+                return self._resample(vi, st.shape[:-1], self._factor(full, st.shape[:-1])).reshape(st.shape).clone()
         return torch.zeros(st.shape, device=self.device)
 
     def _infer(self, t, var):
         """frame t through its variable: (velocity the variable stands for or None, smoothed density, render with the
         identity rotation [1,H,W,3])"""
         st = self._st
+        if self.is2d:
+            return self._infer2d(t, var)
         D, H, W_, _ = st.shape
         sourced = self.target in engine.SOURCED
         if self.target == "p":
@@ -308,10 +348,36 @@ class Styler(StylerBase):
         d_out = ops.smooth3d_relu_fwd(d_adv.contiguous(), float(self.k))
         return (vel if sourced else None), d_out, self.loss.d_img(d_out, self._identity)
 
+    def _infer2d(self, t, var):
+        """``_infer`` on the 2-D path: (velocity [H,W,2] or None, the clipped image [H,W], its 0..255 rendering [1,H,W,3])"""
+        st = self._st
+        H, W_, _ = st.shape
+        vel = None
+        if self.target != "d":
+            var = var.reshape(self._var_shape()).contiguous()
+            if self.adv_order == 2 or self.target in engine.SOURCED:
+                vel = var if self.target == "v" else ops.source2d_velocity(self.target, var)
+            if self.adv_order == 2:
+                d_adv = ops.advect_maccormack(st.d[t].unsqueeze(-1), vel).squeeze(-1)
+            else:
+                d_adv = ops.advect2d_source_fwd(self.target, st.d[t], var)
+        else:
+            d_adv = var.reshape(H, W_)
+        img = ops.colour_clamp_gather(d_adv.reshape(H * W_, 1).contiguous())
+        r, _ = ops.loss_net_input_fwd(img.view(1, H, W_, 1), want_x=False)
+        return (vel if self.target in engine.SOURCED else None), img.view(H, W_), r
+
+    def _var_shape(self):
+        """the variable as the stylizer takes it and the result holds it"""
+        st = self._st
+        if self.is2d:
+            return st.shape if self.target == "d" else ops.source2d_shape(self.target, *st.shape[:2])
+        return st.shape[:3] if self.target == "p" else st.shape
+
     def _octave_variables(self):
         """what an octave leaves behind: the variable of every own key frame at the octave's size"""
         st = self._st
-        shp = st.shape[:3] if self.target == "p" else st.shape
+        shp = self._var_shape()
         return {t: st.g_opt[t].reshape(shp).cpu().numpy() for t in st.mine}
 
     def next_octave(self):
@@ -323,18 +389,17 @@ class Styler(StylerBase):
             raise ValueError("next_octave(): octave %d of %d is the last" % (st.octave, self.octave_n))
         st.opt_octave.append(self._octave_variables())
         imgs = [self._infer(t, st.g_opt[t])[2].cpu().numpy().astype(np.uint8) for t in st.mine]
-        st.d_intm.append(np.concatenate(imgs, axis=0) if imgs else np.zeros((0,) + st.shape[1:3] + (3,), np.uint8))
-        prev = st.shape[:3]
+        st.d_intm.append(np.concatenate(imgs, axis=0) if imgs else np.zeros((0,) + st.shape[-3:-1] + (3,), np.uint8))
+        prev = st.shape[:-1]
         st.octave += 1
         self._enter_octave(prev)
-        return list(st.shape[:3])
+        return list(st.shape[:-1])
 
     def iterate(self):
         """one iteration of the frame loop (styler_3p.py:301-386): a stylisation step per own key frame, the halo
         exchange of the updates, their temporal alignment, ``g_opt += `` -- returns the per-key-frame losses (device
         tensor, summed over ranks)"""
         st = self._st
-        D, H, W_, _ = st.shape
         losses = torch.zeros(len(st.keys), device=self.device)
         upd = {}
         for j, t in enumerate(st.keys):
@@ -344,8 +409,12 @@ class Styler(StylerBase):
                 if adam is None:
                     adam = st.opt_[slot] = engine.make_optimizer(getattr(self, "optimizer", "adam"))
                 st.work.copy_(st.g_opt[t])
-                st.gs.bind(st.d[t], st.work.view(D, H, W_, st.C) if st.C > 1 else st.work.view(D, H, W_), adam)
-                losses[j] = st.gs.step(self._rot())
+                if self.is2d:
+                    st.gs.bind(st.d[t], st.work.view(st.shape[:2] if self.target == "d" else self._var_shape()), adam)
+                    losses[j] = st.gs.step()
+                else:
+                    st.gs.bind(st.d[t], st.work.view(st.shape if st.C > 1 else st.shape[:3]), adam)
+                    losses[j] = st.gs.step(self._rot())
                 dlt = torch.nan_to_num(st.gs.var.reshape(st.shape)) - st.g_opt[t]
                 if self.target == "d":
                     dlt = dlt * st.d[t].reshape(st.shape)          # masking by original density (361-363)
@@ -381,7 +450,6 @@ class Styler(StylerBase):
         ``prepare(frames_on_device=...)`` -- ``result['frames']`` lists which entries of ``d`` / ``r`` / ``v`` these
         are"""
         st = self._st
-        D, H, W_, _ = st.shape
         allv = self.key_frame_variables()
         full = {t: allv[t] for t in st.keys}
         if self.interp > 1:
@@ -397,8 +465,8 @@ class Styler(StylerBase):
             var = full.get(t)
             if var is None:                                        # trailing frames past the last key frame
                 var = self._initial(t)
-            if self.target == "p":
-                var = var.reshape(D, H, W_)                        # (the potential in the shape of params['p_init'][t])
+            if self.target == "p" or self.is2d:
+                var = var.reshape(self._var_shape())               # (the potential in the shape of params['p_init'][t])
             vel, d_out, dimg = self._infer(t, var)
             d_sty.append(torch.abs(d_out).unsqueeze(-1).cpu().numpy())   # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
@@ -410,8 +478,8 @@ class Styler(StylerBase):
         return {"l": per_octave, "l_frames": hist, "d_intm": list(st.d_intm), "opt_octave": st.opt_octave + [self._octave_variables()],
                 "octave_sizes": [[int(n) for n in sz] for sz in self.octave_sizes],
                 "d": np.array(d_sty), "r": np.array(r_sty), "v": v_sty if self.target == "v" else u_sty if sourced else None,
-                "s": v_sty if self.target == "s" else [a[..., :3] for a in v_sty] if self.target == "sp" else None,
-                "phi": v_sty if self.target == "p" else [a[..., 3] for a in v_sty] if self.target == "sp" else None,
+                "s": v_sty if self.target == "s" else [a[..., 0] if self.is2d else a[..., :3] for a in v_sty] if self.target == "sp" else None,
+                "phi": v_sty if self.target == "p" else [a[..., -1] for a in v_sty] if self.target == "sp" else None,
                 "opt": v_sty, "p": None, "c": None, "frames": present}
 
     def run(self, params):

@@ -36,6 +36,33 @@ def curl_velocity(G, rng, max_cells=2.0):
     return v.astype(np.float32)
 
 
+def blob_density2d(H, W, rng, n_blobs=32):
+    """``blob_density`` on an [H,W] grid, the same draws per blob (centre U[.2,.8]^2, sigma U[.03,.10] * min(H,W),
+    amplitude U[.2,1]), clipped to [0,1], values < 0.02 zeroed"""
+    ay, ax = np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64)
+    d = np.zeros((H, W), np.float64)
+    for _ in range(n_blobs):
+        c = rng.uniform(0.2, 0.8, 2) * (np.array([H, W]) - 1)
+        s = rng.uniform(0.03, 0.10) * min(H, W)
+        a = rng.uniform(0.2, 1.0)
+        d += a * np.outer(np.exp(-0.5 * ((ay - c[0]) / s) ** 2), np.exp(-0.5 * ((ax - c[1]) / s) ** 2))
+    d = np.clip(d, 0.0, 1.0)
+    d[d < 0.02] = 0.0
+    return d.astype(np.float32)
+
+
+def curl_velocity2d(H, W, rng, max_cells=2.0):
+    """divergence-free velocity [H,W,2] in the advect2d() units (component k along array axis k): the 2-D curl
+    (-d/dW, d/dH) of a smooth stream function (white noise, Gaussian sigma = min(H,W)/16), scaled so that the largest
+    displacement along an axis is ``max_cells`` cells of that axis"""
+    from scipy.ndimage import gaussian_filter
+    psi = gaussian_filter(rng.randn(H, W), sigma=min(H, W) / 16.0)
+    v = np.stack([-np.gradient(psi, axis=1), np.gradient(psi, axis=0)], -1)
+    cells = np.abs(v) * (np.array([H, W]) - 1) / 2.0
+    v *= max_cells / cells.max()
+    return v.astype(np.float32)
+
+
 def uniform_views(V):
     """V=8: the lattice phi in {-5,5}, theta in {-10,-10/3,10/3,10} (config.py:63-68 defaults);
     other V: theta evenly spaced in [-10,10] at phi 0 (odd) or phi in {-5,5} (even)."""
