@@ -116,12 +116,23 @@ except OSError as e:
     raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (GRID2D_HEADER_PATH, e))
 GRID2D_ABI_VERSION = _c2["NFS_GRID2D_ABI_VERSION"]
 
+# libnfs_descent.so (the update kernels of optimizer 'lapnorm'): the third library and header, bound the same way
+DESCENT_LIB_PATH = os.path.join(_HERE, "libnfs_descent.so")
+DESCENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_descent.h"))
+try:
+    with open(DESCENT_HEADER_PATH) as _f:
+        DESCENT_SIGNATURES, DESCENT_RESTYPES, _, _c3 = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (DESCENT_HEADER_PATH, e))
+DESCENT_ABI_VERSION = _c3["NFS_DESCENT_ABI_VERSION"]
+
 _lib = None
 _lib2d = None
+_libdescent = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so and libnfs_grid2d.so (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so and libnfs_descent.so (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -166,31 +177,47 @@ def lib():
     return _lib
 
 
+def _load_beside(path, signatures, restypes, version_fn, abi):
+    """a library that links against libnfs_hip.so (one error channel, one HIP runtime), loaded after it and checked
+    against its own header: every declared symbol present, the version the header's"""
+    lib()
+    so = os.path.basename(path)
+    if not os.path.exists(path):
+        raise NfsLibraryError(
+            "%s is missing (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "-- there is no CPU fallback for the product path" % (so, path))
+    try:
+        L = C.CDLL(path)
+    except OSError as e:  # pragma: no cover
+        raise NfsLibraryError("cannot load %s: %s" % (path, e))
+    for name, argt in signatures.items():
+        try:
+            f = getattr(L, name)
+        except AttributeError:
+            raise NfsLibraryError("%s does not export %s (stale build?)" % (so, name))
+        f.argtypes = argt
+        f.restype = restypes[name]
+    if getattr(L, version_fn)() != abi:
+        raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d: rebuild (make -C %s)"
+                              % (path, getattr(L, version_fn)(), abi, CSRC_DIR))
+    return L
+
+
 def lib2d():
     """libnfs_grid2d.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
     global _lib2d
     if _lib2d is None:
-        lib()
-        if not os.path.exists(GRID2D_LIB_PATH):
-            raise NfsLibraryError(
-                "libnfs_grid2d.so is missing (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "-- there is no CPU fallback for the product path" % GRID2D_LIB_PATH)
-        try:
-            L = C.CDLL(GRID2D_LIB_PATH)
-        except OSError as e:  # pragma: no cover
-            raise NfsLibraryError("cannot load %s: %s" % (GRID2D_LIB_PATH, e))
-        for name, argt in GRID2D_SIGNATURES.items():
-            try:
-                f = getattr(L, name)
-            except AttributeError:
-                raise NfsLibraryError("libnfs_grid2d.so does not export %s (stale build?)" % name)
-            f.argtypes = argt
-            f.restype = GRID2D_RESTYPES[name]
-        if L.nfs_grid2d_version() != GRID2D_ABI_VERSION:
-            raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d: rebuild (make -C %s)"
-                                  % (GRID2D_LIB_PATH, L.nfs_grid2d_version(), GRID2D_ABI_VERSION, CSRC_DIR))
-        _lib2d = L
+        _lib2d = _load_beside(GRID2D_LIB_PATH, GRID2D_SIGNATURES, GRID2D_RESTYPES, "nfs_grid2d_version", GRID2D_ABI_VERSION)
     return _lib2d
+
+
+def libdescent():
+    """libnfs_descent.so, loaded the same way"""
+    global _libdescent
+    if _libdescent is None:
+        _libdescent = _load_beside(DESCENT_LIB_PATH, DESCENT_SIGNATURES, DESCENT_RESTYPES, "nfs_descent_version",
+                                   DESCENT_ABI_VERSION)
+    return _libdescent
 
 
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
@@ -203,8 +230,10 @@ PROFILE = None
 def call(name, *args):
     """Call an int-returning entry point; raise with nfs_last_error() on failure."""
     L = lib()
-    if name in GRID2D_SIGNATURES:            # (the error text stays libnfs_hip.so's: the two share nfs::set_error)
+    if name in GRID2D_SIGNATURES:            # (the error text stays libnfs_hip.so's: the libraries share nfs::set_error)
         L, L0 = lib2d(), L
+    elif name in DESCENT_SIGNATURES:
+        L, L0 = libdescent(), L
     else:
         L0 = L
     if PROFILE is not None:

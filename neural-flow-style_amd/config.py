@@ -9,7 +9,12 @@ one-Adam-step-per-view loop, ``sum`` = gradient of the summed view losses, shard
 opt-in to seeded synthetic VGG filters when no converted checkpoint exists), ``--ray_mode`` (``max`` / ``mean``: the
 per-ray reductions north_star names beside the reference's transmittance / liquid integrals; '' follows
 ``render_liquid``).  The reference's own ``--optimizer`` flag (config.py:78, default 'adam', the only value its code
-honours) additionally takes ``lbfgs`` here: limited-memory BFGS, north_star's other outer loop (engine.LBFGSState).
+honours) additionally takes ``lbfgs`` here: limited-memory BFGS, north_star's other outer loop (engine.LBFGSState),
+and -- on the grid path -- ``lapnorm``: Laplacian-normalised descent (engine.LapDescentState) with ``--lap_n`` pyramid
+levels (0: mean-|g| normalisation).  ``--lr_decay``: the factor of the reference's ``cosine_decay`` (util.py:49-53) on the
+grid path's learning rate, from ``lr_decay * lr`` at the first iteration of an octave down to ``lr``; 1 = constant.
+``--lr_decay`` (float, default 1) and ``--lap_n`` (int, default 3) are parsed when given and otherwise defaulted by
+``complete()``, like the attributes the drivers inject.
 """
 from __future__ import annotations
 
@@ -99,6 +104,10 @@ _FLAGS = [
     ("MI355X", "synthetic_weights", dict(type=str2bool, default=False)),
     ("MI355X", "transport_recursive", dict(type=str2bool, default=True)),
     ("MI355X", "ray_mode", dict(type=str, default="", choices=["", "transmit", "liquid", "max", "mean"])),
+    # (argparse.SUPPRESS: parsed when given; their defaults -- 1 and 3 -- come from complete(), which every Styler calls,
+    # so that the Namespace of a bare get_config([]) stays the reference's flags plus the five extras above)
+    ("MI355X", "lr_decay", dict(type=float, default=argparse.SUPPRESS)),
+    ("MI355X", "lap_n", dict(type=int, default=argparse.SUPPRESS)),
 ]
 
 
@@ -121,6 +130,23 @@ def get_config(argv=None):
     return config, unparsed
 
 
+def check_optimizer(config, grid):
+    """the build-specific optimiser flags, checked where a stylizer is constructed (``grid``: the grid path, styler_grid):
+    ValueError naming the flag for ``lap_n`` < 0, ``lr_decay`` <= 0, and ``optimizer='lapnorm'`` on the particle stylizers --
+    a Laplacian pyramid needs a grid, and particle attributes have none"""
+    lap_n, lr_decay = getattr(config, "lap_n", 3), getattr(config, "lr_decay", 1)
+    if int(lap_n) < 0:
+        raise ValueError("--lap_n %d: the number of pyramid levels of optimizer 'lapnorm' is 0 (mean-|g| normalisation) "
+                         "or more" % int(lap_n))
+    if not float(lr_decay) > 0:
+        raise ValueError("--lr_decay %g: the cosine schedule's factor must be positive (1 = constant learning rate)"
+                         % float(lr_decay))
+    if getattr(config, "optimizer", "adam") == "lapnorm" and not grid:
+        raise ValueError("--optimizer lapnorm on a particle stylizer (styler_3p / styler_2p): the Laplacian pyramid needs a "
+                         "grid and particle attributes have none -- it is an optimiser of the grid path (styler_grid, "
+                         "--grid_variable); use 'adam' or 'lbfgs' here")
+
+
 def complete(config):
     """defaults for the attributes the reference drivers inject after parsing"""
     if not hasattr(config, "rng") or config.rng is None:
@@ -139,5 +165,9 @@ def complete(config):
         config.transport_recursive = True
     if not hasattr(config, "ray_mode"):
         config.ray_mode = ""
+    if not hasattr(config, "lr_decay"):
+        config.lr_decay = 1
+    if not hasattr(config, "lap_n"):
+        config.lap_n = 3
 
     return config

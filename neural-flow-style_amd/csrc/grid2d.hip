@@ -10,7 +10,7 @@
 // Streaming kernels over at most a few MB: one pixel per lane, row-major, no LDS, no atomics.  H, W >= 2, H * W < 2^30:
 // every index is an int, and every index a kernel forms comes out of axis2d (clamped into [0, n), NaN included) or
 // FdEnd::other / fd_adj (a neighbour inside the array by construction).
-#include "source_ops.h"
+#include "advect_stencil.h"
 #include "../../include/nfs_grid2d.h"
 
 namespace nfs {
@@ -52,52 +52,7 @@ __device__ __forceinline__ float source2d_adj(const float* __restrict__ g, int y
 
 template <int SRC> struct Var2 { static constexpr int NCH = (SRC == SRC_VEL || SRC == SRC_HELMHOLTZ) ? 2 : 1; };
 
-struct Bilinear {
-  int o00, o01, o10, o11;       // o[p][q]: corner p along H, q along W
-  float wy0, wy1, wx0, wx1;
-};
-// Bit-identity with nfs_advect2d_fwd / _bwd (C = 1) needs the very roundings of warp2d.hip's kernels.  Those are compiled
-// with floating-point contraction on, and which products the compiler fused there is not visible in their source: for
-// C = 1 the forward sum is four plain products and three plain additions; the adjoint forms each axis' bracket as ONE
-// fused multiply-add onto ONE plain product (the fused term is the (1 - dx) one along H and the dx one along W) and adds
-// it to its channel sum by an FMA; lin_coord is an FMA in both.  So the arithmetic below is written out with contraction
-// OFF and explicit fmaf() where those kernels fuse; tests/test_grid2d_kernels_gpu.py holds the two together bit for bit.
-__device__ __forceinline__ Axis axis2d(int i, int n, float vel) {
-#pragma clang fp contract(off)
-  const float step = 2.f / (float)(n - 1);                        // (n >= 2)
-  const float c = fmaf(step, (float)i, -1.f) - vel;               // lin_coord(i, n) - vel
-  const float x = (c + 1.f) * (float)(n - 1) * 0.5f;
-  float f = floorf(x);
-  f = fminf(fmaxf(f, -1.f), (float)n);                            // keeps the int conversion defined (also for NaN)
-  const int k = (int)f;
-  Axis a;
-  a.i0 = min(max(k, 0), n - 1);
-  a.i1 = min(max(k + 1, 0), n - 1);
-  a.w1 = x - (float)a.i0;
-  return a;
-}
-__device__ __forceinline__ Bilinear bilinear_setup(int y, int x, int H, int W, float v0, float v1) {
-#pragma clang fp contract(off)
-  const Axis ay = axis2d(y, H, v0), ax = axis2d(x, W, v1);
-  return Bilinear{ay.i0 * W + ax.i0, ay.i0 * W + ax.i1, ay.i1 * W + ax.i0, ay.i1 * W + ax.i1,
-                  1.f - ay.w1, ay.w1, 1.f - ax.w1, ax.w1};
-}
-// add_n order of the reference: w00 I00 + w01 I01 + w10 I10 + w11 I11
-__device__ __forceinline__ float advect2d_sample(const float* __restrict__ d, const Bilinear& b) {
-#pragma clang fp contract(off)
-  const float w00 = b.wy0 * b.wx0, w01 = b.wy0 * b.wx1, w10 = b.wy1 * b.wx0, w11 = b.wy1 * b.wx1;
-  return ((w00 * d[b.o00] + w01 * d[b.o01]) + w10 * d[b.o10]) + w11 * d[b.o11];
-}
-// g_vel of one pixel: minus the sample's derivative along each axis in normalised units, times g
-__device__ __forceinline__ F2u advect2d_grad(const float* __restrict__ d, const Bilinear& b, float g, int H, int W) {
-#pragma clang fp contract(off)
-  const float v00 = d[b.o00], v01 = d[b.o01], v10 = d[b.o10], v11 = d[b.o11];
-  float gy = fmaf(g, fmaf(b.wx0, v10 - v00, b.wx1 * (v11 - v01)), 0.f);
-  float gx = fmaf(g, fmaf(b.wy1, v11 - v10, b.wy0 * (v01 - v00)), 0.f);
-  gy *= (float)(H - 1) * 0.5f;
-  gx *= (float)(W - 1) * 0.5f;
-  return F2u{-gy, -gx};
-}
+// (Bilinear, axis2d, bilinear_setup, advect2d_sample, advect2d_grad: advect_stencil.h, shared with descent.hip)
 
 // MODE 0: out = advect2d(d, vel(var));  1: g_vel of that advect;  2 (SRC_VEL): g_vel consumed by ApplyAdam on var = vel,
 // m, v in place, then out (nullable) = advect2d(d, updated vel) -- all local to the pixel (d is constant)

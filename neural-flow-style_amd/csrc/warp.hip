@@ -3,7 +3,7 @@
 // stores and near-coalesced gathers; coordinates are generated in registers (the
 // reference materialises 3 coordinate volumes + 8 index/weight/gather tensors).
 // HBM-bound: algorithmic bytes = read volume once + write output once.
-#include "source_ops.h"
+#include "advect_stencil.h"
 #include <stdlib.h>
 
 namespace nfs {
@@ -152,104 +152,8 @@ __global__ void __launch_bounds__(256) warp_bwd_kernel(WarpArgs a, const float* 
 struct AdamFused { float* m; float* v; float lr_t, b1, b2, eps; float* adv_next = nullptr;
                    unsigned long long* live = nullptr; unsigned long long* ever = nullptr; };
 
-// live mask (nullable; whole-volume launches only): bit i of the mask = "the eight density corners the back-traced point
-// of voxel i interpolates are NOT all equal".  Where they are equal the sample does not depend on the coordinate and the
-// velocity gradient of that voxel is g * 0 whatever g is, so the adjoint chain above it (rotate, smooth) need not
-// produce g there (rotate_bwd_tiled_kernel skips the tiles / clips to the box that matter).  A wave's lanes hold 64
-// consecutive voxels per j: one ballot = one 64-bit word of the mask.
-__device__ __forceinline__ bool corners_differ(const F2u (&p)[4]) {
-  const float a = p[0].x;
-  return !(p[0].y == a && p[1].x == a && p[1].y == a && p[2].x == a && p[2].y == a && p[3].x == a && p[3].y == a);
-}
-
-// ---- the lean stencil (advect1_kernel, transport_step_kernel), every piece of it written once ---------------------
-// per-volume constants: (n-1)/2 per axis (velocity -> voxels), n-1 per axis (the clamp), row and plane strides
-struct LeanDims { float hz, hy, hx, nz1, ny1, nx1; unsigned uW, uHW; };
-__device__ __forceinline__ LeanDims lean_dims(int D, int H, int W) {
-  return {0.5f * (float)(D - 1), 0.5f * (float)(H - 1), 0.5f * (float)(W - 1),
-          (float)(D - 1), (float)(H - 1), (float)(W - 1), (unsigned)W, (unsigned)(H * W)};
-}
-
-// back-traced point of voxel (z, h, w): coordinate x = index - vel * (n-1)/2 by one FMA (un-clamped: the gradient asks
-// whether it lies inside), clamped to [0, n-1], base cell min(floor, n-2), weights in [0,1], linear offset of the base cell
-struct LeanCell { float xz, xy, xx, wz, wy, wx; unsigned o; };
-__device__ __forceinline__ LeanCell lean_cell(const F3u& v, int z, int h, int w, const LeanDims& s) {
-  LeanCell c;
-  c.xz = fmaf(-v.x, s.hz, (float)z); c.xy = fmaf(-v.y, s.hy, (float)h); c.xx = fmaf(-v.z, s.hx, (float)w);
-  const float cz = __builtin_amdgcn_fmed3f(c.xz, 0.f, s.nz1), cy = __builtin_amdgcn_fmed3f(c.xy, 0.f, s.ny1),
-              cx = __builtin_amdgcn_fmed3f(c.xx, 0.f, s.nx1);
-  const float bz = fminf(floorf(cz), s.nz1 - 1.f), by = fminf(floorf(cy), s.ny1 - 1.f), bx = fminf(floorf(cx), s.nx1 - 1.f);
-  c.wz = cz - bz; c.wy = cy - by; c.wx = cx - bx;
-  c.o = (unsigned)(int)bz * s.uHW + (unsigned)(int)by * s.uW + (unsigned)(int)bx;
-  return c;
-}
-
-// the four rows (z,y), (z,y+1), (z+1,y), (z+1,y+1) of the cell at offset o, each an (x, x+1) pair of T
-template <typename T>
-__device__ __forceinline__ void lean_gather(const T* d, unsigned o, const LeanDims& s, T (&lo)[4], T (&hi)[4]) {
-  const unsigned r[4] = {o, o + s.uW, o + s.uHW, o + s.uHW + s.uW};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { lo[k] = d[r[k]]; hi[k] = d[r[k] + 1]; }
-}
-// ... of a scalar field: one dword-aligned 8-byte load per row
-__device__ __forceinline__ void lean_gather(const float* d, unsigned o, const LeanDims& s, F2u (&p)[4]) {
-  p[0] = *reinterpret_cast<const F2u*>(d + o);
-  p[1] = *reinterpret_cast<const F2u*>(d + o + s.uW);
-  p[2] = *reinterpret_cast<const F2u*>(d + o + s.uHW);
-  p[3] = *reinterpret_cast<const F2u*>(d + o + s.uHW + s.uW);
-}
-
-// trilinear combine: x within each row (e: the row's difference, a: its value at wx), then y, then z
-__device__ __forceinline__ void lean_rows(const F2u (&p)[4], float wx, float (&e)[4], float (&a)[4]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { e[k] = p[k].y - p[k].x; a[k] = fmaf(wx, e[k], p[k].x); }
-}
-__device__ __forceinline__ float lean_sample(const F2u (&p)[4], float wx, float wy, float wz) {
-  float e[4], a[4];
-  lean_rows(p, wx, e, a);
-  const float b0 = fmaf(wy, a[1] - a[0], a[0]), b1 = fmaf(wy, a[3] - a[2], a[2]);
-  return fmaf(wz, b1 - b0, b0);
-}
-
-// gradient of that sample along (z, y, x), in cells: difference of the two faces, interpolated in the other two axes
-// (the arithmetic of advect1_kernel's adjoint branch)
-__device__ __forceinline__ void lean_grad(const F2u (&p)[4], float wx, float wy, float wz, float& dz, float& dy, float& dx) {
-  float e[4], a[4];
-  lean_rows(p, wx, e, a);
-  const float f0 = fmaf(wy, e[1] - e[0], e[0]), f1 = fmaf(wy, e[3] - e[2], e[2]);
-  dx = fmaf(wz, f1 - f0, f0);
-  const float g0 = a[1] - a[0], g1 = a[3] - a[2];
-  dy = fmaf(wz, g1 - g0, g0);
-  const float b0 = fmaf(wy, g0, a[0]), b1 = fmaf(wy, g1, a[2]);
-  dz = b1 - b0;
-}
-
-// next voxel of this lane: 64 further on (clamped at the end of the volume; those results are not stored)
-__device__ __forceinline__ void walk64(int& w, int& h, int& z, int W, int H, int zlast) {
-  w += 64;
-  while (w >= W) { w -= W; if (++h == H) { h = 0; if (z < zlast) ++z; } }
-}
-
-// A wave owns NV x 64 consecutive voxels and lane l takes l, l + 64, ...: every streamed access (12-byte velocity /
-// moment vectors, g_out, out) is then one contiguous run per instruction.  (Consecutive voxels per lane with float4
-// accesses put the lanes 48 bytes apart: 24 cache lines per instruction, a third of each used.)
-// XCD_ORDER: contiguous z-slab per XCD (workgroups are dealt round-robin to the 8 XCDs; the grid is a multiple of 8): the
-// gathered planes of neighbouring rows then come through one L2 instead of being fetched into all eight.
-// Returns the lane's first voxel; the wave has none when first - lane >= n.  (block_threads: blockDim.x, read by the kernel
-// itself -- only there does the compiler fold it to the launch's uniform block size.)
-template <int NV, bool XCD_ORDER>
-__device__ __forceinline__ int lane_first(unsigned block_threads, int lane) {
-  const unsigned per_xcd = gridDim.x / 8;
-  const unsigned lb = XCD_ORDER ? (blockIdx.x % 8) * per_xcd + blockIdx.x / 8 : blockIdx.x;
-  return (lb * block_threads + (threadIdx.x - lane)) * NV + lane;
-}
-// ... and its position (z, h, w), clamped into the volume; walk64 steps on from there
-__device__ __forceinline__ void lane_start(int first, int n, int H, int W, int& w, int& h, int& z) {
-  const int f0 = min(first, n - 1);
-  w = f0 % W;
-  const int t2 = f0 / W;
-  h = t2 % H; z = t2 / H;
-}
+// (the lean stencil -- corners_differ, lean_dims / lean_cell / lean_gather / lean_sample / lean_grad -- and the lane
+// layout -- walk64, lane_first, lane_start -- are advect_stencil.h: libnfs_descent.so forms the same samples from them)
 
 // MODE 0: forward; 1: velocity gradient -> out; 2: velocity gradient consumed on the spot by the TF-Adam update of
 // the velocity itself (vel, m, v updated in place: every thread reads and writes only its own 4 voxels of them;

@@ -808,21 +808,77 @@ class LBFGSState(object):
         x.reshape(-1).add_(d, alpha=self.t)
 
 
+class LapDescentState(object):
+    """Laplacian-normalised descent, the update rule of a transport-based stylizer (the reference ships its pieces --
+    ``util.lap_normalize``, util.py:95-110, and ``cosine_decay``, 49-53 -- and calls neither):
+
+        g^ = lap_normalize(g, scale_n=lap_n)       over ALL channels of the variable at once; lap_n = 0: g / max(mean|g|, 1e-7)
+        x  <- fma(-lr, g^, x)                       one fused multiply-add per element (``ops.descent_step``)
+
+    Every pyramid level enters with RMS 1, so ``lr`` is a length in the variable's own units, whatever the loss weights
+    are: for a velocity, lr = c * 2/(n-1) moves a voxel by about c cells per level and step, at every octave alike; a stream
+    function or potential is differenced per cell, so the same lr is a displacement.  A zero gradient gives a zero update
+    (0 / max(0, eps) = 0).  There is no state besides ``lap_n`` (no moments): ``optimizer_slot`` keys it as it keys Adam.
+    The reference's k5x5x5 / k5x5 tables exist for some channel counts only; they are one kernel times an identity, and the
+    per-channel kernels behind ``util.lap_normalize`` take any C (C = 4 and the 2-D counts run the generic gather forms).
+    ``nd`` (3 or 2): the grid's dimension, which a [H,W,2] velocity and a [D,H,W] potential do not tell apart; the
+    stylizers set it.  Same call surface as ``TFAdamState.step``."""
+
+    def __init__(self, lap_n=3, nd=None):
+        if int(lap_n) < 0:
+            raise ValueError("lap_n=%r: the number of pyramid levels is 0 (mean-|g| normalisation) or more" % (lap_n,))
+        self.lap_n = int(lap_n)
+        self.nd = nd
+
+    def advance(self):
+        """(nothing to advance: the call an idle rank makes on ``TFAdamState``)"""
+
+    def _nd(self, x, nd):
+        nd = nd or self.nd or {4: 3, 2: 2}.get(x.dim())
+        if nd not in (2, 3):
+            raise ValueError("LapDescentState: a %d-d variable does not say whether its grid is 2-D or 3-D: pass nd" % x.dim())
+        return nd
+
+    def normalized(self, g, nd=None):
+        """g^ of a gradient shaped like the variable -> [grid..., C]"""
+        from . import util
+        nd = self._nd(g, nd)
+        grid = tuple(g.shape[:nd])
+        c = g.numel() // max(int(np.prod(grid)), 1)
+        return util.lap_normalize(g.reshape(grid + (c,)), scale_n=self.lap_n, is_3d=nd == 3, c=c)
+
+    def step(self, x, g, lr, nd=None):
+        ops.descent_step(x, self.normalized(g.reshape(x.shape), nd), lr)
+
+    def step_through_advect(self, vel, d0, g, lr, adv_next, live_next=None):
+        """the same update of the velocity variable [D,H,W,3] of ``advect(d0, vel)``, and in the same pass ``adv_next`` =
+        advect(d0, updated vel) -- the next iteration's forward sample -- and ``live_next`` (optional) its live mask"""
+        ops.advect_descent(d0, vel, self.normalized(g, 3), lr, adv_next, live_next)
+
+    def step_through_advect2d(self, vel, d0, g, lr, adv_next):
+        """the 2-D twin: vel [H,W,2], d0 [H,W]"""
+        ops.advect2d_descent(d0, vel, self.normalized(g, 2), lr, adv_next)
+
+
 def optimizer_slot(kind, t, frames_per_opt):
     """key of the optimiser state frame ``t`` steps with.  Adam: ``t // frames_per_opt`` -- one (m, v, step count) shared
     by the frames of a group, updated by them in turn (styler_3p.py:315-323; the moments are running averages and
     tolerate it).  L-BFGS: one state PER FRAME -- its (s, y) pairs are differences of consecutive gradients of one
-    variable; pairs mixed across frames (or across particle counts) are not curvature of anything."""
+    variable; pairs mixed across frames (or across particle counts) are not curvature of anything.  'lapnorm' has no
+    per-variable state and is keyed as Adam is."""
     return ("lbfgs", int(t)) if kind == "lbfgs" else int(t) // int(frames_per_opt)
 
 
-def make_optimizer(kind="adam"):
-    """one optimiser state per ``opt_id`` (styler_3p.py:315-323): TF ApplyAdam (the reference) or L-BFGS (config.optimizer)"""
+def make_optimizer(kind="adam", lap_n=3):
+    """one optimiser state per ``opt_id`` (styler_3p.py:315-323): TF ApplyAdam (the reference), L-BFGS or Laplacian-
+    normalised descent with ``lap_n`` pyramid levels (config.optimizer, config.lap_n)"""
     if kind in (None, "", "adam"):
         return TFAdamState()
     if kind == "lbfgs":
         return LBFGSState()
-    raise ValueError("optimizer %r: 'adam' or 'lbfgs'" % (kind,))
+    if kind == "lapnorm":
+        return LapDescentState(lap_n=lap_n)
+    raise ValueError("optimizer %r: 'adam', 'lbfgs' or 'lapnorm'" % (kind,))
 
 
 SOURCED = ("s", "p", "sp")      # the grid variables a velocity is a function of (ops.source_velocity)
@@ -854,9 +910,20 @@ class GridStylizer(object):
     ``target='p'``: a potential ``phi`` [D,H,W] whose forward differences are the velocity (``ops.potential_velocity``:
     irrotational by construction -- local sources and sinks); ``target='sp'``: the Helmholtz pair ``a`` [D,H,W,4] =
     (psi, phi) with v = stream_velocity(psi) + potential_velocity(phi) (``ops.helmholtz_velocity``).  Both run exactly as
-    's' does, through ``ops.advect_source_fwd`` / ``_bwd`` and ``ops.source_bwd_adam`` of their kind."""
+    's' does, through ``ops.advect_source_fwd`` / ``_bwd`` and ``ops.source_bwd_adam`` of their kind.
+    ``optimizer='lapnorm'`` (``lap_n`` pyramid levels): Laplacian-normalised descent (``LapDescentState``) for all five
+    targets and both orders.  ``lr`` is then a length in the variable's units (every pyramid level enters with RMS 1): for
+    'v', lr = c * 2/(n-1) moves a voxel by about c cells per level and step; a stream function or potential is differenced
+    per cell, so the same lr is a displacement.  The loss chain, its hipGraph replay and the dead-region skipping of the
+    rotate adjoint ('v') are as with Adam; the update is outside the capture.  'v' at order 1 takes the fused kernel
+    (``ops.advect_descent``: update + next forward sample + its live mask, handled like ``advect_bwd_adam``'s
+    ``adv_next`` / ``live_next``; ``NFS_FUSE_ADVECT=0`` turns it off), every other case ``variable_gradient`` ->
+    ``LapDescentState.step`` and, where a fixed forward buffer is in use, ``_advect_now()``.  Never-live skipping is
+    Adam's and does not apply.  Over ranks: the all-reduce mode only (the normalisation is non-local and non-linear: it
+    must see the summed gradient), every rank computing the identical update; the D-slab mode is not entered."""
 
-    def __init__(self, loss, d0, k=3, target="v", lr=0.1, process_group=None, graph=None, optimizer="adam", adv_order=1):
+    def __init__(self, loss, d0, k=3, target="v", lr=0.1, process_group=None, graph=None, optimizer="adam", adv_order=1,
+                 lap_n=3):
         assert target in ("v", "d") + SOURCED, \
             "target is 'v' (velocity), 's' (stream function), 'p' (potential), 'sp' (both) or 'd' (density)"
         self.loss = loss
@@ -865,7 +932,9 @@ class GridStylizer(object):
         self.target = target
         self.lr = float(lr)
         self.pg = process_group
-        self.adam = make_optimizer(optimizer)        # (named after the reference's optimiser; L-BFGS on request)
+        self.adam = make_optimizer(optimizer, lap_n=lap_n)   # (named after the reference's optimiser; L-BFGS / 'lapnorm' on request)
+        if isinstance(self.adam, LapDescentState):
+            self.adam.nd = 3
         # the advect adjoint consumed inside the Adam kernel: only when the optimiser IS Adam
         self.fuse_adam = os.environ.get("NFS_FUSE_ADAM", "1") != "0" and isinstance(self.adam, TFAdamState)
         assert int(adv_order) in (1, 2), "adv_order is 1 (semi-Lagrangian) or 2 (MacCormack)"
@@ -1036,6 +1105,8 @@ class GridStylizer(object):
         if adam is not None:
             self.adam = adam
             self.fuse_adam = self.fuse_adam and isinstance(adam, TFAdamState)
+            if isinstance(adam, LapDescentState):
+                adam.nd = 3
 
     def _apply_binding(self):
         if self._pending is None:
@@ -1058,7 +1129,7 @@ class GridStylizer(object):
     def _adv_target(self):
         """the buffer the fused Adam kernel ('v') or the launch after the update ('s', 'p', 'sp') writes the next forward sample into
         (None: fusion off / not applicable)"""
-        if not (self.fuse_advect and (self._fused_step_ok() or self._source_stored())):
+        if not (self.fuse_advect and (self._fused_step_ok() or self._source_stored() or self._fused_descent_ok())):
             return None
         sl = self.slab
         shape = tuple(self.d0.shape) if sl is None else (sl.hi - sl.lo,) + tuple(self.d0.shape[1:])
@@ -1073,6 +1144,14 @@ class GridStylizer(object):
         updates the variable through ``TFAdamState.step``, which writes no next forward sample."""
         D, H, W = self.d0.shape
         return self.target == "v" and self.fuse_adam and min(D, H, W) >= 2 and (D * H * W) % 4 == 0
+
+    def _fused_descent_ok(self):
+        """optimizer 'lapnorm', velocity variable, order 1: may step() take ``LapDescentState.step_through_advect``, whose
+        kernel writes the next forward sample and its live mask?  On the shapes ``_fused_step_ok`` names, so that the stored
+        sample and the mask are handled exactly as the fused Adam step's"""
+        D, H, W = self.d0.shape
+        return (self.target == "v" and self.adv_order == 1 and isinstance(self.adam, LapDescentState)
+                and min(D, H, W) >= 2 and (D * H * W) % 4 == 0)
 
     def _source_stored(self):
         """stream-function, potential or Helmholtz variable, order 1, on the shapes the fused advect takes: the forward sample
@@ -1284,7 +1363,23 @@ class GridStylizer(object):
             parallel.all_reduce_sum_([self._gbuf], group=self.pg)
         if total is None:
             total = self._loss_slot[0] if (loss_view and self.pg is None) else self._loss_slot[0].clone()
-        if self._fused_step_ok():
+        if isinstance(self.adam, LapDescentState):
+            # Laplacian-normalised descent: the normalisation is non-local, so the gradient of the variable is formed
+            # first (from the all-reduced g_ds: every rank computes the identical update); the velocity variable at order
+            # 1 then takes the fused kernel, which leaves the next forward sample and its mask as the fused Adam step does
+            g = self.variable_gradient(g_ds)
+            adv = self._adv_target() if self._fused_descent_ok() else None
+            if adv is not None:
+                live = self._live_target()
+                self.adam.step_through_advect(self.var, self.d0, g, self.lr, adv_next=adv, live_next=live)
+                self._adv_mark(live=live is not None)
+            else:
+                self.adam.step(self.var, g, self.lr, nd=3)
+                if self._adv_target() is not None:
+                    self._advect_now()    # (a sourced variable's next forward sample and its mask, into the fixed buffers)
+                else:
+                    self._adv_src = None
+        elif self._fused_step_ok():
             g_adv = ops.smooth3d_relu_bwd(self.d_s, g_ds, self.k)
             adv = self._adv_target()
             live = self._live_target()

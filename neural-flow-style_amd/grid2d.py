@@ -8,7 +8,9 @@ Per step, for a density d0 [H,W] (float32) and a variable of one of the kinds of
     img = clip(d^, 0, 1) as [1,H,W,1]        the reference's "value clipping for rendering" (styler_2p.py:88)
     ``engine.ImageStyleLoss`` on img         x255, grey -> 3 channels, - mean, optional ``resize_scale``; the loss network; style,
                                              TV, content, histogram, ``style_mask`` with d_gray = img
-    TF ApplyAdam on the variable             one expression, the project's (``engine.TFAdamState``)
+    TF ApplyAdam on the variable             one expression, the project's (``engine.TFAdamState``); or, with
+                                             ``optimizer='lapnorm'``, Laplacian-normalised descent
+                                             (``engine.LapDescentState``: ``lr`` a length in the variable's units)
 
 A 2-D density is its own image: there is no smoothing, no render and no max-normalisation, and ``k`` is not read.
 Velocities are [H,W,2] in ``ops.advect2d_fwd``'s units: component k moves along array axis k, one cell along an axis of n
@@ -18,10 +20,13 @@ Not built in 2-D (say so here, where a user looks): dead-region masks and never-
 MacCormack transport between frames, ``batch_size > 1``."""
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import ops
-from .engine import SOURCED, Replay, Stamp, TFAdamState, graph_from_env, holds, loss_capture_key, make_optimizer
+from .engine import (SOURCED, LapDescentState, Replay, Stamp, TFAdamState, graph_from_env, holds, loss_capture_key,
+                     make_optimizer)
 
 
 class GridStylizer2D(object):
@@ -30,10 +35,13 @@ class GridStylizer2D(object):
     's', 'p', 'sp' (``ops.advect2d_source_fwd`` / ``_bwd``); 'v' takes the fused update (``ops.advect2d_bwd_adam``, which
     also writes the next step's forward sample), the others ``ops.source2d_velocity_bwd`` + ``ops.adam_tf_step``; order 2
     the unfused one throughout (the velocity materialised, ``ops.advect_maccormack`` / ``_bwd``).
+    ``optimizer='lapnorm'`` (``lap_n`` pyramid levels): all five targets and both orders through ``variable_gradient`` ->
+    ``LapDescentState.step`` over the variable as [H,W,C]; 'v' at order 1 takes the fused kernel
+    (``ops.advect2d_descent``: update + next forward sample; ``NFS_FUSE_ADVECT=0`` turns it off).
     ``graph``: replay the loss chain as a captured hipGraph (``engine.Replay``); None: as ``NFS_GRAPH`` says, eager when
     it is unset."""
 
-    def __init__(self, loss, d0, target="v", lr=0.1, optimizer="adam", adv_order=1, graph=None):
+    def __init__(self, loss, d0, target="v", lr=0.1, optimizer="adam", adv_order=1, graph=None, lap_n=3):
         assert target in ("v", "d") + SOURCED, \
             "target is 'v' (velocity), 's' (stream function), 'p' (potential), 'sp' (both) or 'd' (density)"
         if optimizer == "lbfgs":
@@ -44,7 +52,10 @@ class GridStylizer2D(object):
         self.d0 = d0.contiguous()
         self.target = target
         self.lr = float(lr)
-        self.adam = make_optimizer(optimizer)
+        self.adam = make_optimizer(optimizer, lap_n=lap_n)
+        if isinstance(self.adam, LapDescentState):
+            self.adam.nd = 2
+        self.fuse_advect = os.environ.get("NFS_FUSE_ADVECT", "1") != "0"     # (read by the 'lapnorm' step only)
         self.adv_order = int(adv_order)
         self.use_graph = bool(graph_from_env() if graph is None else graph)
         self._replay = None                          # (None: before the eager call that precedes a capture)
@@ -68,9 +79,11 @@ class GridStylizer2D(object):
         assert tuple(d0.shape) == tuple(self.d0.shape)
         self._pending = (d0, var)
         if adam is not None:
-            if not isinstance(adam, TFAdamState):
-                raise ValueError("the 2-D grid stylizer steps with TF ApplyAdam only (L-BFGS is not built)")
+            if not isinstance(adam, (TFAdamState, LapDescentState)):
+                raise ValueError("the 2-D grid stylizer steps with TF ApplyAdam or 'lapnorm' (L-BFGS is not built)")
             self.adam = adam
+            if isinstance(adam, LapDescentState):
+                adam.nd = 2
 
     def _apply_binding(self):
         if self._pending is None:
@@ -181,7 +194,14 @@ class GridStylizer2D(object):
         """one iteration: loss, gradient, the update; returns the loss (a 0-d device tensor of its own)"""
         loss, g_adv = self._loss_gradient()
         total = loss.sum()
-        if self.target != "d" and self.adv_order == 1:
+        if isinstance(self.adam, LapDescentState):
+            g = self.variable_gradient(g_adv).reshape(self.var.shape)
+            if self.target == "v" and self.adv_order == 1 and self.fuse_advect:
+                self.adam.step_through_advect2d(self.var, self.d0, g, self.lr, self._adv_buf)
+                self._adv_src = Stamp(self.var, self.d0)
+            else:
+                self.adam.step(self.var, g, self.lr, nd=2)
+        elif self.target != "d" and self.adv_order == 1:
             _, hyper = self.adam._begin_step(self.var, self.lr)
             if self.target == "v":
                 ops.advect2d_bwd_adam(self.d0, self.var, g_adv, self.adam.m, self.adam.v, *hyper, adv_next=self._adv_buf)

@@ -608,6 +608,35 @@ def transport_step2d(g, u, scale=1.0, w_g=1.0, addend=None, w_addend=0.0, out=No
     return out
 
 
+# ---- descent along a normalised gradient (include/nfs_descent.h, libnfs_descent.so; engine.LapDescentState) --------------
+
+def descent_step(x, g, lr):
+    """x <- fma(-lr, g, x) in place, one rounding per element (any shape; g shaped like x)"""
+    assert x.numel() == g.numel()
+    _lib.call("nfs_descent_step", _ptr(x), _ptr(g), x.numel(), float(lr), _stream())
+    _written(x)
+
+
+def advect_descent(d, vel, g, lr, adv_next, live_next=None):
+    """the velocity variable's step fused with the next forward sample: vel [D,H,W,3] <- fma(-lr, g, vel) (the bits of
+    ``descent_step``), ``adv_next`` [D,H,W] = advect(d, new vel) and ``live_next`` (optional, ``live_mask``) its live mask
+    (the bits of ``advect_fwd`` on the new velocity); d [D,H,W] or [D,H,W,1]"""
+    D, H, W = d.shape[:3]
+    assert d.numel() == D * H * W and tuple(vel.shape) == (D, H, W, 3) and g.numel() == vel.numel()
+    assert adv_next.is_contiguous() and adv_next.numel() == D * H * W
+    _lib.call("nfs_advect_descent_fwd", _ptr(d), _ptr(vel), _ptr(g), float(lr), _ptr(adv_next), _ptr(live_next), D, H, W,
+              _stream())
+    _written(vel, adv_next, live_next)
+
+
+def advect2d_descent(d, vel, g, lr, adv_next):
+    """the 2-D twin: vel [H,W,2] <- fma(-lr, g, vel), ``adv_next`` [H,W] = advect2d(d [H,W], new vel)"""
+    H, W = d.shape
+    assert tuple(vel.shape) == (H, W, 2) and g.numel() == vel.numel() and adv_next.numel() == H * W
+    _lib.call("nfs_advect2d_descent_fwd", _ptr(d), _ptr(vel), _ptr(g), float(lr), _ptr(adv_next), H, W, _stream())
+    _written(vel, adv_next)
+
+
 # ---- A9 -----------------------------------------------------------------------------
 
 def smooth3d_relu_fwd(d, k, out=None):

@@ -19,12 +19,14 @@ from . import engine
 from . import ops
 from . import transform as T
 from . import vgg as vggmod
+from .config import check_optimizer
 from .styler_base import StylerBase
 from .util import denoise
 
 
 class Styler(StylerBase):
     def __init__(self, self_dict):
+        check_optimizer(self_dict, grid=False)
         StylerBase.__init__(self, self_dict)
         self.batch_size = max(int(self.batch_size), 1)
         if self.batch_size > 1 and getattr(self, "w_hist", 0):

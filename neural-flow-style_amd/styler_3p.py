@@ -28,6 +28,7 @@ import torch
 
 from . import engine, ops, parallel
 from . import transform as T
+from .config import check_optimizer
 from .styler_base import StylerBase
 from .util import temporal_weights
 
@@ -52,6 +53,7 @@ class _SmoothRelu(torch.autograd.Function):
 
 class Styler(StylerBase):
     def __init__(self, self_dict):
+        check_optimizer(self_dict, grid=False)
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (see module docstring)"
         if self.rotate:

@@ -40,6 +40,11 @@ is the same displacement at every octave (factor 1).  A potential or stream func
 the flow it stands for; on an anisotropic grid the three ratios differ slightly and that warm start is approximate.
 Every octave starts with fresh optimiser state (Adam moments, L-BFGS pairs: their shapes belong to the old grid) and a
 fresh ``engine.GridStylizer``.
+
+Optimisers: TF-Adam (the reference's), L-BFGS (3-D), and ``optimizer='lapnorm'``: Laplacian-normalised descent, the
+update rule of a transport-based stylizer built from the reference's unused ``lap_normalize`` (``engine.LapDescentState``).
+The learning rate of every optimiser follows the reference's unused ``cosine_decay`` within an octave (``lr_decay``,
+default 1: constant).  Nothing is carried across octaves.
 """
 from __future__ import annotations
 
@@ -48,8 +53,9 @@ import torch
 
 from . import engine, grid2d, ops, parallel
 from . import transform as T
+from .config import check_optimizer
 from .styler_base import StylerBase
-from .util import temporal_weights
+from .util import cosine_decay, temporal_weights
 
 
 class Styler(StylerBase):
@@ -74,11 +80,17 @@ class Styler(StylerBase):
     frame loop, sharding, temporal weights, ``interp``, ``frames_per_opt``, the 'd' mask and the octaves are the code
     below unchanged (``ops.transport_step2d`` crosses frames, ``ops.resize3d`` resamples the depth-1 volume); the result
     holds ``'d'`` float32 [F,H,W,1] (the clipped image), ``'r'`` uint8 [F,H,W,3], ``'v'`` [H,W,2], ``'s'`` / ``'phi'``
-    [H,W].  Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
+    [H,W].  ``config.optimizer`` = 'lapnorm' (2-D and 3-D, with ``config.lap_n`` pyramid levels): Laplacian-normalised
+    descent (``engine.LapDescentState``) in place of Adam, everything else -- octaves, frame sharding, ``frames_per_opt``,
+    ``interp``, the 'd' mask, the temporal alignment -- unchanged; ``lr`` is then a length in the variable's units (for 'v',
+    lr = c * 2/(n-1) is about c cells per pyramid level and step, at every octave alike).  ``config.lr_decay`` (every
+    optimiser): iteration i of an octave runs at ``util.cosine_decay(i, iter, lr[o], lr_decay)``.
+    Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
     sharding, a MacCormack transport between frames, ``batch_size > 1``, a root-level driver (the reference has none for
     grids)."""
 
     def __init__(self, self_dict):
+        check_optimizer(self_dict, grid=True)
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (styler_3p module docstring)"
         self.target = getattr(self, "grid_variable", "") or "v"
@@ -96,7 +108,8 @@ class Styler(StylerBase):
             raise ValueError("rotate=True with a 2-D resolution %s: a 2-D density is its own image, there are no views"
                              % (list(self.resolution),))
         if self.is2d and getattr(self, "optimizer", "adam") == "lbfgs":
-            raise ValueError("optimizer='lbfgs' is not built for the 2-D grid path: use 'adam'")
+            raise ValueError("optimizer='lbfgs' is not built for the 2-D grid path: use 'adam' or 'lapnorm'")
+        self.lap_n, self.lr_decay = int(getattr(self, "lap_n", 3)), float(getattr(self, "lr_decay", 1))
         self.octave_sizes = octave_sizes(self.resolution, self.octave_n, self.octave_scale)
         if self.octave_n > 1 and min(self.octave_sizes[0]) < 2:
             raise ValueError("octave_n=%d at octave_scale=%g takes resolution %s down to %s: every octave needs at least "
@@ -307,10 +320,12 @@ class Styler(StylerBase):
                                                   torch.zeros(size, device=self.device))
         if self.is2d:
             st.gs = grid2d.GridStylizer2D(self.loss, first, target=self.target, lr=st.lr,
-                                          optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
+                                          optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order,
+                                          lap_n=self.lap_n)
         else:
             st.gs = engine.GridStylizer(self.loss, first, k=self.k, target=self.target, lr=st.lr,
-                                        optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order)
+                                        optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order,
+                                        lap_n=self.lap_n)
         st.opt_ = {}
         st.hist_octave.append([])
 
@@ -402,12 +417,15 @@ class Styler(StylerBase):
         st = self._st
         losses = torch.zeros(len(st.keys), device=self.device)
         upd = {}
+        # the reference's cosine schedule over the octave's iterations (util.py:49-53): lr_decay * lr at the first one, down
+        # to lr; at the default factor 1 it returns lr * 1.0, the very number (every optimiser of the grid path)
+        st.gs.lr = float(cosine_decay(len(st.hist_octave[-1]), max(int(self.iter), 1), st.lr, self.lr_decay))
         for j, t in enumerate(st.keys):
             if st.owner[t] == st.rank:
                 slot = engine.optimizer_slot(getattr(self, "optimizer", "adam"), t, self.frames_per_opt)
                 adam = st.opt_.get(slot)
                 if adam is None:
-                    adam = st.opt_[slot] = engine.make_optimizer(getattr(self, "optimizer", "adam"))
+                    adam = st.opt_[slot] = engine.make_optimizer(getattr(self, "optimizer", "adam"), lap_n=self.lap_n)
                 st.work.copy_(st.g_opt[t])
                 if self.is2d:
                     st.gs.bind(st.d[t], st.work.view(st.shape[:2] if self.target == "d" else self._var_shape()), adam)
