@@ -310,7 +310,9 @@ int nfs_helmholtz_bwd_adam(const float* g_vel, float* a, float* m, float* v, int
 
 /* ---- Laplacian-pyramid gradient normalisation (util.py:57-110) -------------------------------------
  * nfs_lap_down: out [ceil(D/2),ceil(H/2),ceil(W/2),C] = conv(x [D,H,W,C], k, stride 2, 'SAME') (tf.nn.conv3d / conv2d of
- *   lap_split, 60-66); k = k5x5x5 [5][5][5] (nd = 3) or k5x5 [5][5] (nd = 2, D = 1), the same for every channel.
+ *   lap_split, 60-66); k = k5x5x5 [5][5][5] (nd = 3) or k5x5 [5][5] (nd = 2, D = 1), the same for every channel.  k is
+ *   applied as a correlation, out[o] = sum_{a,b,e} k[a][b][e] x[2 o + (a,b,e) - pad] (pad = 1 for an even axis, 2 for an
+ *   odd one, x zero outside the volume), and nfs_lap_up is its exact transpose.
  * nfs_lap_up: out [D,H,W,C] = scale * conv_transpose(lo, k, output shape [D,H,W], stride 2) + addend (nullable):
  *   lo2 of lap_split (scale 5 in 3-D, 4 in 2-D, hi = img - lo2 via scale < 0) and the merge step (80-83).
  * nfs_normalize_mean: out = x / max(m, eps), m = sqrt(mean(x^2)) (normalize_std, 86-90) or mean|x| (use_abs: the
@@ -324,7 +326,9 @@ int nfs_lap_up(const float* lo, const float* k, float scale, const float* addend
  *   addend_part (nullable) [addend_nparts] + addend_n + eps: the addend enters as addend / max(sqrt(sum / addend_n), eps),
  *   the sum formed by every block from the partial sums in a fixed order (deterministic).
  * nfs_lap_up_rms_parts: the number of partial sums (blocks) for an output volume, 0 where only nfs_lap_up applies
- *   (2-D, other channel counts, volumes under 2^21 cells). */
+ *   (2-D, channel counts other than 1 and 3, volumes under 4096 voxels, rows too wide for the row form: it is taken from
+ *   4096 voxels on while its 12 staged coarse rows, 48 ceil(W/2) C bytes, fit 60 KB of LDS; with NFS_LAP_UP=cell the cell
+ *   form is taken instead, from 2^21 voxels on). */
 int nfs_lap_up_rms_parts(int D, int H, int W, int C, int nd);
 int nfs_lap_up_rms(const float* lo, const float* k, float scale, const float* addend, const float* addend_part,
                    int addend_nparts, int64_t addend_n, float eps, float* out, float* out_part, int D, int H, int W, int C,

@@ -212,7 +212,7 @@ def lap_normalize(img, scale_n=3, is_3d=False, c=1):
         _LAP_K[key] = torch.as_tensor(lap_kernel(is_3d)).to(img.device).contiguous()
     k = _LAP_K[key]
     s = 5.0 if is_3d else 4.0
-    # A level of the 200^3 x 3 pyramid is 96 MB: where the cell kernel applies, the sum of squares of a high-pass level is
+    # A level of the 200^3 x 3 pyramid is 96 MB: where the row kernel applies, the sum of squares of a high-pass level is
     # formed by the kernel that writes it and its 1 / RMS is applied by the merge kernel that reads it (no normalisation
     # pass of its own: two reads and a write of the level less)
     fuse = os.environ.get("NFS_LAP_FUSE", "1") != "0"

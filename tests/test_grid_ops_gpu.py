@@ -277,8 +277,8 @@ def test_laplacian_pyramid_normalisation_matches_the_oracle():
             got = util.lap_normalize(torch.tensor(g).cuda(), scale_n=scale_n, is_3d=is_3d, c=shape[-1]).cpu().numpy()
             assert got.shape == g.shape
             assert rel(got, want) < 2e-5, (shape, scale_n)
-    # volumes of >= 2^21 cells: the RMS normalisation of the high-pass levels rides in the kernels that write and merge
-    # them (nfs_lap_up_rms) -- against the three-pass form of the same library and against the oracle
+    # large volumes (the row form is taken from 4096 voxels on): the RMS normalisation of the high-pass levels rides in the
+    # kernels that write and merge them (nfs_lap_up_rms) -- against the three-pass form of the same library and the oracle
     import os
     import neural_flow_style_amd.ops as ops
     for shape in ((130, 128, 129, 3), (128, 132, 128, 1)):
