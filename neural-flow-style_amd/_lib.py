@@ -126,13 +126,25 @@ except OSError as e:
     raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (DESCENT_HEADER_PATH, e))
 DESCENT_ABI_VERSION = _c3["NFS_DESCENT_ABI_VERSION"]
 
+# libnfs_colour.so (colour rendering through the views: target_field 'c' of the 3-D particle stylizer): the fourth
+COLOUR_LIB_PATH = os.path.join(_HERE, "libnfs_colour.so")
+COLOUR_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_colour.h"))
+try:
+    with open(COLOUR_HEADER_PATH) as _f:
+        COLOUR_SIGNATURES, COLOUR_RESTYPES, _, _c4 = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (COLOUR_HEADER_PATH, e))
+COLOUR_ABI_VERSION = _c4["NFS_COLOUR_ABI_VERSION"]
+
 _lib = None
 _lib2d = None
 _libdescent = None
+_libcolour = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so and libnfs_descent.so (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so and libnfs_colour.so
+    (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -220,6 +232,15 @@ def libdescent():
     return _libdescent
 
 
+def libcolour():
+    """libnfs_colour.so, loaded the same way"""
+    global _libcolour
+    if _libcolour is None:
+        _libcolour = _load_beside(COLOUR_LIB_PATH, COLOUR_SIGNATURES, COLOUR_RESTYPES, "nfs_colour_version",
+                                  COLOUR_ABI_VERSION)
+    return _libcolour
+
+
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
 # two events recorded on the SAME stream the kernel is enqueued on; entries are
 # name -> [(start_event, end_event, args)].  Costs two event records per call, so it is off by
@@ -234,6 +255,8 @@ def call(name, *args):
         L, L0 = lib2d(), L
     elif name in DESCENT_SIGNATURES:
         L, L0 = libdescent(), L
+    elif name in COLOUR_SIGNATURES:
+        L, L0 = libcolour(), L
     else:
         L0 = L
     if PROFILE is not None:

@@ -181,6 +181,19 @@ __device__ __forceinline__ float lin_coord(int i, int n) {
   return -1.f + step * (float)i;
 }
 
+// exp(-tau a) = exp2(exp2_rate(tau) a): the ray marches (render.hip, colour.hip) run on the hardware exp2
+__device__ __forceinline__ float exp2_rate(float tau) { return -tau * 1.44269504088896341f; }
+
+// normalised coordinate of the sample (zi, h, w) of a view with row-major rotation r[9] (transform.py:611-628): the
+// output lattice point rotated, axes in array order (shared by render.hip's fused marches and colour.hip)
+__device__ __forceinline__ void ray_coords(const float* r, int D, int H, int W, int zi, int h, int w, float& cx,
+                                           float& cy, float& cz) {
+  const float gx = lin_coord(zi, D), gy = lin_coord(h, H), gz = lin_coord(w, W);
+  cx = r[0] * gx + r[1] * gy + r[2] * gz;
+  cy = r[3] * gx + r[4] * gy + r[5] * gz;
+  cz = r[6] * gx + r[7] * gy + r[8] * gz;
+}
+
 // float4 accesses need it (a contiguous tensor view may start anywhere in its storage)
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -11,8 +11,7 @@
 namespace nfs {
 
 // ---- small shared pieces -------------------------------------------------------------
-// exp(-tau a) = exp2(exp2_rate(tau) a): the marches run on the hardware exp2
-__device__ __forceinline__ float exp2_rate(float tau) { return -tau * 1.44269504088896341f; }
+// (exp(-tau a) = exp2(exp2_rate(tau) a), the marches run on the hardware exp2: exp2_rate is common.h's)
 
 // ray gid of a [V][H][W] image -> view v, pixel px of the view and (with W) row h and column w.  Statements that declare
 // their results, not functions: behind a call the compiler orders the index arithmetic of every kernel differently.
@@ -231,14 +230,6 @@ struct RayGeom {
   float bx, by, bz;  // coordinate of the sample at z-index 0 contribution of (h,w)
   float sx, sy, sz;  // first column of R
 };
-
-__device__ __forceinline__ void ray_coords(const float* r, int D, int H, int W, int zi, int h, int w, float& cx,
-                                           float& cy, float& cz) {
-  const float gx = lin_coord(zi, D), gy = lin_coord(h, H), gz = lin_coord(w, W);
-  cx = r[0] * gx + r[1] * gy + r[2] * gz;
-  cy = r[3] * gx + r[4] * gy + r[5] * gz;
-  cz = r[6] * gx + r[7] * gy + r[8] * gz;
-}
 
 __device__ __forceinline__ float tri_sample1(const float* __restrict__ vol, const Tri& t) {
   float s = 0.f;

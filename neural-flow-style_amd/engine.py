@@ -1503,3 +1503,61 @@ class ImageStyleLoss(object):
             loss = loss + tv / B
         g_d = ops.loss_net_input_bwd(g_x, H, W, Cin)
         return loss, g_d
+
+
+# --------------------------------------------------------------------------------------
+# 3-D colour path: a colour volume seen through the views of a grey density (include/nfs_colour.h)
+# --------------------------------------------------------------------------------------
+
+class ColourRenderLoss(object):
+    """The loss of a colour volume q [D,H,W,3] rendered through V views whose absorption is a grey density d [D,H,W]
+    (target_field 'c' of the 3-D particle stylizer), around an ``ImageStyleLoss``:
+
+        w = T / M (ops.ray_weights), J = sum_z w rotate(q) (ops.colour_project_fwd), img = clip(J, 0, 1) -> image loss
+
+    d does not depend on the variable, so everything of it -- the weights, the grey image and the style mask
+    d_gray = clip(I / M, 0, 1) -- is formed once per frame and view set (``prepare``); a step is the projection, the
+    image loss and the projection's transpose.  The maximum M is taken per ``v_batch`` views (nfs_maxnorm_fwd's groups)
+    and the image loss sees the views v_batch at a time, as one loss-net batch of the reference graph does: the total
+    over V views is the sum of the view batches' losses whichever ``views_mode`` presents them.  Eager launches only."""
+
+    def __init__(self, image_loss, transmit, v_batch=1):
+        self.image_loss = image_loss
+        self.tau = float(transmit)
+        self.v_batch = max(int(v_batch or 1), 1)
+
+    def prepare(self, d3, rot):
+        """d3 [D,H,W], rot [V,3,3] -> the frame's context: ray weights w [V,D,H,W], the grey image, d_gray [V,H,W,1]"""
+        V = int(rot.shape[0])
+        w = torch.empty((V,) + tuple(d3.shape), dtype=torch.float32, device=d3.device)
+        grey, _ = ops.rotate_render_fwd(d3, rot, self.tau, False, d_rot=w)
+        norm, gmax = ops.maxnorm_fwd(grey, max(V // self.v_batch, 1))
+        ops.ray_weights(w, self.tau, gmax, out=w)                # in place: the samples are not needed again
+        d_gray = torch.clamp(norm, 0, 1).unsqueeze(-1).contiguous()
+        return {"rot": rot, "w": w, "grey": grey, "gmax": gmax, "d_gray": d_gray}
+
+    def _batches(self, V):
+        vb = self.v_batch if (V > self.v_batch and V % self.v_batch == 0) else V
+        return [(lo, lo + vb) for lo in range(0, V, vb)]
+
+    def project(self, q, ctx):
+        """(J [V,H,W,C] before the clip, clip(J, 0, 1))"""
+        J = ops.colour_project_fwd(q, ctx["rot"], ctx["w"])
+        return J, torch.clamp(J, 0, 1)
+
+    def loss_and_grad(self, q, ctx):
+        """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3])"""
+        J, img = self.project(q, ctx)
+        V = J.shape[0]
+        losses, grads = [], []
+        for lo, hi in self._batches(V):
+            l, g = self.image_loss.loss_and_grad(img[lo:hi].contiguous(), ctx["d_gray"][lo:hi].contiguous())
+            losses.append(l); grads.append(g)
+        g_img = grads[0] if len(grads) == 1 else torch.cat(grads, 0)
+        g_J = ops.clamp01_bwd(g_img.contiguous(), J)
+        g_q = ops.colour_project_bwd(g_J, ctx["rot"], ctx["w"])
+        return (losses[0] if len(losses) == 1 else torch.cat(losses, 0)), g_q
+
+    def d_img(self, q, ctx):
+        """the 0..255 image the loss network sees, [V,H',W',3] (float32: uint8-ready)"""
+        return self.image_loss.d_img(self.project(q, ctx)[1])

@@ -813,6 +813,97 @@ def maxnorm_input_bwd(img, gmax, g_x):
     return g_img
 
 
+# ---- colour rendering through the views (include/nfs_colour.h) -------------------------------------------------------
+
+def ray_weights(d_rot, tau, gmax, out=None):
+    """d_rot [V,D,H,W] (rotate_render_fwd(d_rot=...)), gmax [G] (maxnorm_fwd of the grey image) ->
+    w [V,D,H,W] = exp(-tau sum_{z' >= z} d_rot) / gmax[view's group]; ``out`` may be d_rot itself (in place)"""
+    V, D, H, W = d_rot.shape
+    if out is None:
+        out = _empty(d_rot.shape, d_rot)
+    _lib.call("nfs_ray_weights", _ptr(d_rot), float(tau), _ptr(gmax), int(gmax.numel()), _ptr(out), V, D, H, W, _stream())
+    _written(out)
+    return out
+
+
+def colour_project_fwd(q, rot, w, out=None):
+    """q [D,H,W,C] (C in 1..4), rot [V,3,3], w [V,D,H,W] -> img [V,H,W,C] = sum_z w rotate(q)[z] (no rotated volume)"""
+    D, H, W, Cn = q.shape
+    V = rot.shape[0]
+    assert tuple(w.shape) == (V, D, H, W), (tuple(w.shape), (V, D, H, W))
+    if out is None:
+        out = _empty((V, H, W, Cn), q)
+    _lib.call("nfs_colour_project_fwd", _ptr(q), _ptr(rot), _ptr(w), _ptr(out), V, D, H, W, Cn, _stream())
+    return out
+
+
+COLOUR_BWD_ROUTES = ("atomic", "tiled", "coef")
+
+
+COLOUR_ATOMIC_UPTO = 1 << 19           # samples V D H W up to which the scatter kernel is the default
+COLOUR_COEF_FROM = 1 << 23             # samples from which the coefficient form is (where the shape has a layout)
+
+
+def colour_bwd_route(V, D, H, W):
+    """the route colour_project_bwd takes when none is named, as measured at C = 3 (tools/colour_bench.py,
+    profiles/colour_ab.txt, first / second run).  The scatter kernel runs at the float atomics' rate
+    (25.6 ms against 1.2 ms at 200^3 x 8 views), so it is the default only where the transpose is bound by its launches:
+    it wins up to 16 x 64 x 64 x 8 = 2^19 samples (177.5 / 177.5 against 239.7 / 241.8 us), no longer at 16 x 64 x 96 x 8
+    (260.0 / 264.0 against 255.3 / 254.6 us) and loses from 2^20 (344 against 266 us).  Above, the output-stationary
+    adjoint per channel: through the materialised product (nfs_rotate_bwd), or, from 64 x 128 x 128 x 8 = 2^23 samples
+    and where the shape has a coefficient layout (D >= 16), nfs_rotate_bwd_coef, which wins there and at every larger
+    size measured (307 against 339 us; 1.21 against 1.44 ms at 6.4e7) and loses by 10 us at 32 x 100 x 100 x 8 = 2.6e6
+    and below.  Between 2^19 and 7.9e5 and between 2.6e6 and 2^23 samples nothing was measured."""
+    n = V * D * H * W
+    if n <= COLOUR_ATOMIC_UPTO:
+        return "atomic"
+    return "coef" if (n >= COLOUR_COEF_FROM and render_coef_layout(V, D, H, W) is not None) else "tiled"
+
+
+def colour_project_bwd(g_img, rot, w, g_q=None, route=None):
+    """the transpose of colour_project_fwd: g_img [V,H,W,C] -> g_q [D,H,W,C] (written when None is passed, else +=).
+    route: 'atomic'  nfs_colour_project_bwd (any shape; not bit-reproducible);
+           'tiled'   per channel, the product g w materialised and nfs_rotate_bwd's output-stationary form (any shape);
+           'coef'    per channel, nfs_rotate_bwd_coef with u = w, A = g_img[..., c], B = 0 (shapes with a coefficient
+                     layout: D >= 16); both compositions are bit-reproducible and end in an interleave of the planes"""
+    V, H, W, Cn = g_img.shape
+    D = w.shape[1]
+    assert tuple(w.shape) == (V, D, H, W), (tuple(w.shape), (V, D, H, W))
+    route = route or colour_bwd_route(V, D, H, W)
+    if route == "atomic":
+        overwrite = g_q is None
+        if overwrite:
+            g_q = _empty((D, H, W, Cn), g_img)
+        _lib.call("nfs_colour_project_bwd", _ptr(g_img), _ptr(rot), _ptr(w), _ptr(g_q), int(overwrite), V, D, H, W, Cn,
+                  _stream())
+        _written(g_q)
+        return g_q
+    if route == "coef":
+        layout = render_coef_layout(V, D, H, W)
+        if layout is None:
+            raise ValueError("colour_project_bwd(route='coef'): no coefficient layout for %s (D >= 16 needed)"
+                             % ((V, D, H, W),))
+        wmax = w.amax()
+    elif route != "tiled":
+        raise ValueError("colour_project_bwd: route %r is none of %s" % (route, COLOUR_BWD_ROUTES))
+    planes = []
+    for c in range(Cn):
+        gc = g_img[..., c]
+        if route == "tiled":
+            planes.append(rotate_bwd((w * gc.unsqueeze(1)).unsqueeze(-1), rot, tiled=True).squeeze(-1))
+        else:
+            ab = _zeros((V, layout[0], H, W, 2), g_img)
+            ab[..., 0] = gc.unsqueeze(1)
+            # >= every |sample gradient| = |g| w (and positive: the fixed-point scale is derived from it)
+            bounds = (gc.abs().amax() * wmax).clamp_min(1e-30).reshape(1).contiguous()
+            planes.append(rotate_bwd_coef(w, ab, rot, bounds))
+    out = torch.stack(planes, -1)
+    if g_q is None:
+        return out
+    g_q += out
+    return g_q
+
+
 # ---- A5 -----------------------------------------------------------------------------
 
 def loss_net_input_fwd(img, H2=None, W2=None, want_d_img=True, want_x=True):

@@ -7,6 +7,10 @@ final inference), driving the HIP kernels instead of a TF-1.15 graph.
 Forward graph per frame (styler_3p.py:42-164):
   'd': r + clip(r_opt,-1,1) -> sum_k p2g_wavg(p, r_k, support / kernel_scale^k)
   'p': p + v              -> p2g(p) / rest_density        (+ pressure loss, 96-98)
+  'c': the grey field of 'p' at zero displacement absorbs, q = p2g(p, pc=clip(c,0,1), pd=r) [D,H,W,3] emits
+       (transform.py:1429-1441, the colour branch of the 3-D splat that no reference driver calls); the colour image
+       of a view is clip(sum_z T/M rotate(q), 0, 1) -> x255 -> loss network: ``engine.ColourRenderLoss`` (build
+       extension; conventions of styler_2p)
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -28,6 +32,7 @@ import torch
 
 from . import engine, ops, parallel
 from . import transform as T
+from . import vgg as vggmod
 from .config import check_optimizer
 from .styler_base import StylerBase
 from .util import temporal_weights
@@ -52,10 +57,30 @@ class _SmoothRelu(torch.autograd.Function):
 
 
 class Styler(StylerBase):
+    _colour = False                                  # target_field 'c' (set by the constructor)
+
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
+        if getattr(self_dict, "target_field", "") == "c":
+            # the colour path renders by emission-absorption only and has no auxiliary field terms (refused before the
+            # base class loads a network)
+            if getattr(self_dict, "render_liquid", False):
+                raise ValueError("target_field 'c': render_liquid is not built for the colour render (pass "
+                                 "--render_liquid false)")
+            if getattr(self_dict, "ray_mode", ""):
+                raise ValueError("target_field 'c': ray_mode %r is not built for the colour render (leave --ray_mode empty)"
+                                 % (self_dict.ray_mode,))
+            if (getattr(self_dict, "w_pressure", 0) or 0) > 0:
+                raise ValueError("target_field 'c': w_pressure acts on moved positions and the colours move none (pass "
+                                 "--w_pressure 0)")
+            if (getattr(self_dict, "w_density", 0) or 0) > 0:
+                raise ValueError("target_field 'c': w_density acts on the density variable (pass --w_density 0)")
+            if getattr(self_dict, "style_mask_on_ref", False):
+                raise ValueError("target_field 'c': style_mask_on_ref is not built for the colour render (pass "
+                                 "--style_mask_on_ref false)")
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (see module docstring)"
+        self._colour = self.target_field == "c"
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -64,7 +89,9 @@ class Styler(StylerBase):
                 self.n_views = len(self.views)
             print("# vps:", self.n_views)
             assert self.n_views % self.v_batch == 0
-        self.loss = self._make_loss(rotate=self.rotate)
+        # one loss chain per stylizer: the grey render's, or for 'c' the colour render's around an image loss
+        self.loss = None if self._colour else self._make_loss(rotate=self.rotate)
+        self.colour = self._make_colour_loss() if self._colour else None
         self._graph_loss = None                      # engine.GraphedLoss, decided at the first loss call
         self._identity = T.rot_to_device([np.identity(3)], self.device)
         # multi-GPU (set by the driver): ``pg`` = the process group; ``shard_by`` = 'views' (views=sum: the views of every
@@ -73,6 +100,80 @@ class Styler(StylerBase):
         # exchange is the halo of per-frame updates the temporal filter reaches, point-to-point)
         self.pg = None
         self.shard_by = getattr(self, "shard_by", None) or "views"
+
+    def _make_colour_loss(self):
+        w_layers = list(self.w_style_layer)
+        if len(w_layers) == 1 and len(self.style_layer) > 1:
+            w_layers = w_layers * len(self.style_layer)
+        image_loss = engine.ImageStyleLoss(self.net, self.style_layer, w_layers, self.w_style, w_tv=self.w_tv,
+                                           resize_scale=self.resize_scale, style_mask=getattr(self, "style_mask", False),
+                                           w_content=getattr(self, "w_content", 0),
+                                           content_layer=getattr(self, "content_layer", None),
+                                           content_channel=getattr(self, "content_channel", 0),
+                                           w_content_amp=getattr(self, "w_content_amp", 100),
+                                           w_hist=getattr(self, "w_hist", 0), hist_layer=getattr(self, "hist_layer", ()),
+                                           w_hist_layer=getattr(self, "w_hist_layer", ()))
+        return engine.ColourRenderLoss(image_loss, self.transmit, self.v_batch if self.rotate else 1)
+
+    # ---- the colour path (target_field 'c'): what a step does not change is formed once -------------------------
+    _COLOUR_CTX_FLOATS = 1 << 30          # ray weights kept across steps (4 GiB); beyond it a context is formed per call
+
+    def _colour_frame(self, p, r, res):
+        """the frame's constants for this octave: its grid order, positions and densities in that order, the splat
+        configuration and the grey volume d [D,H,W] (the 'p' path at zero displacement)"""
+        frames = self.__dict__.setdefault("_cframes", {})
+        key = (p.data_ptr(), p.shape[0], tuple(res))
+        if key not in frames:
+            order = self.__dict__.get("_orders", {}).get((p.data_ptr(), p.shape[0]))
+            with torch.no_grad():
+                _, d_out, _ = self._field(p, None, None, res)
+            pp, rr = (p, r) if order is None else (p[order].contiguous(), r[order].contiguous())
+            cfg = ops.make_splat_cfg(3, list(res), list(self.domain), self.radius, self.support, self.rest_density,
+                                     self.nsize, self.clip, 1)
+            frames[key] = {"order": order, "p": pp, "r": rr.reshape(-1).contiguous(), "cfg": cfg,
+                           "d3": d_out.detach().reshape(d_out.shape[1:4]).contiguous(), "ctx": {}}
+        return frames[key]
+
+    def _colour_ctx(self, fr, rot):
+        """ray weights, grey image and mask of a frame for one view set: kept until the views are re-sampled (the set is
+        identified by its matrices' device buffer: ``_rot`` caches them per slice of the current view list)"""
+        key = (rot.data_ptr(), int(rot.shape[0]))
+        ctx = fr["ctx"].get(key)
+        if ctx is None:
+            ctx = self.colour.prepare(fr["d3"], rot)
+            held = self.__dict__.get("_cctx_floats", 0) + ctx["w"].numel()
+            if held <= self._COLOUR_CTX_FLOATS:
+                ctx["held"] = rot                    # (keeps the key's address alive as long as the entry)
+                fr["ctx"][key] = ctx
+                self._cctx_floats = held
+        return ctx
+
+    def _colour_volume(self, fr, var):
+        cc = ops.colour_clamp_gather(var.contiguous(), fr["order"])
+        return cc, ops.p2g_fwd(fr["p"], fr["cfg"], attr=cc, pd=fr["r"])
+
+    def _colour_value_and_grad(self, p, r, var, res, rot):
+        """per-view losses and d loss / d c of one frame: clamp -> splat -> ColourRenderLoss -> splat adjoint -> clamp
+        adjoint, on the C-ABI operators (as styler_2p's explicit chain)"""
+        fr = self._colour_frame(p, r, res)
+        ctx = self._colour_ctx(fr, rot)
+        cc, q = self._colour_volume(fr, var)
+        losses, g_q = self.colour.loss_and_grad(q, ctx)
+        _, g_cc, _ = ops.p2g_bwd(fr["p"], fr["cfg"], g_q, attr=cc, pd=fr["r"], need_p=False, need_attr=True)
+        return losses, ops.colour_clamp_scatter_bwd(g_cc, var.contiguous(), fr["order"])
+
+    def _colour_d_img(self, p, r, var, res):
+        """the colour image at the identity view, [1,H',W',3] 0..255"""
+        fr = self._colour_frame(p, r, res)
+        return self.colour.d_img(self._colour_volume(fr, var)[1], self._colour_ctx(fr, self._identity))
+
+    def _colour_reset(self, views_only=False):
+        for fr in self.__dict__.get("_cframes", {}).values():
+            fr["ctx"] = {}
+        self._cctx_floats = 0
+        self._rot_cache = {}
+        if not views_only:
+            self._cframes = {}
 
     # ---- forward graph: variable -> d_out [1,D,H,W,1] (autograd) ---------------------------------
     def _field(self, p, r, var, res):
@@ -84,7 +185,7 @@ class Styler(StylerBase):
         p_ = p.unsqueeze(0)
         if "p" in self.target_field:
             p_ = p_ + var.unsqueeze(0)
-        p_all = p_
+        p_all = p_                                   # ('c': the positions as they came; var is not read)
         # a sequence keeps ONE particle order for all frames (frame 0's: the temporal filter needs particle i to be the
         # same particle everywhere), so by frame 60 of a flowing liquid the neighbours of that order have dispersed and
         # the splat would fall back to scattered global atomics; it therefore sees every frame through that frame's
@@ -147,6 +248,8 @@ class Styler(StylerBase):
     def _value_and_grad(self, p, r, var, res, rot, view_shard=True):
         """loss (per view, device) and d loss / d var for one frame.  ``view_shard``: the views are sharded over the
         ranks of ``self.pg`` (then only rank 0 adds the view-independent terms)"""
+        if self._colour:
+            return self._colour_value_and_grad(p, r, var, res, rot if (self.rotate and rot is not None) else self._identity)
         v = var.detach().clone().requires_grad_(True)
         _, d_out, extra = self._field(p, r, v, res)
         d3 = d_out.detach().reshape(d_out.shape[1:4]).contiguous()
@@ -176,10 +279,18 @@ class Styler(StylerBase):
         return losses, v.grad
 
     def _rot(self, lo, hi):
+        if self._colour:
+            # one device buffer per slice of the current view list: the colour contexts are keyed on it
+            cache = self.__dict__.setdefault("_rot_cache", {})
+            if (lo, hi) not in cache:
+                cache[(lo, hi)] = T.rot_to_device(self.rot_mat_[lo:hi], self.device)
+            return cache[(lo, hi)]
         return T.rot_to_device(self.rot_mat_[lo:hi], self.device)
 
     def _resample_views(self):
         if "uniform" not in self.sample_type:
+            if self._colour:
+                self._colour_reset(views_only=True)       # new views: new ray weights
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
                                                   nv=self.n_views)
@@ -193,6 +304,14 @@ class Styler(StylerBase):
         for t in range(self.num_frames):
             p = self._dev(params["p"][t])
             n = p.shape[0]
+            if self._colour:
+                # mid-grey particles at rest density through the colour render (as styler_2p.render_test)
+                r = torch.full((n, 1), float(self.rest_density), device=self.device)
+                with torch.no_grad():
+                    dimg = self._colour_d_img(p, r, torch.full((n, 3), 0.5, device=self.device), list(self.resolution))
+                imgs.append(dimg[0].cpu().numpy().astype(np.uint8))
+                self._colour_reset()
+                continue
             r = self._dev(params["r"][t]) if "d" in self.target_field else None
             var = torch.zeros(n, 3 if "p" in self.target_field else self.num_kernels, device=self.device)
             with torch.no_grad():
@@ -203,6 +322,9 @@ class Styler(StylerBase):
 
     # ---- the optimisation loop (styler_3p.py:229-439) ----------------------------------------------
     def run(self, params):
+        if self._colour and self.pg is not None:
+            raise ValueError("target_field 'c' over a process group: sharding the colour path over ranks is not built "
+                             "(run it on one GPU)")
         if abs(self.lr_scale - 1) > 1e-7 and not isinstance(self.lr, list):
             self.lr = [self.lr / self.lr_scale ** i for i in range(self.octave_n)]
 
@@ -216,6 +338,22 @@ class Styler(StylerBase):
 
         p = [self._dev(x) for x in params["p"]]
         r = [self._dev(x) for x in params["r"]] if "d" in self.target_field else [None] * self.num_frames
+        c_init = None
+        if self._colour:
+            # per-particle densities [N,1] (the first kernel's column; rest_density where the frames carry none) and the
+            # colour start: noise around the VGG mean / 255 (styler_2p.py:189-192) unless the caller brings one
+            if params.get("r") is not None:
+                r = [self._dev(np.asarray(x, np.float32).reshape(len(x), -1)[:, :1]) for x in params["r"]]
+            else:
+                r = [torch.full((x.shape[0], 1), float(self.rest_density), device=self.device) for x in p]
+            if params.get("c_init") is not None:
+                c_init = np.asarray([np.asarray(x, np.float32) for x in params["c_init"]], np.float32)
+            else:
+                assert len(set(int(x.shape[0]) for x in p)) == 1, "the drawn colour start needs the same particles in every frame (or pass params['c_init'])"
+                c_init = self.rng.uniform(-5, 5, [self.num_frames, p[0].shape[0], 3]).astype(np.float32)
+                c_init += np.array([vggmod._R_MEAN, vggmod._G_MEAN, vggmod._B_MEAN], np.float32)
+                c_init /= 255
+            self._colour_reset()
         # Particles in grid-cell order (one permutation for all frames, from the first frame's positions: the temporal
         # filter and the frame interpolation need particle i to be the same particle in every frame).  A block of
         # consecutive particles then touches a small box of cells and the splat accumulates it in LDS
@@ -233,8 +371,12 @@ class Styler(StylerBase):
             for x in p[1:]:                                  # (frame 0 is in its own order already)
                 if x.shape[0] > 1:
                     self._orders[(x.data_ptr(), x.shape[0])] = T.grid_order(x, self.resolution)
-        nvar = 3 if "p" in self.target_field else self.num_kernels
+        nvar = 3 if ("p" in self.target_field or self._colour) else self.num_kernels
         g_opt = [torch.zeros(p[i].shape[0], nvar, device=self.device) for i in range(self.num_frames)]
+        if self._colour:
+            g_opt = [self._dev(c_init[i]) for i in range(self.num_frames)]
+            if inv is not None:
+                g_opt = [g[perm].contiguous() for g in g_opt]
         mode = getattr(self, "views_mode", "sequential")
         if getattr(self, "optimizer", "adam") == "lbfgs" and self.rotate and mode == "sequential" \
                 and self.n_views > self.v_batch:
@@ -283,12 +425,15 @@ class Styler(StylerBase):
         for octave in range(self.octave_n):
             loss_history_o, d_intm_o = [], []
             res = [int(v) for v in oct_size[octave]]
+            loss_net = self.colour.image_loss if self._colour else self.loss       # (who holds the image targets)
             if self.style_img is not None:
-                self.loss.set_style_image(self._style_feature(self.style_img, res[1:]))
+                loss_net.set_style_image(self._style_feature(self.style_img, res[1:]))
                 if getattr(self, "w_hist", 0) > 0:                # styler_3p.py:288-293
-                    self.loss.set_hist_image(self._hist_feature(self.style_img, res[1:]))
+                    loss_net.set_hist_image(self._hist_feature(self.style_img, res[1:]))
             if self.content_img is not None:                     # styler_3p.py:277-279
-                self.loss.set_content_image(self._content_feature(self.content_img, res[1:]), top_k=self._content_top_k())
+                loss_net.set_content_image(self._content_feature(self.content_img, res[1:]), top_k=self._content_top_k())
+            if self._colour:
+                self._colour_reset()                             # the frames' grey volumes and ray weights are per octave
             lr = self.lr[octave] if isinstance(self.lr, list) else self.lr
 
             for step in range(self.iter):
@@ -345,8 +490,11 @@ class Styler(StylerBase):
 
                     if step == self.iter - 1 and octave < self.octave_n - 1 and not by_frames:
                         with torch.no_grad():
-                            _, d_out, _ = self._field(p[t], r[t], var, res)
-                            dimg = self.loss_d_img(d_out)
+                            if self._colour:
+                                dimg = self._colour_d_img(p[t], r[t], var, res)
+                            else:
+                                _, d_out, _ = self._field(p[t], r[t], var, res)
+                                dimg = self.loss_d_img(d_out)
                         d_intm_o.append(dimg.cpu().numpy().astype(np.uint8))
 
                 if by_frames:
@@ -391,7 +539,7 @@ class Styler(StylerBase):
         for t in range(self.num_frames):
             with torch.no_grad():
                 p_out, d_out, _ = self._field(p[t], r[t], g_opt[t], res)
-                dimg = self.loss_d_img(d_out)
+                dimg = self._colour_d_img(p[t], r[t], g_opt[t], res) if self._colour else self.loss_d_img(d_out)
             p_sty.append((p_out if inv is None else p_out[inv]).cpu().numpy())
             if "p" in self.target_field:
                 v_sty.append((g_opt[t] if inv is None else g_opt[t][inv]).cpu().numpy())
@@ -403,6 +551,12 @@ class Styler(StylerBase):
         result["d"] = np.array(d_sty)
         result["r"] = np.array(r_sty)
         result["opt"] = [(g if inv is None else g[inv]).cpu().numpy() for g in g_opt]   # build extension: the variables
+        if self._colour:
+            # the colours as styler_2p returns them: clipped, and faded by the particle's density (styler_2p.py:297-300)
+            result["c"] = [((torch.clamp(g_opt[t], 0, 1) * torch.clamp(r[t] / self.rest_density, 0, 1))
+                            [slice(None) if inv is None else inv]).cpu().numpy() for t in range(self.num_frames)]
+            result["c_init"] = c_init
+            self._colour_reset()
         self._orders, self._order_age = {}, {}   # keyed by device address: the frame tensors die with this call
         return result
 

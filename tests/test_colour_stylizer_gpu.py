@@ -1,0 +1,285 @@
+"""target_field 'c' of the 3-D particle stylizer: the gradient of one frame's loss in the colours against the float64
+reference (tests/colour_ref.py), ``Styler(config).run`` against the float64 loop, the result's surface, octaves, the
+refusals, and the other targets' bits against arrays recorded on the commit before this one."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import nfs_oracle as O
+from tests import colour_ref as CR
+from tests import colour_runs as RUNS
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RES = [17, 12, 12]
+LAYERS = ["conv1_1", "conv2_1"]
+N = 400
+
+
+def rel(a, b):
+    a = torch.as_tensor(np.asarray(a)).double(); b = torch.as_tensor(np.asarray(b)).double()
+    return float((a - b).norm() / (b.norm() + 1e-300))
+
+
+@pytest.fixture(scope="module")
+def scene():
+    """seeded particles (float32 values), a style image at the render's size, the float64 loss network and its style
+    features: computed once and left alone"""
+    from neural_flow_style_amd import synthetic as S
+    rng = np.random.RandomState(31)
+    F = 2
+    p = [rng.uniform(0.1, 0.9, (N, 3)).astype(np.float32) for _ in range(F)]
+    r = [(rng.uniform(0.8, 1.2, (N, 1)) * 1000).astype(np.float32) for _ in range(F)]
+    c_init = rng.uniform(-0.15, 1.15, (F, N, 3)).astype(np.float32)          # some colours outside [0,1]
+    simg = S.style_image(RES[1], RES[2], rng)
+    w64 = {k: (np.asarray(a, np.float64), np.asarray(b, np.float64))
+           for k, (a, b) in O.synthetic_vgg19_weights(123, upto="conv2_1").items()}
+    sfe = O.style_target_features(torch.tensor(np.asarray(simg, np.float64))[None], w64, LAYERS, upto="conv2_1")
+    return dict(p=p, r=r, c_init=c_init, simg=simg, w64=w64, sfe=sfe, F=F)
+
+
+def _styler(scene, F=1, **over):
+    from neural_flow_style_amd.styler_3p import Styler
+    cfg = RUNS.base_config(RES, "c", F=F, style_target=scene["simg"], **over)
+    st = Styler(cfg)
+    st.load_img(RES[1:])
+    return st, cfg
+
+
+def _ref_cfg(cfg):
+    return dict(vars(cfg))
+
+
+def _ref_loss_grad(scene, cfg, t, c, R):
+    """float64: (loss, d loss / d c) of frame t through the view batch R"""
+    c64 = torch.tensor(np.asarray(c, np.float64), requires_grad=True)
+    l = CR.frame_loss(torch.tensor(scene["p"][t]).double(), torch.tensor(scene["r"][t]).double(), c64, _ref_cfg(cfg), RES,
+                      torch.tensor(np.asarray(R, np.float32)).double(), scene["w64"], scene["sfe"])
+    (g,) = torch.autograd.grad(l, c64)
+    return float(l.detach()), g
+
+
+@pytest.mark.parametrize("mode,v_batch,style_mask,w_tv", [("sequential", 1, True, 0.0), ("sum", 1, False, 0.05),
+                                                          ("sum", 3, True, 0.05), ("sequential", 1, False, 0.05)])
+def test_gradient_of_one_frame(scene, mode, v_batch, style_mask, w_tv):
+    """d loss / d c against the float64 reference: relative L2 <= 1e-3 (BASELINE's gradient bar), per view batch in the
+    sequential mode and for the summed views; colours outside [0,1] get exactly zero"""
+    st, cfg = _styler(scene, views_mode=mode, v_batch=v_batch, style_mask=style_mask, w_tv=w_tv)
+    st.colour.image_loss.set_style_image(st._style_feature(st.style_img, RES[1:]))
+    dev = st.device
+    p, r = st._dev(scene["p"][0]), st._dev(scene["r"][0])
+    c = scene["c_init"][0]
+    var = st._dev(c)
+    outside = torch.tensor((c < 0) | (c > 1))
+    assert bool(outside.any())
+    nv = len(st.rot_mat_)
+    assert nv == 3
+    batches = [(i, i + v_batch) for i in range(0, nv, v_batch)] if mode == "sequential" else [(0, nv)]
+    for lo, hi in batches:
+        losses, g = st._value_and_grad(p, r, var, RES, st._rot(lo, hi), view_shard=False)
+        assert tuple(losses.shape) == (hi - lo,) and tuple(g.shape) == (N, 3) and g.device == dev
+        # the reference takes the views one loss-net batch (v_batch views, one maximum) at a time
+        l_ref, g_ref = 0.0, 0.0
+        for b in range(lo, hi, v_batch):
+            l_b, g_b = _ref_loss_grad(scene, cfg, 0, c, st.rot_mat_[b:b + v_batch])
+            l_ref, g_ref = l_ref + l_b, g_ref + g_b
+        rg, rl = rel(g.cpu(), g_ref), abs(float(losses.sum()) - l_ref) / abs(l_ref)
+        print("colour gradient %s v_batch %d mask %s tv %g views %d:%d  rel-L2 %.3g  loss rel %.3g"
+              % (mode, v_batch, style_mask, w_tv, lo, hi, rg, rl))
+        assert float(g_ref.abs().max()) > 0
+        assert rg <= 1e-3, rg
+        assert rl <= 1e-3, rl
+        assert float(g.cpu()[outside].abs().max()) == 0.0
+
+
+def _ref_run(scene, cfg, rot_mats, steps):
+    """the float64 loop on the same c_init: styler_3p's sequential iteration (one TF-Adam step per view batch, iterates
+    averaged), the temporal filter over the frames' updates"""
+    F = scene["F"]
+    g_opt = [torch.tensor(scene["c_init"][t]).double() for t in range(F)]
+    opt = [O.TFAdam() for _ in range(F)]
+    Wt = O.temporal_filter_matrix(F, cfg.window_sigma)
+    hist = []
+    for _ in range(steps):
+        upd = []
+        for t in range(F):
+            var, acc, ls = g_opt[t].clone(), 0.0, []
+            for i in range(len(rot_mats)):
+                l, g = _ref_loss_grad(scene, cfg, t, var, rot_mats[i:i + 1])
+                var = opt[t].step(var, g, cfg.lr)
+                ls.append(l)
+                acc = acc + torch.nan_to_num(var)
+            hist.append(float(np.mean(ls)))
+            upd.append(acc / len(rot_mats) - g_opt[t])
+        for t in range(F):
+            g_opt[t] = g_opt[t] + sum(float(Wt[t, s]) * upd[s] for s in range(F))
+    return hist, g_opt
+
+
+def test_run_against_the_float64_loop(scene):
+    """3 Adam steps, 2 frames, window_sigma > 0: per-step losses within 1e-3 of the float64 loop on the same c_init;
+    the result's keys, shapes and dtypes; 'r' is a re-render of 'opt' through ops; 'c' lies in [0,1]"""
+    from neural_flow_style_amd import ops
+    from neural_flow_style_amd import transform as T
+    F = scene["F"]
+    st, cfg = _styler(scene, F=F, iter=3, window_sigma=1.0, lr=0.01, style_mask=True, w_tv=0.01)
+    params = {"p": scene["p"], "r": scene["r"], "c_init": scene["c_init"]}
+    res = st.run(params)
+    hist, g_ref = _ref_run(scene, cfg, st.rot_mat_, 3)
+    got = np.asarray(res["l"][0])
+    print("colour run losses", got, "reference", np.asarray(hist), "rel", np.abs(got - hist) / np.abs(hist))
+    assert got.shape == (3 * F,)
+    np.testing.assert_allclose(got, hist, rtol=1e-3)
+    for t in range(F):
+        assert rel(res["opt"][t], g_ref[t]) <= 1e-3
+    # the surface
+    assert set(res) >= {"l", "d_intm", "v", "c", "p", "d", "r", "opt", "c_init"}
+    assert res["v"] is None and res["d_intm"] == []
+    assert res["r"].shape == (F, RES[1], RES[2], 3) and res["r"].dtype == np.uint8
+    assert res["d"].shape == (F,) + tuple(RES) + (1,) and res["d"].dtype == np.float32
+    assert np.array_equal(np.asarray(res["c_init"]), scene["c_init"])
+    for t in range(F):
+        assert res["opt"][t].shape == (N, 3) and res["opt"][t].dtype == np.float32
+        assert res["c"][t].shape == (N, 3) and res["c"][t].min() >= 0.0 and res["c"][t].max() <= 1.0
+        fade = np.clip(scene["r"][t] / 1000.0, 0, 1)
+        np.testing.assert_allclose(res["c"][t], np.clip(res["opt"][t], 0, 1) * fade, rtol=1e-6)
+        assert np.array_equal(res["p"][t], scene["p"][t])                 # the positions as they came
+    assert res["r"].max() > 0 and len(np.unique(res["r"])) > 8
+    # 'r': the identity view of 'opt', rendered again through ops in the caller's particle order
+    dev = st.device
+    eye = T.rot_to_device([np.identity(3)], dev)
+    cfg3 = ops.make_splat_cfg(3, RES, list(cfg.domain), cfg.radius, cfg.support, cfg.rest_density, cfg.nsize, cfg.clip, 1)
+    cfg0 = ops.make_splat_cfg(3, RES, list(cfg.domain), cfg.radius, cfg.support, 1.0, cfg.nsize, cfg.clip, 0)
+    for t in range(F):
+        p, r = st._dev(scene["p"][t]), st._dev(scene["r"][t]).reshape(-1)
+        d3 = ops.smooth3d_relu_fwd(ops.p2g_fwd(p, cfg0)[..., 0].contiguous(), float(cfg.k))
+        np.testing.assert_allclose(res["d"][t][..., 0], d3.cpu().numpy(), rtol=1e-4, atol=1e-6)
+        w = torch.empty((1,) + tuple(RES), device=dev)
+        grey, _ = ops.rotate_render_fwd(d3, eye, cfg.transmit, False, d_rot=w)
+        _, gmax = ops.maxnorm_fwd(grey, 1)
+        ops.ray_weights(w, cfg.transmit, gmax, out=w)
+        q = ops.p2g_fwd(p, cfg3, attr=ops.colour_clamp_gather(st._dev(res["opt"][t])), pd=r)
+        img = (torch.clamp(ops.colour_project_fwd(q, eye, w), 0, 1) * 255)[0].cpu().numpy().astype(np.float64)
+        got = res["r"][t].astype(np.float64)
+        # 'r' is the truncation of the run's own float image, which differs from this one by the order of the splat's
+        # float atomics only (the run sorts its particles): got <= image < got + 1 up to that rounding.  A pixel is a
+        # sum of 17 weighted 8-corner samples of a volume whose cells collect some 30 particles: about 64 roundings
+        # of magnitudes that stay below 2 before the clip, on the 0..255 scale
+        tol = 64 * 2.0 ** -24 * 2 * 255
+        low, high = float((img - got).min()), float((img - got).max())
+        print("'r' of frame %d against the float re-render: image - r in [%.6f, %.6f], tolerance %.2g" % (t, low, high, tol))
+        assert low >= -tol and high < 1 + tol, (low, high)
+        # ... and no bias of a level: re-truncated, a pixel differs only where the image sits on a level's edge
+        flips = img.astype(np.uint8) != res["r"][t]
+        edge = np.minimum(img - np.floor(img), np.ceil(img) - img)
+        assert not flips.any() or float(edge[flips].max()) <= tol, (int(flips.sum()), float(edge[flips].max()))
+
+
+def test_two_octaves(scene):
+    st, cfg = _styler(scene, F=1, iter=2, octave_n=2, octave_scale=1.5, lr=0.01, views_mode="sum")
+    res = st.run({"p": scene["p"][:1], "r": scene["r"][:1], "c_init": scene["c_init"][:1]})
+    assert len(res["l"]) == 2 and len(res["l"][0]) == 2 and len(res["l"][1]) == 2
+    assert all(np.isfinite(l).all() for l in res["l"])
+    lo = [int(v // 1.5) for v in RES]
+    assert len(res["d_intm"]) == 1 and res["d_intm"][0].shape == (1, lo[1], lo[2], 3)      # in colour
+    assert res["d_intm"][0].dtype == np.uint8
+    assert res["r"].shape == (1, RES[1], RES[2], 3)
+    assert not np.array_equal(res["opt"][0], scene["c_init"][0])
+
+
+def test_default_start_and_missing_densities(scene):
+    """without c_init the start is the seeded noise around the VGG mean / 255 (styler_2p.py:189-192); without 'r' the
+    particles splat at rest density"""
+    st, cfg = _styler(scene, F=1, iter=1)
+    res = st.run({"p": scene["p"][:1]})
+    ci = np.asarray(res["c_init"])
+    assert ci.shape == (1, N, 3)
+    mean = np.array(O.VGG_MEAN) / 255
+    assert np.all(np.abs(ci - mean) <= 5.0 / 255 + 1e-6)
+    np.testing.assert_allclose(res["c"][0], np.clip(res["opt"][0], 0, 1), rtol=1e-6)     # rest density: no fade
+
+
+@pytest.mark.parametrize("flag,over", [("render_liquid", dict(render_liquid=True)), ("ray_mode", dict(ray_mode="max")),
+                                       ("w_pressure", dict(w_pressure=1.0)), ("w_density", dict(w_density=1.0)),
+                                       ("style_mask_on_ref", dict(style_mask_on_ref=True))])
+def test_constructor_refusals(scene, flag, over):
+    with pytest.raises(ValueError, match=flag):
+        _styler(scene, **over)
+
+
+def _run(scene, monkeypatch=None, keep=None, F=2, **over):
+    """a short run; ``keep``: the stylizer's budget of kept ray weights (0: every context is formed per call)"""
+    from neural_flow_style_amd.styler_3p import Styler
+    if keep is not None:
+        monkeypatch.setattr(Styler, "_COLOUR_CTX_FLOATS", keep)
+    st, cfg = _styler(scene, F=F, **over)
+    prepared = []
+    inner = st.colour.prepare
+    st.colour.prepare = lambda d3, rot: (prepared.append(rot.cpu().numpy().copy()), inner(d3, rot))[1]
+    res = st.run({"p": scene["p"][:F], "r": scene["r"][:F], "c_init": scene["c_init"][:F]})
+    return st, res, prepared
+
+
+def _same_run(a, b):
+    """two runs of the same trajectory: equal up to the order of the float atomics (the splat's, the scatter transpose's)"""
+    np.testing.assert_allclose(np.asarray(a["l"]), np.asarray(b["l"]), rtol=1e-5)
+    for x, y in zip(a["opt"], b["opt"]):
+        assert rel(x, y) <= 1e-5
+    assert np.abs(a["r"].astype(np.int32) - b["r"].astype(np.int32)).max() <= 1
+
+
+def test_kept_contexts_equal_contexts_formed_per_call(scene, monkeypatch):
+    """uniform views: the ray weights of a frame and view set are formed once per octave and kept; with no budget to keep
+    them they are formed at every call -- the same trajectory"""
+    kw = dict(iter=3, window_sigma=1.0, lr=0.01, style_mask=True, w_tv=0.01)
+    st, kept, n_kept = _run(scene, **kw)
+    _, percall, n_percall = _run(scene, monkeypatch, keep=0, **kw)
+    nv = len(st.rot_mat_)
+    # kept: one per frame and view batch, and the identity view of the final render; per call: every step's, again
+    assert len(n_kept) == 2 * nv + 2 and len(n_percall) == 3 * 2 * nv + 2
+    _same_run(kept, percall)
+
+
+def test_redrawn_views_get_new_contexts(scene, monkeypatch):
+    """Poisson-sampled views are redrawn after every frame step: the kept contexts are dropped with them.  Against the
+    same run with every context formed per call (a stale context would render the old views)"""
+    kw = dict(iter=3, window_sigma=1.0, lr=0.01, sample_type="poisson", n_views=2, phi0=-5, phi1=5, phi_unit=5,
+              theta0=-10, theta1=10, theta_unit=10, views_mode="sum", w_tv=0.01)
+    st, kept, p_kept = _run(scene, **kw)
+    _, percall, p_percall = _run(scene, monkeypatch, keep=0, **kw)
+    views = [m for m in p_kept if m.shape[0] == 2]
+    assert len(views) == 3 * 2 and len(set(m.tobytes() for m in views)) == len(views)      # every step saw its own views
+    assert len(p_kept) == len(p_percall) and all(np.array_equal(a, b) for a, b in zip(p_kept, p_percall))
+    _same_run(kept, percall)
+
+
+def test_interpolated_frames(scene):
+    """interp = 2 over three frames: frames 0 and 2 are stylised, frame 1 gets the blend of their colours"""
+    rng = np.random.RandomState(5)
+    sc = dict(scene, p=scene["p"] + [scene["p"][0]], r=scene["r"] + [scene["r"][0]],
+              c_init=np.concatenate([scene["c_init"], rng.uniform(0, 1, (1, N, 3)).astype(np.float32)]))
+    st, res, prepared = _run(sc, F=3, iter=2, interp=2, window_sigma=0, lr=0.01)
+    assert len(res["l"][0]) == 2 * 2 and res["r"].shape == (3, RES[1], RES[2], 3)
+    np.testing.assert_allclose(res["opt"][1], 0.5 * res["opt"][0] + 0.5 * res["opt"][2], rtol=1e-6, atol=1e-7)
+    assert not np.array_equal(res["opt"][0], sc["c_init"][0]) and not np.array_equal(res["opt"][2], sc["c_init"][2])
+
+
+def test_a_process_group_is_refused(scene):
+    st, _ = _styler(scene)
+    st.pg = object()
+    with pytest.raises(ValueError, match="process group"):
+        st.run({"p": scene["p"][:1], "r": scene["r"][:1]})
+
+
+@pytest.mark.parametrize("target", ["p", "d"])
+def test_other_targets_keep_their_bits(target):
+    """a 'p' and a 'd' run against tests/golden/colour_unchanged_targets.npz, recorded on an MI355X from the commit before
+    target_field 'c' (tests/golden/make_colour_unchanged_fixture.py)"""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "colour_unchanged_targets.npz"))
+    got = RUNS.unchanged_target_run(target)
+    for k, v in got.items():
+        assert np.array_equal(v, gold["%s_%s" % (target, k)]), (target, k, np.abs(v.astype(np.float64)
+                                                                 - gold["%s_%s" % (target, k)]).max())
