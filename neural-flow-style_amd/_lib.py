@@ -136,15 +136,26 @@ except OSError as e:
     raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (COLOUR_HEADER_PATH, e))
 COLOUR_ABI_VERSION = _c4["NFS_COLOUR_ABI_VERSION"]
 
+# libnfs_emission.so (the emission model of a colour grid: grid_variable 'c' of the grid-sequence stylizer): the fifth
+EMISSION_LIB_PATH = os.path.join(_HERE, "libnfs_emission.so")
+EMISSION_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_emission.h"))
+try:
+    with open(EMISSION_HEADER_PATH) as _f:
+        EMISSION_SIGNATURES, EMISSION_RESTYPES, _, _c5 = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (EMISSION_HEADER_PATH, e))
+EMISSION_ABI_VERSION = _c5["NFS_EMISSION_ABI_VERSION"]
+
 _lib = None
 _lib2d = None
 _libdescent = None
 _libcolour = None
+_libemission = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so and libnfs_colour.so
-    (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so, libnfs_colour.so and
+    libnfs_emission.so (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -241,6 +252,15 @@ def libcolour():
     return _libcolour
 
 
+def libemission():
+    """libnfs_emission.so, loaded the same way"""
+    global _libemission
+    if _libemission is None:
+        _libemission = _load_beside(EMISSION_LIB_PATH, EMISSION_SIGNATURES, EMISSION_RESTYPES, "nfs_emission_version",
+                                    EMISSION_ABI_VERSION)
+    return _libemission
+
+
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
 # two events recorded on the SAME stream the kernel is enqueued on; entries are
 # name -> [(start_event, end_event, args)].  Costs two event records per call, so it is off by
@@ -257,6 +277,8 @@ def call(name, *args):
         L, L0 = libdescent(), L
     elif name in COLOUR_SIGNATURES:
         L, L0 = libcolour(), L
+    elif name in EMISSION_SIGNATURES:
+        L, L0 = libemission(), L
     else:
         L0 = L
     if PROFILE is not None:

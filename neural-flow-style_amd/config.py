@@ -100,7 +100,7 @@ _FLAGS = [
     ("Misc", "gpu_id", dict(type=str, default="0")),
     # ---- build-specific -------------------------------------------------------------------
     ("MI355X", "views_mode", dict(type=str, default="sequential", choices=["sequential", "sum"])),
-    ("MI355X", "grid_variable", dict(type=str, default="", choices=["", "v", "d", "s", "p", "sp"])),
+    ("MI355X", "grid_variable", dict(type=str, default="", choices=["", "v", "d", "s", "p", "sp", "c"])),
     ("MI355X", "synthetic_weights", dict(type=str2bool, default=False)),
     ("MI355X", "transport_recursive", dict(type=str2bool, default=True)),
     ("MI355X", "ray_mode", dict(type=str, default="", choices=["", "transmit", "liquid", "max", "mean"])),

@@ -723,6 +723,12 @@ class TFAdamState(object):
         _, hyper = self._begin_step(x, lr)
         ops.source_bwd_adam(kind, g_vel, x, self.m, self.v, *hyper)
 
+    def step_through_emission(self, c, e, g_q, lr):
+        """the same update for the colours ``c`` [D,H,W,C] of an emission q = clamp01(c) e (``ops.emission_fwd``) given
+        dL/dq: g_c = ``ops.emission_bwd(g_q, c, e)`` is formed and consumed inside one kernel"""
+        _, hyper = self._begin_step(c, lr)
+        ops.emission_bwd_adam(g_q, c, e, self.m, self.v, *hyper)
+
     def step_through_advect(self, vel, d0, g_adv, lr, adv_next=None, live_next=None, live_current=False):
         """the same update for the velocity variable of ``advect(d0, vel)`` given dL/d(advected density): the
         velocity gradient is formed and consumed inside one kernel (never written to HBM).  ``adv_next`` [D,H,W]
@@ -1545,8 +1551,8 @@ class ColourRenderLoss(object):
         J = ops.colour_project_fwd(q, ctx["rot"], ctx["w"])
         return J, torch.clamp(J, 0, 1)
 
-    def loss_and_grad(self, q, ctx):
-        """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3])"""
+    def loss_and_grad(self, q, ctx, route=None):
+        """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3]); ``route``: the transpose's (``ops.colour_project_bwd``; None: by size)"""
         J, img = self.project(q, ctx)
         V = J.shape[0]
         losses, grads = [], []
@@ -1555,9 +1561,112 @@ class ColourRenderLoss(object):
             losses.append(l); grads.append(g)
         g_img = grads[0] if len(grads) == 1 else torch.cat(grads, 0)
         g_J = ops.clamp01_bwd(g_img.contiguous(), J)
-        g_q = ops.colour_project_bwd(g_J, ctx["rot"], ctx["w"])
+        g_q = ops.colour_project_bwd(g_J, ctx["rot"], ctx["w"], route=route)
         return (losses[0] if len(losses) == 1 else torch.cat(losses, 0)), g_q
 
     def d_img(self, q, ctx):
         """the 0..255 image the loss network sees, [V,H',W',3] (float32: uint8-ready)"""
         return self.image_loss.d_img(self.project(q, ctx)[1])
+
+
+# --------------------------------------------------------------------------------------
+# 3-D colour grid: a colour field seen through the frame's own grey volume (include/nfs_emission.h)
+# --------------------------------------------------------------------------------------
+
+class ColourGridStylizer(object):
+    """One key frame of a 3-D grid sequence stylised in colour (``grid_variable 'c'`` of styler_grid), around a
+    ``ColourRenderLoss``.  For the bound input density d [D,H,W]:
+
+        e    = smooth3d_relu(d, k)          the grey volume the 'd' path renders at zero change: it absorbs AND emits, and
+                                            does not depend on the variable
+        ctx  = ColourRenderLoss.prepare(e, rot)      ray weights w = T / M, the grey image, d_gray = clip(I / M, 0, 1), one
+                                            maximum per ``v_batch`` views
+        q    = clamp01(c) * e               the emission (``ops.emission_fwd``), e broadcast over the channels; c [D,H,W,3]
+                                            is the variable ``var``
+        J    = sum_z w rotate(q),  img = clip(J, 0, 1)  ->  the image loss;  (losses [V], g_q) = loss_and_grad(q, ctx)
+        g_c  = g_q * e  where 0 <= c <= 1, else 0     (``ops.emission_bwd``: the clamp's convention is nfs_clamp01_bwd's, a
+                                            colour exactly 0 or 1 passes its gradient)
+
+    and one optimiser step on the summed view losses (``views = sum``, as every grid variable).  Where e == 0 the gradient
+    is an exact zero; e may carry the -0.0 with which nfs_smooth3d_relu_fwd marks the voxels its ReLU cut, which compares
+    equal to zero everywhere it is used.
+    The surface is the one styler_grid's frame loop uses on ``GridStylizer``: ``var``, ``lr``, ``bind(d0, var, adam)``,
+    ``step(rot)`` -> the summed loss (0-d device tensor), ``gradient(rot)`` -> (losses [V], g_c) without an update.
+    e and the context are formed anew whenever the bound density or the view tensor is not the one they were formed from
+    (``Stamp`` / ``holds``): a one-frame run with fixed views forms them once, redrawn views form the context every step.
+    Adam takes the fused update (``TFAdamState.step_through_emission``; ``NFS_FUSE_ADAM=0``: ``ops.emission_bwd`` then
+    ``step``), L-BFGS and 'lapnorm' (nd = 3) ``ops.emission_bwd`` then their own ``step``.  ``bwd_route``: the route of the
+    projection's transpose (``ops.colour_project_bwd``; None: by size); with 'tiled' a step is bit-reproducible.
+    Eager launches only.  Not built: hipGraph replay, dead-region masks, slab sharding, a view process group."""
+
+    def __init__(self, colour_loss, d0, k=3, lr=0.1, optimizer="adam", lap_n=3, bwd_route=None):
+        if bwd_route is not None and bwd_route not in ops.COLOUR_BWD_ROUTES:
+            raise ValueError("bwd_route %r is none of %s" % (bwd_route, ops.COLOUR_BWD_ROUTES))
+        self.loss = colour_loss
+        self.k = float(k)
+        self.lr = float(lr)
+        self.bwd_route = bwd_route
+        self.adam = make_optimizer(optimizer, lap_n=lap_n)
+        if isinstance(self.adam, LapDescentState):
+            self.adam.nd = 3
+        self.fuse_adam = os.environ.get("NFS_FUSE_ADAM", "1") != "0" and isinstance(self.adam, TFAdamState)
+        self.d0 = d0.contiguous()
+        D, H, W = d0.shape
+        self.var = torch.zeros(D, H, W, 3, dtype=torch.float32, device=d0.device)
+        self.e = self._e_of = None                  # smooth3d_relu(d0, k) and the stamp of the density it was formed from
+        self.ctx = self._ctx_of = None              # the frame's context and the stamp of (e, rot)
+        self.contexts_formed = 0
+
+    def bind(self, d0, var=None, adam=None):
+        """re-point the stylizer at another frame of the same shape: a pointer swap"""
+        assert tuple(d0.shape) == tuple(self.d0.shape)
+        self.d0 = d0.contiguous()
+        if var is not None:
+            assert tuple(var.shape) == tuple(self.var.shape), (tuple(var.shape), tuple(self.var.shape))
+            self.var = var
+        if adam is not None:
+            self.adam = adam
+            self.fuse_adam = self.fuse_adam and isinstance(adam, TFAdamState)
+            if isinstance(adam, LapDescentState):
+                adam.nd = 3
+
+    def grey(self):
+        """e = smooth3d_relu(d0, k) of the bound density (kept while that density stands unmodified)"""
+        if not holds(self._e_of, self.d0):
+            self.e = ops.smooth3d_relu_fwd(self.d0, self.k)
+            self._e_of = Stamp(self.d0)
+        return self.e
+
+    def context(self, rot):
+        e = self.grey()
+        if not holds(self._ctx_of, e, rot):
+            self.ctx = self.loss.prepare(e, rot)
+            self._ctx_of = Stamp(e, rot)
+            self.contexts_formed += 1
+        return self.ctx
+
+    def emission(self):
+        """q [D,H,W,3] of the current variable"""
+        return ops.emission_fwd(self.var, self.grey())
+
+    def _loss_gradient(self, rot):
+        ctx = self.context(rot)
+        return self.loss.loss_and_grad(self.emission(), ctx, route=self.bwd_route)
+
+    def gradient(self, rot):
+        """(losses [V], d sum(losses) / d c [D,H,W,3]) without an update"""
+        losses, g_q = self._loss_gradient(rot)
+        return losses, ops.emission_bwd(g_q.contiguous(), self.var, self.grey())
+
+    def step(self, rot):
+        losses, g_q = self._loss_gradient(rot)
+        g_q = g_q.contiguous()
+        if self.fuse_adam:
+            self.adam.step_through_emission(self.var, self.grey(), g_q, self.lr)
+        else:
+            self.adam.step(self.var, ops.emission_bwd(g_q, self.var, self.grey()), self.lr)
+        return losses.sum()
+
+    def d_img(self, rot):
+        """the 0..255 colour image of the current variable through ``rot``, [V,H',W',3]"""
+        return self.loss.d_img(self.emission(), self.context(rot))

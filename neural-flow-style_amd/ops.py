@@ -904,6 +904,46 @@ def colour_project_bwd(g_img, rot, w, g_q=None, route=None):
     return g_q
 
 
+# ---- the emission of a colour grid (include/nfs_emission.h) -----------------------------------------------------------
+
+def _emission_dims(c, e):
+    Cn = int(c.shape[-1])
+    if tuple(c.shape[:-1]) != tuple(e.shape):
+        raise ValueError("emission: the colours %s are not the grey volume %s with a channel axis"
+                         % (tuple(c.shape), tuple(e.shape)))
+    return int(e.numel()), Cn
+
+
+def emission_fwd(c, e, out=None):
+    """c [..., C] (C in 1..4), e [...] -> q = clamp01(c) * e, e broadcast over the channels"""
+    n, Cn = _emission_dims(c, e)
+    if out is None:
+        out = _empty(c.shape, c)
+    _lib.call("nfs_emission_fwd", _ptr(c), _ptr(e), _ptr(out), n, Cn, _stream())
+    _written(out)
+    return out
+
+
+def emission_bwd(g_q, c, e, out=None):
+    """the adjoint of emission_fwd in c: g_c = g_q * e where 0 <= c <= 1, else +0"""
+    n, Cn = _emission_dims(c, e)
+    assert g_q.shape == c.shape, (tuple(g_q.shape), tuple(c.shape))
+    if out is None:
+        out = _empty(c.shape, c)
+    _lib.call("nfs_emission_bwd", _ptr(g_q), _ptr(c), _ptr(e), _ptr(out), n, Cn, _stream())
+    _written(out)
+    return out
+
+
+def emission_bwd_adam(g_q, c, e, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
+    """emission_bwd consumed by TF ApplyAdam on (c, m, v) in place: bit-equal to emission_bwd + adam_tf_step"""
+    n, Cn = _emission_dims(c, e)
+    assert g_q.shape == c.shape == m.shape == v.shape
+    _lib.call("nfs_emission_bwd_adam", _ptr(g_q), _ptr(c), _ptr(e), _ptr(m), _ptr(v), n, Cn, float(lr_t), float(beta1),
+              float(beta2), float(eps), _stream())
+    _written(c, m, v)
+
+
 # ---- A5 -----------------------------------------------------------------------------
 
 def loss_net_input_fwd(img, H2=None, W2=None, want_d_img=True, want_x=True):

@@ -41,6 +41,19 @@ the flow it stands for; on an anisotropic grid the three ratios differ slightly 
 Every octave starts with fresh optimiser state (Adam moments, L-BFGS pairs: their shapes belong to the old grid) and a
 fresh ``engine.GridStylizer``.
 
+Colour (``grid_variable 'c'``, 3-D only; a build extension like the 2-D sequences: the reference has no such path).  The
+variable of key frame t is a colour field c_t [D,H,W,3] seen through the frame's own grey volume:
+        e_t = smooth3d_relu(d_t, k)         what the 'd' path renders at zero change: absorbs AND emits, constant in c_t
+        ctx_t = ColourRenderLoss.prepare(e_t, rot): ray weights w = T / M, the grey image, d_gray = clip(I / M, 0, 1),
+                                            one maximum per ``v_batch`` views
+        q = clamp01(c_t) * e_t  ->  J = sum_z w rotate(q), img = clip(J, 0, 1)  ->  ImageStyleLoss (style, TV, content,
+                                            histogram; ``style_mask`` masks by d_gray)
+        g_c = g_q * e_t where 0 <= c_t <= 1 (a colour exactly 0 or 1 passes its gradient), else 0
+        one optimiser step on the summed view losses;  upd_t = nan_to_num(new) - g_opt[t], NOT masked: where e_t == 0 the
+                                            gradient is an exact zero (e_t may carry -0.0, which compares equal to zero)
+(``engine.ColourGridStylizer``, kernels: include/nfs_emission.h).  Temporal alignment, ``frames_per_opt``, ``interp``,
+``lr_decay``, the octaves (a colour resamples with factor 1) and frame sharding are the loop below on a three-channel field.
+
 Optimisers: TF-Adam (the reference's), L-BFGS (3-D), and ``optimizer='lapnorm'``: Laplacian-normalised descent, the
 update rule of a transport-based stylizer built from the reference's unused ``lap_normalize`` (``engine.LapDescentState``).
 The learning rate of every optimiser follows the reference's unused ``cosine_decay`` within an octave (``lr_decay``,
@@ -85,16 +98,43 @@ class Styler(StylerBase):
     ``interp``, the 'd' mask, the temporal alignment -- unchanged; ``lr`` is then a length in the variable's units (for 'v',
     lr = c * 2/(n-1) is about c cells per pyramid level and step, at every octave alike).  ``config.lr_decay`` (every
     optimiser): iteration i of an octave runs at ``util.cosine_decay(i, iter, lr[o], lr_decay)``.
+    ``grid_variable`` = 'c' (3-D): a colour field [D,H,W,3] per key frame, emitted by the frame's smoothed density (module
+    docstring).  It starts from the resample of ``params['c_init'][t]`` [D,H,W,3] or, where that is missing, from ONE seeded
+    field shared by all frames, drawn once at full resolution from ``self.rng``: (uniform(-5, 5) + the VGG means) / 255 (a
+    sharded run passes ``c_init`` for every frame or for none, so that every rank draws alike).  The result holds ``'c'``:
+    clamp01(opt) * clip(e, 0, 1) per present frame (the masked colour, as styler_2p returns it), ``'opt'`` the raw
+    variables, ``'r'`` uint8 colour images [F,H,W,3], ``'d'`` = abs(e) [F,D,H,W,1], ``'d_intm'`` in colour, ``'c_init'``
+    what the run started from, ``'v'`` / ``'s'`` / ``'phi'`` / ``'p'`` None.  ``adv_order`` is accepted and has no effect
+    (as with 'd'); an attribute ``colour_bwd_route`` on the config names the route of the projection's transpose ('tiled':
+    bit-reproducible).  Refused with a ValueError naming the flag: a two-entry ``resolution``, ``render_liquid``, a
+    non-empty ``ray_mode``, ``style_mask_on_ref``, ``w_density`` > 0.  Eager launches only.
     Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
     sharding, a MacCormack transport between frames, ``batch_size > 1``, a root-level driver (the reference has none for
     grids)."""
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=True)
+        if getattr(self_dict, "grid_variable", "") == "c":
+            # the colour grid renders by emission-absorption through an image loss and has no auxiliary field terms
+            # (refused before the base class loads a network)
+            if len(self_dict.resolution) == 2:
+                raise ValueError("grid_variable 'c' with a two-entry resolution %s: 2-D colour grids are not built"
+                                 % (list(self_dict.resolution),))
+            if getattr(self_dict, "render_liquid", False):
+                raise ValueError("grid_variable 'c': render_liquid is not built for the colour render (pass "
+                                 "--render_liquid false)")
+            if getattr(self_dict, "ray_mode", ""):
+                raise ValueError("grid_variable 'c': ray_mode %r is not built for the colour render (leave --ray_mode empty)"
+                                 % (self_dict.ray_mode,))
+            if getattr(self_dict, "style_mask_on_ref", False):
+                raise ValueError("grid_variable 'c': style_mask_on_ref is not built for the colour render (pass "
+                                 "--style_mask_on_ref false)")
+            if (getattr(self_dict, "w_density", 0) or 0) > 0:
+                raise ValueError("grid_variable 'c': w_density acts on a density variable (pass --w_density 0)")
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (styler_3p module docstring)"
         self.target = getattr(self, "grid_variable", "") or "v"
-        assert self.target in ("v", "d") + engine.SOURCED
+        assert self.target in ("v", "d", "c") + engine.SOURCED
         self.adv_order = int(getattr(self, "adv_order", 1) or 1)       # config.py adv_order: 1 = SL, 2 = MacCormack
         self.octave_n = int(self.octave_n)
         if self.target == "d" and self.octave_n > 1:
@@ -121,7 +161,13 @@ class Styler(StylerBase):
                                                   nv=self.n_views)
             if self.n_views is None:
                 self.n_views = len(self.views)
-        self.loss = self._make_image_loss() if self.is2d else self._make_loss(rotate=self.rotate)
+        if self.target == "c":
+            # the colour render around an image loss (styler_3p's 'c' path); the image targets live in the image loss
+            self.loss = engine.ColourRenderLoss(self._make_image_loss(), self.transmit, self.v_batch if self.rotate else 1)
+            self.colour_bwd_route = getattr(self, "colour_bwd_route", None)   # ('tiled': bit-reproducible steps)
+        else:
+            self.loss = self._make_image_loss() if self.is2d else self._make_loss(rotate=self.rotate)
+        self._rot_dev = self._rot_src = None
         self._identity = T.rot_to_device([np.identity(3)], self.device)
         self.recursive = bool(getattr(self, "transport_recursive", True))
         self.pg = None          # set by the driver: frames shard over the ranks of this group
@@ -150,6 +196,11 @@ class Styler(StylerBase):
     def _rot(self):
         if not self.rotate:
             return self._identity
+        if self.target == "c":
+            # ONE device tensor per drawn view list: the colour stylizer keeps its ray weights while the views stand
+            if self._rot_src is not self.rot_mat_:
+                self._rot_dev, self._rot_src = T.rot_to_device(self.rot_mat_, self.device), self.rot_mat_
+            return self._rot_dev
         return T.rot_to_device(self.rot_mat_, self.device)
 
     def _resample_views(self):
@@ -263,11 +314,20 @@ class Styler(StylerBase):
         if st.Wt is not None and st.mine and not st.u_full:
             raise ValueError("params['v'] (simulation velocities) is needed to align the updates of a sequence")
         st.u_full = st.u_full or {}
-        st.C = ({"v": 2, "sp": 2} if self.is2d else {"v": 3, "s": 3, "sp": 4}).get(self.target, 1)
+        st.C = ({"v": 2, "sp": 2} if self.is2d else {"v": 3, "s": 3, "sp": 4, "c": 3}).get(self.target, 1)
         # the variable per key frame: stylisation velocity (zero, or params['v_init'][t]) / the density itself.
         # NOTE: at velocity == 0 every back-traced point sits exactly on a grid node, where the trilinear stencil has a
         # kink -- the first gradient is a one-sided derivative whose side depends on float rounding
-        st.v_init = params.get(self.target + "_init" if self.target in engine.SOURCED else "v_init")
+        st.v_init = params.get(self.target + "_init" if self.target in engine.SOURCED + ("c",) else "v_init")
+        st.c_noise = None
+        if self.target == "c" and not self._has_every(st.v_init, range(F_)):
+            # ONE seeded field for all frames, drawn once at full resolution by every rank alike: noise around the VGG
+            # mean / 255 (styler_2p.py:189-192, with its commented "same noise" choice: no flicker is seeded)
+            from . import vgg as vggmod
+            noise = self.rng.uniform(-5, 5, tuple(int(n) for n in self.resolution) + (3,)).astype(np.float32)
+            noise += np.array([vggmod._R_MEAN, vggmod._G_MEAN, vggmod._B_MEAN], np.float32)
+            noise /= 255
+            st.c_noise = noise
         st.hist, st.hist_octave, st.d_intm, st.opt_octave = [], [], [], []
         st.octave = 0
         self._enter_octave(None)
@@ -302,12 +362,13 @@ class Styler(StylerBase):
         st.d = {t: self._resample(x, size) for t, x in st.d_full.items()}
         st.u = {t: self._resample(x, size) for t, x in st.u_full.items()}
         st.shape = size + (st.C,)
+        targets = self.loss.image_loss if self.target == "c" else self.loss      # (who holds the image targets)
         if self.style_img is not None:
-            self.loss.set_style_image(self._style_feature(self.style_img, [H, W_]))
+            targets.set_style_image(self._style_feature(self.style_img, [H, W_]))
             if getattr(self, "w_hist", 0) > 0:
-                self.loss.set_hist_image(self._hist_feature(self.style_img, [H, W_]))
+                targets.set_hist_image(self._hist_feature(self.style_img, [H, W_]))
         if self.content_img is not None:
-            self.loss.set_content_image(self._content_feature(self.content_img, [H, W_]), top_k=self._content_top_k())
+            targets.set_content_image(self._content_feature(self.content_img, [H, W_]), top_k=self._content_top_k())
         st.lr = self.lr[o] if isinstance(self.lr, list) else self.lr
         if prev is None:
             st.g_opt = {t: self._initial(t) for t in st.mine}
@@ -318,7 +379,11 @@ class Styler(StylerBase):
         # (a rank beyond the number of optimiser groups owns no frame: it only takes part in the collectives)
         first = st.d[st.mine[0]] if st.mine else (next(iter(st.d.values())) if st.d else
                                                   torch.zeros(size, device=self.device))
-        if self.is2d:
+        if self.target == "c":
+            st.gs = engine.ColourGridStylizer(self.loss, first, k=self.k, lr=st.lr,
+                                              optimizer=getattr(self, "optimizer", "adam"), lap_n=self.lap_n,
+                                              bwd_route=self.colour_bwd_route)
+        elif self.is2d:
             st.gs = grid2d.GridStylizer2D(self.loss, first, target=self.target, lr=st.lr,
                                           optimizer=getattr(self, "optimizer", "adam"), adv_order=self.adv_order,
                                           lap_n=self.lap_n)
@@ -341,7 +406,17 @@ class Styler(StylerBase):
                 full = tuple(int(n) for n in self.resolution)
                 vi = self._dev(vi).reshape(full + (st.C,))
                 return self._resample(vi, st.shape[:-1], self._factor(full, st.shape[:-1])).reshape(st.shape).clone()
+        if self.target == "c":
+            return self._resample(self._dev(st.c_noise), st.shape[:-1]).reshape(st.shape).clone()
         return torch.zeros(st.shape, device=self.device)
+
+    @staticmethod
+    def _has_every(x, frames):
+        """does the params entry (list or {frame: array}) hold every one of ``frames``?"""
+        if x is None:
+            return False
+        get = (lambda t: x[t] if t < len(x) else None) if not isinstance(x, dict) else (lambda t: x.get(t))
+        return all(get(t) is not None for t in frames)
 
     def _infer(self, t, var):
         """frame t through its variable: (velocity the variable stands for or None, smoothed density, render with the
@@ -349,6 +424,8 @@ class Styler(StylerBase):
         st = self._st
         if self.is2d:
             return self._infer2d(t, var)
+        if self.target == "c":
+            return self._infer_colour(t, var)
         D, H, W_, _ = st.shape
         sourced = self.target in engine.SOURCED
         if self.target == "p":
@@ -362,6 +439,13 @@ class Styler(StylerBase):
             d_adv = var.reshape(D, H, W_)
         d_out = ops.smooth3d_relu_fwd(d_adv.contiguous(), float(self.k))
         return (vel if sourced else None), d_out, self.loss.d_img(d_out, self._identity)
+
+    def _infer_colour(self, t, var):
+        """``_infer`` of a colour frame: (None, the grey volume e_t, the colour image at the identity rotation [1,H,W,3]
+        0..255).  Through the loop's own stylizer bound to the frame (the loop re-binds before every step)"""
+        st = self._st
+        st.gs.bind(st.d[t], var.reshape(st.shape).contiguous())
+        return None, st.gs.grey(), st.gs.d_img(self._identity)
 
     def _infer2d(self, t, var):
         """``_infer`` on the 2-D path: (velocity [H,W,2] or None, the clipped image [H,W], its 0..255 rendering [1,H,W,3])"""
@@ -477,6 +561,7 @@ class Styler(StylerBase):
                     if t + self.interp < st.F:
                         full[t + i] = full[t] * float(1 - w[i]) + full[t + self.interp] * float(w[i])
         d_sty, r_sty, v_sty, u_sty = [], [], [], []        # (u_sty: the velocities of a run whose variable stands for one)
+        c_sty = []                                         # ('c': the masked colours, as styler_2p returns them)
         sourced = self.target in engine.SOURCED
         present = [t for t in range(st.F) if t in st.d]
         for t in present:
@@ -489,6 +574,8 @@ class Styler(StylerBase):
             d_sty.append(torch.abs(d_out).unsqueeze(-1).cpu().numpy())   # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
             v_sty.append(var.cpu().numpy())
+            if self.target == "c":
+                c_sty.append((torch.clamp(var, 0, 1) * torch.clamp(torch.abs(d_out), 0, 1).unsqueeze(-1)).cpu().numpy())
             if sourced:
                 u_sty.append(vel.cpu().numpy())
         hist = [[float(x) for x in l_.cpu()] for l_ in st.hist]
@@ -498,7 +585,20 @@ class Styler(StylerBase):
                 "d": np.array(d_sty), "r": np.array(r_sty), "v": v_sty if self.target == "v" else u_sty if sourced else None,
                 "s": v_sty if self.target == "s" else [a[..., 0] if self.is2d else a[..., :3] for a in v_sty] if self.target == "sp" else None,
                 "phi": v_sty if self.target == "p" else [a[..., -1] for a in v_sty] if self.target == "sp" else None,
-                "opt": v_sty, "p": None, "c": None, "frames": present}
+                "opt": v_sty, "p": None, "c": c_sty if self.target == "c" else None, "frames": present,
+                **({"c_init": self._c_init_result()} if self.target == "c" else {})}
+
+    def _c_init_result(self):
+        """what a colour run started from, per frame at full resolution: the caller's ``c_init`` where given, else the one
+        drawn field (the same array for every frame)"""
+        st = self._st
+        out = []
+        for t in range(st.F):
+            vi = None
+            if st.v_init is not None:
+                vi = st.v_init.get(t) if isinstance(st.v_init, dict) else (st.v_init[t] if t < len(st.v_init) else None)
+            out.append(np.asarray(vi, np.float32) if vi is not None else st.c_noise)
+        return out
 
     def run(self, params):
         self.prepare(params)
