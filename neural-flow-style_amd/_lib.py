@@ -146,16 +146,27 @@ except OSError as e:
     raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (EMISSION_HEADER_PATH, e))
 EMISSION_ABI_VERSION = _c5["NFS_EMISSION_ABI_VERSION"]
 
+# libnfs_liquid.so (the ray weights of a liquid colour render: --colour_render liquid of the two colour stylizers): the sixth
+LIQUID_LIB_PATH = os.path.join(_HERE, "libnfs_liquid.so")
+LIQUID_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_liquid.h"))
+try:
+    with open(LIQUID_HEADER_PATH) as _f:
+        LIQUID_SIGNATURES, LIQUID_RESTYPES, _, _c6 = read_header(_f.read())
+except OSError as e:
+    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (LIQUID_HEADER_PATH, e))
+LIQUID_ABI_VERSION = _c6["NFS_LIQUID_ABI_VERSION"]
+
 _lib = None
 _lib2d = None
 _libdescent = None
 _libcolour = None
 _libemission = None
+_libliquid = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so, libnfs_colour.so and
-    libnfs_emission.so (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so, libnfs_colour.so,
+    libnfs_emission.so and libnfs_liquid.so (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -261,6 +272,15 @@ def libemission():
     return _libemission
 
 
+def libliquid():
+    """libnfs_liquid.so, loaded the same way"""
+    global _libliquid
+    if _libliquid is None:
+        _libliquid = _load_beside(LIQUID_LIB_PATH, LIQUID_SIGNATURES, LIQUID_RESTYPES, "nfs_liquid_version",
+                                  LIQUID_ABI_VERSION)
+    return _libliquid
+
+
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
 # two events recorded on the SAME stream the kernel is enqueued on; entries are
 # name -> [(start_event, end_event, args)].  Costs two event records per call, so it is off by
@@ -279,6 +299,8 @@ def call(name, *args):
         L, L0 = libcolour(), L
     elif name in EMISSION_SIGNATURES:
         L, L0 = libemission(), L
+    elif name in LIQUID_SIGNATURES:
+        L, L0 = libliquid(), L
     else:
         L0 = L
     if PROFILE is not None:

@@ -14,7 +14,10 @@ and -- on the grid path -- ``lapnorm``: Laplacian-normalised descent (engine.Lap
 levels (0: mean-|g| normalisation).  ``--lr_decay``: the factor of the reference's ``cosine_decay`` (util.py:49-53) on the
 grid path's learning rate, from ``lr_decay * lr`` at the first iteration of an octave down to ``lr``; 1 = constant.
 ``--lr_decay`` (float, default 1) and ``--lap_n`` (int, default 3) are parsed when given and otherwise defaulted by
-``complete()``, like the attributes the drivers inject.
+``complete()``, like the attributes the drivers inject.  So are ``--colour_render`` ('' / 'smoke': the colour paths'
+emission-absorption render over black, max-normalised; 'liquid': front-to-back alpha compositing over a background,
+include/nfs_liquid.h; default '') and ``--colour_background`` (three floats in [0,1], the liquid render's background;
+default 1 1 1), read by the two colour stylizers (styler_3p ``target_field 'c'``, styler_grid ``grid_variable 'c'``).
 """
 from __future__ import annotations
 
@@ -108,7 +111,11 @@ _FLAGS = [
     # so that the Namespace of a bare get_config([]) stays the reference's flags plus the five extras above)
     ("MI355X", "lr_decay", dict(type=float, default=argparse.SUPPRESS)),
     ("MI355X", "lap_n", dict(type=int, default=argparse.SUPPRESS)),
+    ("MI355X", "colour_render", dict(type=str, default=argparse.SUPPRESS)),
+    ("MI355X", "colour_background", dict(nargs=3, type=float, default=argparse.SUPPRESS)),
 ]
+
+COLOUR_RENDERS = ("", "smoke", "liquid")
 
 
 def make_parser():
@@ -147,6 +154,35 @@ def check_optimizer(config, grid):
                          "--grid_variable); use 'adam' or 'lbfgs' here")
 
 
+def colour_background(background):
+    """``colour_background`` as a tuple of three floats in [0,1], or a ValueError naming the flag (a NaN is not in [0,1])"""
+    try:
+        bg = tuple(float(x) for x in background)
+    except (TypeError, ValueError):
+        bg = None
+    if bg is None or len(bg) != 3 or not all(0.0 <= x <= 1.0 for x in bg):
+        raise ValueError("--colour_background %r: the background of the liquid colour render is three numbers in [0,1]"
+                         % (background,))
+    return bg
+
+
+def check_colour_render(config, colour):
+    """the colour render's flags, checked where a stylizer is constructed, before a network is loaded (``colour``: the
+    stylizer's variable is a colour rendered through views -- styler_3p target_field 'c', styler_grid grid_variable 'c').
+    ValueError naming the flag for a ``colour_render`` outside '' / 'smoke' / 'liquid', for 'liquid' without a colour
+    variable, and for a ``colour_background`` that is not three numbers in [0,1].  -> (render, background)"""
+    render = getattr(config, "colour_render", "")
+    render = "" if render is None else render
+    if render not in COLOUR_RENDERS:
+        raise ValueError("--colour_render %r is none of %s" % (render, COLOUR_RENDERS))
+    bg = colour_background(getattr(config, "colour_background", (1.0, 1.0, 1.0)))
+    if render == "liquid" and not colour:
+        raise ValueError("--colour_render liquid without a colour variable: the liquid colour render belongs to "
+                         "--target_field c of the 3-D particle stylizer and --grid_variable c of the grid stylizer (the "
+                         "grey liquid render is --render_liquid)")
+    return render, bg
+
+
 def complete(config):
     """defaults for the attributes the reference drivers inject after parsing"""
     if not hasattr(config, "rng") or config.rng is None:
@@ -169,5 +205,9 @@ def complete(config):
         config.lr_decay = 1
     if not hasattr(config, "lap_n"):
         config.lap_n = 3
+    if not hasattr(config, "colour_render"):
+        config.colour_render = ""
+    if not hasattr(config, "colour_background"):
+        config.colour_background = [1.0, 1.0, 1.0]
 
     return config

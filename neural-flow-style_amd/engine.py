@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops, parallel
+from .config import COLOUR_RENDERS, colour_background
 
 HOST_BOUND = 0.85       # issue time over this share of the wall time: the GPU finished as soon as the host had issued the work
 
@@ -1525,15 +1526,49 @@ class ColourRenderLoss(object):
     d_gray = clip(I / M, 0, 1) -- is formed once per frame and view set (``prepare``); a step is the projection, the
     image loss and the projection's transpose.  The maximum M is taken per ``v_batch`` views (nfs_maxnorm_fwd's groups)
     and the image loss sees the views v_batch at a time, as one loss-net batch of the reference graph does: the total
-    over V views is the sum of the view batches' losses whichever ``views_mode`` presents them.  Eager launches only."""
+    over V views is the sum of the view batches' losses whichever ``views_mode`` presents them.  Eager launches only.
 
-    def __init__(self, image_loss, transmit, v_batch=1):
+    ``render="liquid"`` (include/nfs_liquid.h; '' and 'smoke' are the model above, every launch and bit of it unchanged):
+    front-to-back alpha compositing over ``background`` (three numbers in [0,1], default white).  With S = rotate(d),
+    B[z] the sum of the samples in front of z and t = exp(-tau sum_z S) the ray's transmittance,
+
+        w = tau exp(-tau B) phi(tau S) (ops.liquid_weights, one pass, no maximum),  J = sum_z w rotate(q) + t bg
+
+    still linear in q, so the projection, its transposes and the image loss are the ones above; the context carries
+    ``t_total``, the constant image ``bg_img`` = t (x) bg [V,H,W,3], ``grey`` = 1 - t (the reference's liquid image),
+    ``d_gray`` = (1 - t)[..., None] and ``gmax`` = None; ``v_batch`` only groups the image-loss batches.  sum_z w S + t = 1,
+    so a uniform colour c0 (q = c0 d) renders c0 (1 - t) + t bg, the reference's commented line styler_3p.py:153.  The
+    clip and its adjoint (``ops.clamp01_bwd``) see J with the background in it.  The weights are non-negative and at most
+    tau, so the 'coef' route's bound max |g| max w on the sample gradient (``ops.colour_project_bwd``,
+    nfs_rotate_bwd_coef in nfs_hip.h) holds as it does for T / M.  On the particle path d is smoothed by ``k`` and the
+    emission q is not (as in the smoke mode), so rotate(q) / S can exceed the particles' colour there and the clip takes
+    what is above 1; smoothing the emission is not built."""
+
+    RENDERS = COLOUR_RENDERS
+
+    def __init__(self, image_loss, transmit, v_batch=1, render="", background=(1, 1, 1)):
+        if render not in self.RENDERS:
+            raise ValueError("colour_render %r is none of %s" % (render, self.RENDERS))
         self.image_loss = image_loss
         self.tau = float(transmit)
         self.v_batch = max(int(v_batch or 1), 1)
+        self.liquid = render == "liquid"
+        self.background = colour_background(background)
+        self._bg_dev = None
+
+    def _prepare_liquid(self, d3, rot):
+        w, grey, t = ops.liquid_weights(d3, rot, self.tau)
+        if self._bg_dev is None or self._bg_dev.device != d3.device:
+            self._bg_dev = torch.tensor(self.background, dtype=torch.float32, device=d3.device)
+        bg_img = (t.unsqueeze(-1) * self._bg_dev).contiguous()
+        return {"rot": rot, "w": w, "grey": grey, "gmax": None, "d_gray": grey.unsqueeze(-1).contiguous(), "t_total": t,
+                "bg_img": bg_img}
 
     def prepare(self, d3, rot):
-        """d3 [D,H,W], rot [V,3,3] -> the frame's context: ray weights w [V,D,H,W], the grey image, d_gray [V,H,W,1]"""
+        """d3 [D,H,W], rot [V,3,3] -> the frame's context: ray weights w [V,D,H,W], the grey image, d_gray [V,H,W,1]
+        (liquid: also t_total [V,H,W] and bg_img [V,H,W,3])"""
+        if self.liquid:
+            return self._prepare_liquid(d3, rot)
         V = int(rot.shape[0])
         w = torch.empty((V,) + tuple(d3.shape), dtype=torch.float32, device=d3.device)
         grey, _ = ops.rotate_render_fwd(d3, rot, self.tau, False, d_rot=w)
@@ -1549,6 +1584,8 @@ class ColourRenderLoss(object):
     def project(self, q, ctx):
         """(J [V,H,W,C] before the clip, clip(J, 0, 1))"""
         J = ops.colour_project_fwd(q, ctx["rot"], ctx["w"])
+        if self.liquid:
+            J += ctx["bg_img"]                           # (t bg: one small add per step)
         return J, torch.clamp(J, 0, 1)
 
     def loss_and_grad(self, q, ctx, route=None):

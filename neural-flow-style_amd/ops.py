@@ -904,6 +904,27 @@ def colour_project_bwd(g_img, rot, w, g_q=None, route=None):
     return g_q
 
 
+# ---- the ray weights of a liquid colour render (include/nfs_liquid.h) -------------------------------------------------
+
+def liquid_weights(d, rot, tau, w=None, grey=None, t_total=None):
+    """d [D,H,W], rot [V,3,3] -> (w [V,D,H,W], grey [V,H,W], t_total [V,H,W]) in one pass over the rays:
+    w = tau exp(-tau B) phi(tau S) with S = rotate(d) gathered on the fly and B the sum of the samples in front,
+    t_total = exp(-tau sum_z S), grey = 1 - t_total (rotate_render_fwd(liquid=True)'s image).  sum_z w S + t_total = 1."""
+    D, H, W = d.shape
+    V = int(rot.shape[0])
+    if w is None:
+        w = _empty((V, D, H, W), d)
+    if grey is None:
+        grey = _empty((V, H, W), d)
+    if t_total is None:
+        t_total = _empty((V, H, W), d)
+    assert tuple(w.shape) == (V, D, H, W) and tuple(grey.shape) == (V, H, W) == tuple(t_total.shape)
+    _lib.call("nfs_liquid_weights", _ptr(d), _ptr(rot), float(tau), _ptr(w), _ptr(grey), _ptr(t_total), V, D, H, W,
+              _stream())
+    _written(w, grey, t_total)
+    return w, grey, t_total
+
+
 # ---- the emission of a colour grid (include/nfs_emission.h) -----------------------------------------------------------
 
 def _emission_dims(c, e):

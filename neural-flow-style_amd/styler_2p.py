@@ -19,7 +19,7 @@ from . import engine
 from . import ops
 from . import transform as T
 from . import vgg as vggmod
-from .config import check_optimizer
+from .config import check_colour_render, check_optimizer
 from .styler_base import StylerBase
 from .util import denoise
 
@@ -27,6 +27,7 @@ from .util import denoise
 class Styler(StylerBase):
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
+        check_colour_render(self_dict, colour=False)     # (a 2-D colour image has no rays: 'liquid' is refused here)
         StylerBase.__init__(self, self_dict)
         self.batch_size = max(int(self.batch_size), 1)
         if self.batch_size > 1 and getattr(self, "w_hist", 0):

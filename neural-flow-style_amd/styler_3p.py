@@ -10,7 +10,10 @@ Forward graph per frame (styler_3p.py:42-164):
   'c': the grey field of 'p' at zero displacement absorbs, q = p2g(p, pc=clip(c,0,1), pd=r) [D,H,W,3] emits
        (transform.py:1429-1441, the colour branch of the 3-D splat that no reference driver calls); the colour image
        of a view is clip(sum_z T/M rotate(q), 0, 1) -> x255 -> loss network: ``engine.ColourRenderLoss`` (build
-       extension; conventions of styler_2p)
+       extension; conventions of styler_2p).  ``--colour_render liquid``: the image is
+       clip(sum_z w rotate(q) + t bg, 0, 1), front-to-back alpha compositing over ``--colour_background`` (w, t:
+       include/nfs_liquid.h); 'r' and 'd_intm' are then over the background.  The grey volume is smoothed by k and q is
+       not, so rotate(q) / rotate(d) can exceed the particles' colour and the clip takes it
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -33,7 +36,7 @@ import torch
 from . import engine, ops, parallel
 from . import transform as T
 from . import vgg as vggmod
-from .config import check_optimizer
+from .config import check_colour_render, check_optimizer
 from .styler_base import StylerBase
 from .util import temporal_weights
 
@@ -61,12 +64,14 @@ class Styler(StylerBase):
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
+        check_colour_render(self_dict, colour=getattr(self_dict, "target_field", "") == "c")
         if getattr(self_dict, "target_field", "") == "c":
             # the colour path renders by emission-absorption only and has no auxiliary field terms (refused before the
             # base class loads a network)
             if getattr(self_dict, "render_liquid", False):
-                raise ValueError("target_field 'c': render_liquid is not built for the colour render (pass "
-                                 "--render_liquid false)")
+                raise ValueError("target_field 'c': render_liquid is the grey liquid render and is not built for the "
+                                 "colour render (pass --render_liquid false; the liquid colour render is "
+                                 "--colour_render liquid)")
             if getattr(self_dict, "ray_mode", ""):
                 raise ValueError("target_field 'c': ray_mode %r is not built for the colour render (leave --ray_mode empty)"
                                  % (self_dict.ray_mode,))
@@ -113,7 +118,9 @@ class Styler(StylerBase):
                                            w_content_amp=getattr(self, "w_content_amp", 100),
                                            w_hist=getattr(self, "w_hist", 0), hist_layer=getattr(self, "hist_layer", ()),
                                            w_hist_layer=getattr(self, "w_hist_layer", ()))
-        return engine.ColourRenderLoss(image_loss, self.transmit, self.v_batch if self.rotate else 1)
+        render, background = check_colour_render(self, colour=True)
+        return engine.ColourRenderLoss(image_loss, self.transmit, self.v_batch if self.rotate else 1, render=render,
+                                       background=background)
 
     # ---- the colour path (target_field 'c'): what a step does not change is formed once -------------------------
     _COLOUR_CTX_FLOATS = 1 << 30          # ray weights kept across steps (4 GiB); beyond it a context is formed per call

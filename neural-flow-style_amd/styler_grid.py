@@ -66,7 +66,7 @@ import torch
 
 from . import engine, grid2d, ops, parallel
 from . import transform as T
-from .config import check_optimizer
+from .config import check_colour_render, check_optimizer
 from .styler_base import StylerBase
 from .util import cosine_decay, temporal_weights
 
@@ -106,14 +106,19 @@ class Styler(StylerBase):
     variables, ``'r'`` uint8 colour images [F,H,W,3], ``'d'`` = abs(e) [F,D,H,W,1], ``'d_intm'`` in colour, ``'c_init'``
     what the run started from, ``'v'`` / ``'s'`` / ``'phi'`` / ``'p'`` None.  ``adv_order`` is accepted and has no effect
     (as with 'd'); an attribute ``colour_bwd_route`` on the config names the route of the projection's transpose ('tiled':
-    bit-reproducible).  Refused with a ValueError naming the flag: a two-entry ``resolution``, ``render_liquid``, a
-    non-empty ``ray_mode``, ``style_mask_on_ref``, ``w_density`` > 0.  Eager launches only.
+    bit-reproducible).  ``colour_render`` = 'liquid': the frame's image is clip(sum_z w rotate(q) + t bg, 0, 1), front-to-back
+    alpha compositing over ``colour_background`` (include/nfs_liquid.h; ``engine.ColourRenderLoss``); ``'r'`` and
+    ``'d_intm'`` are then over the background, everything else of the path unchanged.  Refused with a ValueError naming
+    the flag: a two-entry ``resolution``, ``render_liquid``, a non-empty ``ray_mode``, ``style_mask_on_ref``,
+    ``w_density`` > 0, a ``colour_render`` outside '' / 'smoke' / 'liquid' (and 'liquid' with another variable), a
+    ``colour_background`` that is not three numbers in [0,1].  Eager launches only.
     Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
     sharding, a MacCormack transport between frames, ``batch_size > 1``, a root-level driver (the reference has none for
     grids)."""
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=True)
+        check_colour_render(self_dict, colour=getattr(self_dict, "grid_variable", "") == "c")
         if getattr(self_dict, "grid_variable", "") == "c":
             # the colour grid renders by emission-absorption through an image loss and has no auxiliary field terms
             # (refused before the base class loads a network)
@@ -121,8 +126,9 @@ class Styler(StylerBase):
                 raise ValueError("grid_variable 'c' with a two-entry resolution %s: 2-D colour grids are not built"
                                  % (list(self_dict.resolution),))
             if getattr(self_dict, "render_liquid", False):
-                raise ValueError("grid_variable 'c': render_liquid is not built for the colour render (pass "
-                                 "--render_liquid false)")
+                raise ValueError("grid_variable 'c': render_liquid is the grey liquid render and is not built for the "
+                                 "colour render (pass --render_liquid false; the liquid colour render is "
+                                 "--colour_render liquid)")
             if getattr(self_dict, "ray_mode", ""):
                 raise ValueError("grid_variable 'c': ray_mode %r is not built for the colour render (leave --ray_mode empty)"
                                  % (self_dict.ray_mode,))
@@ -163,7 +169,9 @@ class Styler(StylerBase):
                 self.n_views = len(self.views)
         if self.target == "c":
             # the colour render around an image loss (styler_3p's 'c' path); the image targets live in the image loss
-            self.loss = engine.ColourRenderLoss(self._make_image_loss(), self.transmit, self.v_batch if self.rotate else 1)
+            render, background = check_colour_render(self, colour=True)
+            self.loss = engine.ColourRenderLoss(self._make_image_loss(), self.transmit, self.v_batch if self.rotate else 1,
+                                                render=render, background=background)
             self.colour_bwd_route = getattr(self, "colour_bwd_route", None)   # ('tiled': bit-reproducible steps)
         else:
             self.loss = self._make_image_loss() if self.is2d else self._make_loss(rotate=self.rotate)
