@@ -329,8 +329,19 @@ __global__ void __launch_bounds__(256) loss_net_input_bwd_kernel(const float* __
   const int x2 = (int)(gid % W2);
   const int y2 = (int)((gid / W2) % H2);
   const int b = (int)(gid / ((int64_t)W2 * H2));
-  float g[3] = {g_x[gid * 3] * 255.f, g_x[gid * 3 + 1] * 255.f, g_x[gid * 3 + 2] * 255.f};
-  if (Cin == 1) g[0] = g[0] + g[1] + g[2];
+  float g[3];
+  {
+    // three products and, for a grey image, two sums, each its own float32 rounding -- GradInput's arithmetic (render.hip),
+    // so that the two-step adjoint and the fused one take the same gradient; contracted, the third product rode in an FMA
+#pragma clang fp contract(off)
+    g[0] = g_x[gid * 3] * 255.f;
+    g[1] = g_x[gid * 3 + 1] * 255.f;
+    g[2] = g_x[gid * 3 + 2] * 255.f;
+    if (Cin == 1) {
+      const float g01 = g[0] + g[1];
+      g[0] = g01 + g[2];
+    }
+  }
   float* gi = g_img + (int64_t)b * H * W * Cin;
   const bool resize = (H2 != H) || (W2 != W);
   if (!resize) {

@@ -656,11 +656,16 @@ struct StorePlain {                                     // y = x / m
 };
 struct StoreInput {                                     // the loss net's three channels
   static constexpr int C = 3;
+  // every operation its own float32 rounding (v as the stored intermediate of the two-step form).  The operators are
+  // written out under contract(off): HIP's __fmul_rn / __fsub_rn are plain x * y / x - y, and inlined they were
+  // contracted -- x[., 2] came out as fma(x / m, 255, -mean[2]) where x[., 0] and x[., 1] took the rounded v
   static __device__ __forceinline__ void put(float* __restrict__ o, int i, float x, float m) {
-    const float v = __fmul_rn(x / m, 255.f);            // (rounded like the stored intermediate of the two-step form)
-    o[3 * (int64_t)i] = __fsub_rn(v, kInputMean[0]);
-    o[3 * (int64_t)i + 1] = __fsub_rn(v, kInputMean[1]);
-    o[3 * (int64_t)i + 2] = __fsub_rn(v, kInputMean[2]);
+#pragma clang fp contract(off)
+    const float q = x / m;
+    const float v = q * 255.f;
+    o[3 * (int64_t)i] = v - kInputMean[0];
+    o[3 * (int64_t)i + 1] = v - kInputMean[1];
+    o[3 * (int64_t)i + 2] = v - kInputMean[2];
   }
 };
 struct GradPlain {
@@ -670,7 +675,10 @@ struct GradPlain {
 struct GradInput {                                      // 255 (g[.,0] + g[.,1] + g[.,2])
   static constexpr int C = 3;
   static __device__ __forceinline__ float at(const float* __restrict__ g, int64_t i) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(g[3 * i], 255.f), __fmul_rn(g[3 * i + 1], 255.f)), __fmul_rn(g[3 * i + 2], 255.f));
+#pragma clang fp contract(off)                          // (three products and two sums, each rounded: as StoreInput)
+    const float a = g[3 * i] * 255.f, b = g[3 * i + 1] * 255.f, c = g[3 * i + 2] * 255.f;
+    const float ab = a + b;
+    return ab + c;
   }
 };
 

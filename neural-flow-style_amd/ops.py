@@ -186,18 +186,19 @@ def advect_bwd_adam_slab(d, vel_slab, g_slab, m_slab, v_slab, z0, lr_t, beta1=0.
     _written(vel_slab, m_slab, v_slab, adv_next)
 
 
-def warp2d_fwd(imgs, coords):
+def warp2d_fwd(imgs, coords, out=None):
     """imgs [B,X,Y,C], coords [B,2,X,Y] -> [B,X,Y,C]  (transform.py:206-236, 280-341)"""
     B, X, Y, Cn = imgs.shape
-    out = _empty(imgs.shape, imgs)
+    if out is None:
+        out = _empty(imgs.shape, imgs)
     _lib.call("nfs_warp2d_fwd", _ptr(imgs), _ptr(coords), _ptr(out), B, X, Y, Cn, _stream())
     return out
 
 
-def warp2d_bwd(imgs, coords, g_out, need_imgs=True, need_coords=True):
+def warp2d_bwd(imgs, coords, g_out, need_imgs=True, need_coords=True, out_coords=None):
     B, X, Y, Cn = imgs.shape
     g_imgs = _zeros(imgs.shape, imgs) if need_imgs else None
-    g_coords = _empty(coords.shape, imgs) if need_coords else None
+    g_coords = (_empty(coords.shape, imgs) if out_coords is None else out_coords) if need_coords else None
     _lib.call("nfs_warp2d_bwd", _ptr(imgs), _ptr(coords), _ptr(g_out), _ptr(g_imgs), _ptr(g_coords), B, X, Y, Cn,
               _stream())
     return g_imgs, g_coords
@@ -793,20 +794,21 @@ def maxnorm_bwd(img, gmax, g_out, g_img=None):
     return g_img
 
 
-def maxnorm_input_fwd(img, groups):
+def maxnorm_input_fwd(img, groups, out=None, gmax=None):
     """img [V,H,W] (grey render) -> (x [V,H,W,3] = (img / max) * 255 - mean, gmax [groups]): nfs_maxnorm_fwd +
     nfs_loss_net_input_fwd in one pass (loss net at the render's size)"""
     V, H, W = img.shape
-    x = _empty((V, H, W, 3), img)
-    gmax = _empty((groups,), img)
+    x = _empty((V, H, W, 3), img) if out is None else out
+    if gmax is None:
+        gmax = _empty((groups,), img)
     _lib.call("nfs_maxnorm_input_fwd", _ptr(img), _ptr(x), _ptr(gmax), groups, img.numel() // groups, _stream())
     return x, gmax
 
 
-def maxnorm_input_bwd(img, gmax, g_x):
+def maxnorm_input_bwd(img, gmax, g_x, out=None):
     """adjoint of maxnorm_input_fwd: g_x [V,H,W,3] -> g_img [V,H,W]"""
     groups = gmax.numel()
-    g_img = _empty(img.shape, img)
+    g_img = _empty(img.shape, img) if out is None else out
     ws = _empty((_lib.lib().nfs_maxnorm_workspace_floats(groups),), img)
     _lib.call("nfs_maxnorm_input_bwd", _ptr(img), _ptr(gmax), _ptr(g_x), _ptr(g_img), groups, img.numel() // groups,
               _ptr(ws), _stream())
@@ -967,20 +969,20 @@ def emission_bwd_adam(g_q, c, e, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
 
 # ---- A5 -----------------------------------------------------------------------------
 
-def loss_net_input_fwd(img, H2=None, W2=None, want_d_img=True, want_x=True):
+def loss_net_input_fwd(img, H2=None, W2=None, want_d_img=True, want_x=True, out_d_img=None, out_x=None):
     """img [B,H,W,Cin] in [0,1] -> (d_img [B,H2,W2,3] 0..255, x = d_img - mean)"""
     B, H, W, Cin = img.shape
     H2 = H if H2 is None else H2
     W2 = W if W2 is None else W2
-    d_img = _empty((B, H2, W2, 3), img) if want_d_img else None
-    x = _empty((B, H2, W2, 3), img) if want_x else None
+    d_img = (_empty((B, H2, W2, 3), img) if out_d_img is None else out_d_img) if want_d_img else None
+    x = (_empty((B, H2, W2, 3), img) if out_x is None else out_x) if want_x else None
     _lib.call("nfs_loss_net_input_fwd", _ptr(img), _ptr(d_img), _ptr(x), B, H, W, Cin, H2, W2, _stream())
     return d_img, x
 
 
-def loss_net_input_bwd(g_x, H, W, Cin):
+def loss_net_input_bwd(g_x, H, W, Cin, out=None):
     B, H2, W2, _ = g_x.shape
-    g_img = _empty((B, H, W, Cin), g_x)
+    g_img = _empty((B, H, W, Cin), g_x) if out is None else out
     _lib.call("nfs_loss_net_input_bwd", _ptr(g_x), _ptr(g_img), B, H, W, Cin, H2, W2, _stream())
     return g_img
 
@@ -1209,10 +1211,11 @@ def content_loss(F, weight, loss_acc, g_acc, channel=0, target=None, amp=100.0, 
     return g_acc
 
 
-def resize_bicubic_tf1(x, oh, ow):
+def resize_bicubic_tf1(x, oh, ow, out=None):
     """TF-1 legacy bicubic resize of x [B,H,W,C] -> [B,oh,ow,C] (styler_base.py:166), forward only"""
     B, H, W, Cn = x.shape
-    out = _empty((B, oh, ow, Cn), x)
+    if out is None:
+        out = _empty((B, oh, ow, Cn), x)
     _lib.call("nfs_resize_bicubic_tf1", _ptr(x), _ptr(out), B, H, W, Cn, int(oh), int(ow), _stream())
     return out
 
@@ -1411,23 +1414,25 @@ def _iptr(t):
     return t.data_ptr()
 
 
-def colour_clamp_gather(var, order=None):
+def colour_clamp_gather(var, order=None, out=None):
     """clip(var, 0, 1) read through a permutation (int64 [N], None = identity): var [N,C] -> [N,C]"""
-    out = _empty(var.shape, var)
+    if out is None:
+        out = _empty(var.shape, var)
     _lib.call("nfs_colour_clamp_gather", _ptr(var), _iptr(order), _ptr(out), var.shape[0], var.shape[1], _stream())
     return out
 
 
-def clamp01_bwd(g, x):
+def clamp01_bwd(g, x, out=None):
     """adjoint of clip(x, 0, 1): g where 0 <= x <= 1, else 0"""
-    out = _empty(g.shape, g)
+    if out is None:
+        out = _empty(g.shape, g)
     _lib.call("nfs_clamp01_bwd", _ptr(g), _ptr(x), _ptr(out), g.numel(), _stream())
     return out
 
 
-def colour_clamp_scatter_bwd(g_cc, var, order=None):
+def colour_clamp_scatter_bwd(g_cc, var, order=None, out=None):
     """adjoint of colour_clamp_gather: g_var[order[i]] = g_cc[i] where 0 <= var[order[i]] <= 1, else 0"""
-    g_var = _empty(var.shape, var)
+    g_var = _empty(var.shape, var) if out is None else out
     _lib.call("nfs_colour_clamp_scatter_bwd", _ptr(g_cc), _iptr(order), _ptr(var), _ptr(g_var), var.shape[0], var.shape[1],
               _stream())
     return g_var

@@ -216,14 +216,17 @@ def advect_adjoint(d, vel, g, init_d=None, stencil="generic", face_margin=FACE_M
 
 
 def warp_fwd(imgs, coords, stencil="generic"):
-    """nfs_warp3d_fwd: imgs [B,X,Y,Z,C], coords [B,3,X,Y,Z] -> (out, bound) [B,X,Y,Z,C]"""
+    """nfs_warp3d_fwd: imgs [B,X,Y,Z,C], coords [B,3,X,Y,Z] -> (out, bound) [B,X,Y,Z,C]; nfs_warp2d_fwd on two axes:
+    imgs [B,X,Y,C], coords [B,2,X,Y] (nothing below assumes three: the 2-D stencil has fewer roundings than K_GENERIC
+    counts)"""
     res = [sample(imgs[b], coords[b], explicit=True, stencil=stencil) for b in range(imgs.shape[0])]
     return np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
 
 
 def warp_adjoint(imgs, coords, g):
     """nfs_warp3d_bwd: g_imgs [B,X,Y,Z,C] and g_coords [B,3,X,Y,Z] with their bounds; vel_cand / bound_vel hold the
-    coordinate gradient per batch entry in [X,Y,Z,3] layout for vel_excess"""
+    coordinate gradient per batch entry in [X,Y,Z,3] layout for vel_excess.  nfs_warp2d_bwd on two axes: g_imgs
+    [B,X,Y,C], g_coords [B,2,X,Y], the candidates in [X,Y,2] layout"""
     out = []
     for b in range(imgs.shape[0]):
         f = np.asarray(imgs[b], dtype=np.float64)

@@ -1,5 +1,7 @@
 """Writes tests/golden/colour_unchanged_targets.npz: the 'p' and 'd' runs of tests/colour_runs.py as the commit BEFORE
 target_field 'c' computed them on an MI355X (tests/test_colour_stylizer_gpu.py compares the current build's bits).
+A commit that changes a kernel's roundings on purpose records the fixture again from its own build and says so in that
+test's docstring (so far: StoreInput / GradInput of render.hip rounding every operation).
 
     python tests/golden/make_colour_unchanged_fixture.py CHECKOUT OUT.npz
 

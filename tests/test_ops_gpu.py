@@ -1,7 +1,12 @@
 """Operator parity: every HIP entry point vs the CPU oracle on the same seeded
 inputs (through the C ABI).  Tolerance: relative L2 <= 1e-4 per operator for
 float32 (north_star's end-to-end bar is 1e-3; float atomics make the scatter
-adjoints run-to-run non-deterministic at ~1e-7)."""
+adjoints run-to-run non-deterministic at ~1e-7).
+
+These are aggregate checks.  The max-normalisation, the loss-net input, the legacy bicubic resize and the explicit 2-D
+warp are also held element by element, bit for bit or within derived bounds, by tests/test_seam_kernels_gpu.py (most
+other operators by the test_*_gpu.py file of their reference module); the aggregate tests of those operators stay here
+beside them."""
 import numpy as np
 import pytest
 import torch
