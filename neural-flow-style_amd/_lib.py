@@ -1,7 +1,12 @@
-"""ctypes loader for libnfs_hip.so.
+"""ctypes loader for libnfs_hip.so and the side libraries beside it.
 
 include/nfs_hip.h is the only declaration of the C ABI: ``read_header`` derives the argtypes, the return types, the
 struct layouts, the NFS_E* codes and the ABI version from it at import time (no compiler, no library, no GPU).
+
+A side library is a key of ``SIDE``: libnfs_<key>.so beside the package, declared in include/nfs_<key>.h (read by the
+same ``read_header``), versioned by NFS_<KEY>_ABI_VERSION / nfs_<key>_version().  It links against libnfs_hip.so (one error
+channel, one HIP runtime).  ``SIDE`` holds one record per key, ``side(key)`` returns the loaded library, and ``call`` finds
+the library that owns a name.
 
 The HIP library is the product path: there is NO CPU fallback.  If the shared
 object is missing, importing an op raises immediately (``NfsLibraryError``).
@@ -97,76 +102,55 @@ def read_header(text):
     return signatures, restypes, structs, constants
 
 
-try:
-    with open(HEADER_PATH) as _f:
-        SIGNATURES, RESTYPES, _structs, _constants = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (HEADER_PATH, e))
+def _read(path):
+    try:
+        with open(path) as f:
+            return read_header(f.read())
+    except OSError as e:
+        raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (path, e))
+
+
+SIGNATURES, RESTYPES, _structs, _constants = _read(HEADER_PATH)
 SplatCfg, GramLayer, ConvDesc = _structs["nfs_splat_cfg"], _structs["nfs_gram_layer_t"], _structs["nfs_conv2d_desc_t"]
 NFS_EINVAL, NFS_ELAUNCH = _constants["NFS_EINVAL"], _constants["NFS_ELAUNCH"]
 ABI_VERSION = _constants["NFS_ABI_VERSION"]          # what nfs_version() of a library built from this header returns
 
-# libnfs_grid2d.so (the 2-D grid stylizer's operators): a library and a header of its own, bound the same way
-GRID2D_LIB_PATH = os.path.join(_HERE, "libnfs_grid2d.so")
-GRID2D_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_grid2d.h"))
-try:
-    with open(GRID2D_HEADER_PATH) as _f:
-        GRID2D_SIGNATURES, GRID2D_RESTYPES, _, _c2 = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (GRID2D_HEADER_PATH, e))
-GRID2D_ABI_VERSION = _c2["NFS_GRID2D_ABI_VERSION"]
 
-# libnfs_descent.so (the update kernels of optimizer 'lapnorm'): the third library and header, bound the same way
-DESCENT_LIB_PATH = os.path.join(_HERE, "libnfs_descent.so")
-DESCENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_descent.h"))
-try:
-    with open(DESCENT_HEADER_PATH) as _f:
-        DESCENT_SIGNATURES, DESCENT_RESTYPES, _, _c3 = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (DESCENT_HEADER_PATH, e))
-DESCENT_ABI_VERSION = _c3["NFS_DESCENT_ABI_VERSION"]
+class SideLibrary:
+    """what the binding knows of libnfs_<key>.so: everything but ``handle`` (the loaded library, see ``side``) is derived
+    from the key and from include/nfs_<key>.h at import"""
 
-# libnfs_colour.so (colour rendering through the views: target_field 'c' of the 3-D particle stylizer): the fourth
-COLOUR_LIB_PATH = os.path.join(_HERE, "libnfs_colour.so")
-COLOUR_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_colour.h"))
-try:
-    with open(COLOUR_HEADER_PATH) as _f:
-        COLOUR_SIGNATURES, COLOUR_RESTYPES, _, _c4 = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (COLOUR_HEADER_PATH, e))
-COLOUR_ABI_VERSION = _c4["NFS_COLOUR_ABI_VERSION"]
+    def __init__(self, key):
+        self.key, self.handle = key, None
+        self.path = os.path.join(_HERE, "libnfs_%s.so" % key)
+        self.header_path = os.path.join(os.path.dirname(HEADER_PATH), "nfs_%s.h" % key)
+        self.signatures, self.restypes, _, constants = _read(self.header_path)
+        self.abi, self.version_fn = constants["NFS_%s_ABI_VERSION" % key.upper()], "nfs_%s_version" % key
 
-# libnfs_emission.so (the emission model of a colour grid: grid_variable 'c' of the grid-sequence stylizer): the fifth
-EMISSION_LIB_PATH = os.path.join(_HERE, "libnfs_emission.so")
-EMISSION_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_emission.h"))
-try:
-    with open(EMISSION_HEADER_PATH) as _f:
-        EMISSION_SIGNATURES, EMISSION_RESTYPES, _, _c5 = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (EMISSION_HEADER_PATH, e))
-EMISSION_ABI_VERSION = _c5["NFS_EMISSION_ABI_VERSION"]
 
-# libnfs_liquid.so (the ray weights of a liquid colour render: --colour_render liquid of the two colour stylizers): the sixth
-LIQUID_LIB_PATH = os.path.join(_HERE, "libnfs_liquid.so")
-LIQUID_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "nfs_liquid.h"))
-try:
-    with open(LIQUID_HEADER_PATH) as _f:
-        LIQUID_SIGNATURES, LIQUID_RESTYPES, _, _c6 = read_header(_f.read())
-except OSError as e:
-    raise NfsLibraryError("the binding is derived from %s, which cannot be read: %s" % (LIQUID_HEADER_PATH, e))
-LIQUID_ABI_VERSION = _c6["NFS_LIQUID_ABI_VERSION"]
+def _owners(records):
+    """entry point -> the record of the side library that declares it; a name of nfs_hip.h is in none of them"""
+    owners = {}
+    for r in records:
+        for name in r.signatures:
+            if name in owners or name in SIGNATURES:
+                raise NfsLibraryError("%s declares %s, which %s declares too: call() could not tell whose it is"
+                                      % (r.header_path, name, owners[name].header_path if name in owners else HEADER_PATH))
+            owners[name] = r
+    return owners
 
+
+# grid2d: the 2-D grid stylizer's operators; descent: the update kernels of optimizer 'lapnorm'; colour: colour rendering
+# through the views (target_field 'c' of the 3-D particle stylizer); emission: the emission model of a colour grid
+# (grid_variable 'c' of the grid-sequence stylizer); liquid: the ray weights of a liquid colour render (colour_render
+# 'liquid')
+SIDE = {k: SideLibrary(k) for k in ("grid2d", "descent", "colour", "emission", "liquid")}
+_OWNER = _owners(SIDE.values())
 _lib = None
-_lib2d = None
-_libdescent = None
-_libcolour = None
-_libemission = None
-_libliquid = None
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into libnfs_hip.so, libnfs_grid2d.so, libnfs_descent.so, libnfs_colour.so,
-    libnfs_emission.so and libnfs_liquid.so (in-tree)."""
+    """Compile csrc/*.hip for gfx950 into libnfs_hip.so and one libnfs_<key>.so per side library (in-tree)."""
     # (MAX_JOBS when set, else at most 16: the core count of a shared host is not this build's to take)
     jobs = os.environ.get("MAX_JOBS") or str(min(os.cpu_count() or 4, 16))
     r = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs],
@@ -178,48 +162,16 @@ def build(verbose=False):
     return LIB_PATH
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise NfsLibraryError(
-                "libnfs_hip.so is missing (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "-- there is no CPU fallback for the product path" % LIB_PATH)
-        # PyTorch-ROCm ships its own HIP runtime; it must be the one already resident when libnfs_hip.so resolves
-        # libamdhip64 -- loading this library first leaves the process with two runtimes and every later launch
-        # fails with "no ROCm-capable device is detected" (seen when build() and smoke() shared a process)
-        import torch  # noqa: F401
-        try:
-            L = C.CDLL(LIB_PATH)
-        except OSError as e:  # pragma: no cover
-            raise NfsLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-        for name, argt in SIGNATURES.items():
-            try:
-                f = getattr(L, name)
-            except AttributeError:
-                raise NfsLibraryError("libnfs_hip.so does not export %s (stale build?)" % name)
-            f.argtypes = argt
-            f.restype = RESTYPES[name]
-        # the binding is the header at hand, and the library moves with it (entry points, packed-filter sizes, the default
-        # GEMM arithmetic): a .so built from another header, with every symbol present, must not be driven by this one
-        if L.nfs_version() != ABI_VERSION:
-            stale = ("the library is stale: rebuild (make -C %s)" % CSRC_DIR if L.nfs_version() < ABI_VERSION else
-                     "the header is stale: %s is older than the library" % HEADER_PATH)
-            raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d; %s"
-                                  % (LIB_PATH, L.nfs_version(), ABI_VERSION, stale))
-        _lib = L
-    return _lib
-
-
-def _load_beside(path, signatures, restypes, version_fn, abi):
-    """a library that links against libnfs_hip.so (one error channel, one HIP runtime), loaded after it and checked
-    against its own header: every declared symbol present, the version the header's"""
-    lib()
-    so = os.path.basename(path)
+def _open(so, path, header_path, signatures, restypes, version_fn, abi):
+    """the shared object at ``path``, every declared symbol bound, its version the header's"""
     if not os.path.exists(path):
         raise NfsLibraryError(
             "%s is missing (%s): run `python -c 'import __graft_entry__ as g; g.build()'` "
             "-- there is no CPU fallback for the product path" % (so, path))
+    # PyTorch-ROCm ships its own HIP runtime; it must be the one already resident when libnfs_hip.so resolves
+    # libamdhip64 -- loading this library first leaves the process with two runtimes and every later launch
+    # fails with "no ROCm-capable device is detected" (seen when build() and smoke() shared a process)
+    import torch  # noqa: F401
     try:
         L = C.CDLL(path)
     except OSError as e:  # pragma: no cover
@@ -231,54 +183,31 @@ def _load_beside(path, signatures, restypes, version_fn, abi):
             raise NfsLibraryError("%s does not export %s (stale build?)" % (so, name))
         f.argtypes = argt
         f.restype = restypes[name]
-    if getattr(L, version_fn)() != abi:
-        raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d: rebuild (make -C %s)"
-                              % (path, getattr(L, version_fn)(), abi, CSRC_DIR))
+    # the binding is the header at hand, and the library moves with it (entry points, packed-filter sizes, the default
+    # GEMM arithmetic): a .so built from another header, with every symbol present, must not be driven by this one
+    got = getattr(L, version_fn)()
+    if got != abi:
+        stale = ("the library is stale: rebuild (make -C %s)" % CSRC_DIR if got < abi else
+                 "the header is stale: %s is older than the library" % header_path)
+        raise NfsLibraryError("%s reports ABI %d, the header this binding is read from declares %d; %s"
+                              % (path, got, abi, stale))
     return L
 
 
-def lib2d():
-    """libnfs_grid2d.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
-    global _lib2d
-    if _lib2d is None:
-        _lib2d = _load_beside(GRID2D_LIB_PATH, GRID2D_SIGNATURES, GRID2D_RESTYPES, "nfs_grid2d_version", GRID2D_ABI_VERSION)
-    return _lib2d
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = _open("libnfs_hip.so", LIB_PATH, HEADER_PATH, SIGNATURES, RESTYPES, "nfs_version", ABI_VERSION)
+    return _lib
 
 
-def libdescent():
-    """libnfs_descent.so, loaded the same way"""
-    global _libdescent
-    if _libdescent is None:
-        _libdescent = _load_beside(DESCENT_LIB_PATH, DESCENT_SIGNATURES, DESCENT_RESTYPES, "nfs_descent_version",
-                                   DESCENT_ABI_VERSION)
-    return _libdescent
-
-
-def libcolour():
-    """libnfs_colour.so, loaded the same way"""
-    global _libcolour
-    if _libcolour is None:
-        _libcolour = _load_beside(COLOUR_LIB_PATH, COLOUR_SIGNATURES, COLOUR_RESTYPES, "nfs_colour_version",
-                                  COLOUR_ABI_VERSION)
-    return _libcolour
-
-
-def libemission():
-    """libnfs_emission.so, loaded the same way"""
-    global _libemission
-    if _libemission is None:
-        _libemission = _load_beside(EMISSION_LIB_PATH, EMISSION_SIGNATURES, EMISSION_RESTYPES, "nfs_emission_version",
-                                    EMISSION_ABI_VERSION)
-    return _libemission
-
-
-def libliquid():
-    """libnfs_liquid.so, loaded the same way"""
-    global _libliquid
-    if _libliquid is None:
-        _libliquid = _load_beside(LIQUID_LIB_PATH, LIQUID_SIGNATURES, LIQUID_RESTYPES, "nfs_liquid_version",
-                                  LIQUID_ABI_VERSION)
-    return _libliquid
+def side(key):
+    """libnfs_<key>.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
+    r = SIDE[key]
+    if r.handle is None:
+        lib()
+        r.handle = _open(os.path.basename(r.path), r.path, r.header_path, r.signatures, r.restypes, r.version_fn, r.abi)
+    return r.handle
 
 
 # Optional live profiling (used by bench.py --full): when PROFILE is a dict, every call is bracketed by
@@ -290,19 +219,9 @@ PROFILE = None
 
 def call(name, *args):
     """Call an int-returning entry point; raise with nfs_last_error() on failure."""
-    L = lib()
-    if name in GRID2D_SIGNATURES:            # (the error text stays libnfs_hip.so's: the libraries share nfs::set_error)
-        L, L0 = lib2d(), L
-    elif name in DESCENT_SIGNATURES:
-        L, L0 = libdescent(), L
-    elif name in COLOUR_SIGNATURES:
-        L, L0 = libcolour(), L
-    elif name in EMISSION_SIGNATURES:
-        L, L0 = libemission(), L
-    elif name in LIQUID_SIGNATURES:
-        L, L0 = libliquid(), L
-    else:
-        L0 = L
+    L0 = lib()                       # (the error text stays libnfs_hip.so's: the libraries share nfs::set_error)
+    r = _OWNER.get(name)
+    L = L0 if r is None else side(r.key)
     if PROFILE is not None:
         import torch
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)

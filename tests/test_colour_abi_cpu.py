@@ -1,67 +1,11 @@
-"""The boundary of libnfs_colour.so without a GPU: it exports exactly what include/nfs_colour.h declares, the three
-libraries beside it export what they did, and every entry point refuses bad arguments before any launch."""
+"""The boundary of libnfs_colour.so without a GPU: every entry point refuses bad arguments before any launch
+(what it exports, its version and the routing of its names: tests/test_side_libraries_cpu.py)."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _built():
-    from neural_flow_style_amd import _lib
-    if not all(os.path.exists(p) for p in (_lib.LIB_PATH, _lib.GRID2D_LIB_PATH, _lib.DESCENT_LIB_PATH,
-                                           _lib.COLOUR_LIB_PATH)):
-        _lib.build()
-    return _lib
-
-
-def _defined(path):
-    nm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else shutil.which("nm")
-    assert nm, "neither llvm-nm of the ROCm toolchain that built the library nor nm"
-    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.split()}
-    return {n for n in names if re.fullmatch(r"nfs_\w+", n)}
-
-
-def test_exported_symbols_equal_the_header():
-    _lib = _built()
-    hdr = open(os.path.join(ROOT, "include", "nfs_colour.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(nfs_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == {"nfs_colour_version", "nfs_ray_weights", "nfs_colour_project_fwd", "nfs_colour_project_bwd"}
-    assert declared == set(_lib.COLOUR_SIGNATURES)
-    assert _defined(_lib.COLOUR_LIB_PATH) == declared
-    assert _lib.libcolour().nfs_colour_version() == _lib.COLOUR_ABI_VERSION == 100
-
-
-def test_the_other_libraries_export_what_they_did():
-    """libnfs_hip.so keeps its 134 entry points, and each library defines exactly its own header's names: nothing moved
-    between them"""
-    _lib = _built()
-    hip = _defined(_lib.LIB_PATH)
-    assert hip == set(_lib.SIGNATURES) and len(hip) == 134
-    assert _defined(_lib.GRID2D_LIB_PATH) == set(_lib.GRID2D_SIGNATURES)
-    assert _defined(_lib.DESCENT_LIB_PATH) == set(_lib.DESCENT_SIGNATURES)
-    assert _lib.ABI_VERSION == _lib.lib().nfs_version()
-    assert _lib.lib2d().nfs_grid2d_version() == _lib.GRID2D_ABI_VERSION
-    assert _lib.libdescent().nfs_descent_version() == _lib.DESCENT_ABI_VERSION
-    names = [set(_lib.SIGNATURES), set(_lib.GRID2D_SIGNATURES), set(_lib.DESCENT_SIGNATURES), set(_lib.COLOUR_SIGNATURES)]
-    for i in range(4):
-        for j in range(i + 1, 4):
-            assert not (names[i] & names[j]), names[i] & names[j]
-
-
-def test_the_binding_routes_a_call_to_the_fourth_library():
-    _lib = _built()
-    with pytest.raises(_lib.NfsError, match="nfs_ray_weights: null pointer") as e:
-        _lib.call("nfs_ray_weights", None, 0.1, None, 1, None, 1, 1, 1, 1, None)
-    assert e.value.code == _lib.NFS_EINVAL
+from tests.test_side_libraries_cpu import _built
 
 
 # (the pointers below are host memory that must never reach a kernel: with a device present a bug in the code under test

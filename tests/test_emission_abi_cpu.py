@@ -1,62 +1,17 @@
-"""The boundary of libnfs_emission.so without a GPU: it exports exactly what include/nfs_emission.h declares, the binding
-has the same names and routes to it, and every entry point refuses bad arguments before any launch."""
+"""The boundary of libnfs_emission.so without a GPU: the ops layer has its three forms and every entry point refuses bad
+arguments before any launch (what it exports, its version and the routing of its names: tests/test_side_libraries_cpu.py)."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"nfs_emission_version", "nfs_emission_fwd", "nfs_emission_bwd", "nfs_emission_bwd_adam"}
-
-
-def _built():
-    from neural_flow_style_amd import _lib
-    if not all(os.path.exists(p) for p in (_lib.LIB_PATH, _lib.EMISSION_LIB_PATH)):
-        _lib.build()
-    return _lib
-
-
-def _defined(path):
-    nm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else shutil.which("nm")
-    assert nm, "neither llvm-nm of the ROCm toolchain that built the library nor nm"
-    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.split()}
-    return {n for n in names if re.fullmatch(r"nfs_\w+", n)}
-
-
-def test_exported_symbols_equal_the_header():
-    _lib = _built()
-    hdr = open(os.path.join(ROOT, "include", "nfs_emission.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(nfs_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == NAMES
-    assert declared == set(_lib.EMISSION_SIGNATURES)
-    assert _defined(_lib.EMISSION_LIB_PATH) == declared
-    assert _lib.libemission().nfs_emission_version() == _lib.EMISSION_ABI_VERSION == 100
-
-
-def test_no_name_is_shared_with_another_library():
-    _lib = _built()
-    for other in (_lib.SIGNATURES, _lib.GRID2D_SIGNATURES, _lib.DESCENT_SIGNATURES, _lib.COLOUR_SIGNATURES):
-        assert not (set(other) & NAMES)
+from tests.test_side_libraries_cpu import _built
 
 
 def test_the_ops_layer_has_the_three_forms():
     from neural_flow_style_amd import engine, ops
     assert callable(ops.emission_fwd) and callable(ops.emission_bwd) and callable(ops.emission_bwd_adam)
     assert callable(engine.TFAdamState.step_through_emission)
-
-
-def test_the_binding_routes_a_call_to_the_fifth_library():
-    _lib = _built()
-    with pytest.raises(_lib.NfsError, match="nfs_emission_fwd: null pointer") as e:
-        _lib.call("nfs_emission_fwd", None, None, None, 1, 3, None)
-    assert e.value.code == _lib.NFS_EINVAL
 
 
 # (the pointers below are host memory that must never reach a kernel: with a device present a bug in the code under test

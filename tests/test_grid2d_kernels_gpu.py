@@ -181,7 +181,7 @@ def test_transport_step2d(ops, shape, C):
 # ---- 7: refusals ----------------------------------------------------------------------------------------------------------------------
 def test_refusals_write_nothing(ops):
     from neural_flow_style_amd import _lib
-    L, L0 = _lib.lib2d(), _lib.lib()           # (the error text is libnfs_hip.so's: one channel for both libraries)
+    L, L0 = _lib.side("grid2d"), _lib.lib()       # (the error text is libnfs_hip.so's: one channel for both libraries)
     SENT = 12345.0
     H, W = 4, 6
     n = H * W
