@@ -3,10 +3,11 @@
 include/nfs_hip.h is the only declaration of the C ABI: ``read_header`` derives the argtypes, the return types, the
 struct layouts, the NFS_E* codes and the ABI version from it at import time (no compiler, no library, no GPU).
 
-A side library is a key of ``SIDE``: libnfs_<key>.so beside the package, declared in include/nfs_<key>.h (read by the
-same ``read_header``), versioned by NFS_<KEY>_ABI_VERSION / nfs_<key>_version().  It links against libnfs_hip.so (one error
-channel, one HIP runtime).  ``SIDE`` holds one record per key, ``side(key)`` returns the loaded library, and ``call`` finds
-the library that owns a name.
+A side library is a key of ``SIDE`` or of ``SIDE_LATER``: libnfs_<key>.so beside the package, declared in
+include/nfs_<key>.h (read by the same ``read_header``), versioned by NFS_<KEY>_ABI_VERSION / nfs_<key>_version().  It links
+against libnfs_hip.so (one error channel, one HIP runtime).  The two tables hold one record per key (``SIDE`` the first five
+libraries, ``SIDE_LATER`` every one since: a new key goes there), ``side(key)`` returns the loaded library of a key of
+either, and ``call`` finds the library that owns a name.
 
 The HIP library is the product path: there is NO CPU fallback.  If the shared
 object is missing, importing an op raises immediately (``NfsLibraryError``).
@@ -145,7 +146,11 @@ def _owners(records):
 # (grid_variable 'c' of the grid-sequence stylizer); liquid: the ray weights of a liquid colour render (colour_render
 # 'liquid')
 SIDE = {k: SideLibrary(k) for k in ("grid2d", "descent", "colour", "emission", "liquid")}
-_OWNER = _owners(SIDE.values())
+# Two tables, one kind of record: tests/test_side_libraries_cpu.py pins SIDE to the five keys above (and each one's names),
+# so a library added since is a record of SIDE_LATER, built after SIDE and bound, owned and loaded in the same way.
+# absorb: the derivative of the liquid colour render in the density it is seen through (target_field 'pc')
+SIDE_LATER = {k: SideLibrary(k) for k in ("absorb",)}
+_OWNER = _owners(list(SIDE.values()) + list(SIDE_LATER.values()))
 _lib = None
 
 
@@ -203,7 +208,7 @@ def lib():
 
 def side(key):
     """libnfs_<key>.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
-    r = SIDE[key]
+    r = SIDE[key] if key in SIDE else SIDE_LATER[key]
     if r.handle is None:
         lib()
         r.handle = _open(os.path.basename(r.path), r.path, r.header_path, r.signatures, r.restypes, r.version_fn, r.abi)

@@ -18,6 +18,9 @@ grid path's learning rate, from ``lr_decay * lr`` at the first iteration of an o
 emission-absorption render over black, max-normalised; 'liquid': front-to-back alpha compositing over a background,
 include/nfs_liquid.h; default '') and ``--colour_background`` (three floats in [0,1], the liquid render's background;
 default 1 1 1), read by the two colour stylizers (styler_3p ``target_field 'c'``, styler_grid ``grid_variable 'c'``).
+``--target_field pc`` (styler_3p): positions and colours of a liquid in one variable, through ``--colour_render liquid``
+only; ``--colour_lr_scale`` (positive float, default 1, defaulted by ``complete()`` too): one optimiser step of ``lr``
+moves a colour of that variable by ``colour_lr_scale * lr``.
 """
 from __future__ import annotations
 
@@ -73,7 +76,7 @@ _FLAGS = [
     ("Render", "n_views", dict(type=int, default=9)),
     ("Render", "sample_type", dict(type=str, default="poisson", choices=["uniform", "poisson", "both"])),
     ("Render", "render_liquid", dict(type=str2bool, default=False)),
-    ("Optimizer", "target_field", dict(type=str, default="p", choices=["d", "p", "c"])),
+    ("Optimizer", "target_field", dict(type=str, default="p", choices=["d", "p", "c", "pc"])),
     ("Optimizer", "optimizer", dict(type=str, default="adam")),
     ("Optimizer", "iter", dict(type=int, default=20)),
     ("Optimizer", "lr", dict(type=float, default=0.0007)),
@@ -113,6 +116,7 @@ _FLAGS = [
     ("MI355X", "lap_n", dict(type=int, default=argparse.SUPPRESS)),
     ("MI355X", "colour_render", dict(type=str, default=argparse.SUPPRESS)),
     ("MI355X", "colour_background", dict(nargs=3, type=float, default=argparse.SUPPRESS)),
+    ("MI355X", "colour_lr_scale", dict(type=float, default=argparse.SUPPRESS)),
 ]
 
 COLOUR_RENDERS = ("", "smoke", "liquid")
@@ -168,7 +172,8 @@ def colour_background(background):
 
 def check_colour_render(config, colour):
     """the colour render's flags, checked where a stylizer is constructed, before a network is loaded (``colour``: the
-    stylizer's variable is a colour rendered through views -- styler_3p target_field 'c', styler_grid grid_variable 'c').
+    stylizer's variable is, or holds, a colour rendered through views -- styler_3p target_field 'c' and 'pc', styler_grid
+    grid_variable 'c').
     ValueError naming the flag for a ``colour_render`` outside '' / 'smoke' / 'liquid', for 'liquid' without a colour
     variable, and for a ``colour_background`` that is not three numbers in [0,1].  -> (render, background)"""
     render = getattr(config, "colour_render", "")
@@ -209,5 +214,7 @@ def complete(config):
         config.colour_render = ""
     if not hasattr(config, "colour_background"):
         config.colour_background = [1.0, 1.0, 1.0]
+    if not hasattr(config, "colour_lr_scale"):
+        config.colour_lr_scale = 1.0
 
     return config

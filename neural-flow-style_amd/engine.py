@@ -1542,7 +1542,15 @@ class ColourRenderLoss(object):
     tau, so the 'coef' route's bound max |g| max w on the sample gradient (``ops.colour_project_bwd``,
     nfs_rotate_bwd_coef in nfs_hip.h) holds as it does for T / M.  On the particle path d is smoothed by ``k`` and the
     emission q is not (as in the smoke mode), so rotate(q) / S can exceed the particles' colour there and the clip takes
-    what is above 1; smoothing the emission is not built."""
+    what is above 1; smoothing the emission is not built.
+
+    ``loss_and_grad(..., absorb=True)`` (liquid render, no ``style_mask``; include/nfs_absorb.h) also returns the gradient
+    in the volume d given to ``prepare`` with q held constant -- the joint variable of target_field 'pc', where d moves
+    with the particles.  It is formed after the projection's transpose, which needs the weights: ``ops.liquid_absorb_bwd``
+    writes g_S over ``ctx["w"]`` and ``ops.rotate_bwd`` (tiled, bit-reproducible) takes it to d, so the context is SPENT
+    afterwards (``ctx["spent"]``; a second call with it raises).  Two cases are refused with a ValueError: the smoke
+    render, whose maximum M couples every ray (its adjoint in the density is not built), and ``style_mask``, whose mask
+    1 - t would depend on the variable (the gradient through it is not built)."""
 
     RENDERS = COLOUR_RENDERS
 
@@ -1562,11 +1570,11 @@ class ColourRenderLoss(object):
             self._bg_dev = torch.tensor(self.background, dtype=torch.float32, device=d3.device)
         bg_img = (t.unsqueeze(-1) * self._bg_dev).contiguous()
         return {"rot": rot, "w": w, "grey": grey, "gmax": None, "d_gray": grey.unsqueeze(-1).contiguous(), "t_total": t,
-                "bg_img": bg_img}
+                "bg_img": bg_img, "d3": d3}
 
     def prepare(self, d3, rot):
         """d3 [D,H,W], rot [V,3,3] -> the frame's context: ray weights w [V,D,H,W], the grey image, d_gray [V,H,W,1]
-        (liquid: also t_total [V,H,W] and bg_img [V,H,W,3])"""
+        (liquid: also t_total [V,H,W], bg_img [V,H,W,3] and ``d3`` itself, for ``loss_and_grad(absorb=True)``)"""
         if self.liquid:
             return self._prepare_liquid(d3, rot)
         V = int(rot.shape[0])
@@ -1588,8 +1596,20 @@ class ColourRenderLoss(object):
             J += ctx["bg_img"]                           # (t bg: one small add per step)
         return J, torch.clamp(J, 0, 1)
 
-    def loss_and_grad(self, q, ctx, route=None):
-        """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3]); ``route``: the transpose's (``ops.colour_project_bwd``; None: by size)"""
+    def loss_and_grad(self, q, ctx, route=None, absorb=False):
+        """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3]); ``route``: the transpose's (``ops.colour_project_bwd``; None: by size).
+        ``absorb``: -> (losses, g_q, g_d [D,H,W]), g_d the gradient in the volume ``prepare`` was given (liquid render
+        without style_mask only); the context's weights are overwritten and the context marked spent"""
+        if absorb:
+            if not self.liquid:
+                raise ValueError("absorb=True on the smoke colour render: the maximum M of w = T / M couples every ray and "
+                                 "its adjoint in the density is not built (use colour_render 'liquid')")
+            if self.image_loss.style_mask:
+                raise ValueError("absorb=True with style_mask: the mask 1 - t would depend on the density and the gradient "
+                                 "through it is not built (pass style_mask false)")
+        if ctx.get("spent"):
+            raise ValueError("this colour context is spent: loss_and_grad(absorb=True) overwrote its ray weights (prepare "
+                             "a new one)")
         J, img = self.project(q, ctx)
         V = J.shape[0]
         losses, grads = [], []
@@ -1599,7 +1619,14 @@ class ColourRenderLoss(object):
         g_img = grads[0] if len(grads) == 1 else torch.cat(grads, 0)
         g_J = ops.clamp01_bwd(g_img.contiguous(), J)
         g_q = ops.colour_project_bwd(g_J, ctx["rot"], ctx["w"], route=route)
-        return (losses[0] if len(losses) == 1 else torch.cat(losses, 0)), g_q
+        losses = losses[0] if len(losses) == 1 else torch.cat(losses, 0)
+        if not absorb:
+            return losses, g_q
+        ctx["spent"] = True                              # (the weights are dead from here on: g_S goes over them)
+        g_S = ops.liquid_absorb_bwd(g_J, q, ctx["d3"], ctx["rot"], ctx["w"], ctx["t_total"], self._bg_dev[:q.shape[-1]],
+                                    self.tau, out=ctx["w"])
+        g_d = ops.rotate_bwd(g_S.unsqueeze(-1), ctx["rot"], tiled=True).squeeze(-1)
+        return losses, g_q, g_d
 
     def d_img(self, q, ctx):
         """the 0..255 image the loss network sees, [V,H',W',3] (float32: uint8-ready)"""

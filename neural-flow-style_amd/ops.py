@@ -927,6 +927,29 @@ def liquid_weights(d, rot, tau, w=None, grey=None, t_total=None):
     return w, grey, t_total
 
 
+# ---- the liquid colour render's derivative in the density (include/nfs_absorb.h) -------------------------------------
+
+def liquid_absorb_bwd(g_J, q, d, rot, w, t_total, bg, tau, out=None):
+    """g_J [V,H,W,C], q [D,H,W,C] (C in 1..4), d [D,H,W], rot [V,3,3], w [V,D,H,W] and t_total [V,H,W] as
+    ``liquid_weights`` wrote them, bg [C] (device) -> g_S [V,D,H,W] = d loss / d rotate(d) of J = sum_z w rotate(q) + t bg
+    with q held constant (``rotate_bwd`` of it is the gradient in d).  ``out`` may be ``w`` itself: the weights are then
+    overwritten."""
+    D, H, W = d.shape
+    V, C = int(rot.shape[0]), int(q.shape[-1])
+    if tuple(q.shape) != (D, H, W, C) or tuple(g_J.shape) != (V, H, W, C) or tuple(w.shape) != (V, D, H, W) \
+            or tuple(t_total.shape) != (V, H, W) or int(bg.numel()) != C:
+        raise ValueError("liquid_absorb_bwd: g_J %s, q %s, w %s, t_total %s, bg %s do not fit d %s through %d views"
+                         % (tuple(g_J.shape), tuple(q.shape), tuple(w.shape), tuple(t_total.shape), tuple(bg.shape),
+                            tuple(d.shape), V))
+    if out is None:
+        out = _empty((V, D, H, W), d)
+    assert tuple(out.shape) == (V, D, H, W)
+    _lib.call("nfs_liquid_absorb_bwd", _ptr(g_J), _ptr(q), _ptr(d), _ptr(rot), _ptr(w), _ptr(t_total), _ptr(bg), float(tau),
+              _ptr(out), V, D, H, W, C, _stream())
+    _written(out)
+    return out
+
+
 # ---- the emission of a colour grid (include/nfs_emission.h) -----------------------------------------------------------
 
 def _emission_dims(c, e):

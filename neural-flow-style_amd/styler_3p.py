@@ -14,6 +14,14 @@ Forward graph per frame (styler_3p.py:42-164):
        clip(sum_z w rotate(q) + t bg, 0, 1), front-to-back alpha compositing over ``--colour_background`` (w, t:
        include/nfs_liquid.h); 'r' and 'd_intm' are then over the background.  The grey volume is smoothed by k and q is
        not, so rotate(q) / rotate(d) can exceed the particles' colour and the clip takes it
+  'pc': positions AND colours of a liquid in one variable [N,6] = (v, c / colour_lr_scale) (build extension, DESIGN.md
+       section 8): the grey field of 'p' at p + v absorbs, q = p2g(p + v, pc=clip(c,0,1), pd=r) emits, the image is the
+       liquid colour render's (``--colour_render liquid`` only).  The geometry moves, so nothing of a frame is kept across
+       steps but its densities r and the splat configurations: an evaluation forms the ray weights, and
+       ``engine.ColourRenderLoss.loss_and_grad(absorb=True)`` returns the gradient in the emission AND in the absorbing
+       volume (include/nfs_absorb.h); both reach the positions through the splat's adjoint.  One optimiser step of ``lr``
+       moves a colour by ``colour_lr_scale * lr``.  ``w_pressure`` acts as for 'p'; ``style_mask`` and the smoke colour
+       render are refused (the mask and the maximum would depend on the variable)
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -61,10 +69,13 @@ class _SmoothRelu(torch.autograd.Function):
 
 class Styler(StylerBase):
     _colour = False                                  # target_field 'c' (set by the constructor)
+    _joint = False                                   # target_field 'pc' (set by the constructor)
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
-        check_colour_render(self_dict, colour=getattr(self_dict, "target_field", "") == "c")
+        check_colour_render(self_dict, colour=getattr(self_dict, "target_field", "") in ("c", "pc"))
+        if getattr(self_dict, "target_field", "") == "pc":
+            self._check_joint(self_dict)
         if getattr(self_dict, "target_field", "") == "c":
             # the colour path renders by emission-absorption only and has no auxiliary field terms (refused before the
             # base class loads a network)
@@ -86,6 +97,7 @@ class Styler(StylerBase):
         StylerBase.__init__(self, self_dict)
         assert self.batch_size == 1, "batch_size > 1 is not supported (see module docstring)"
         self._colour = self.target_field == "c"
+        self._joint = self.target_field == "pc"
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -95,8 +107,8 @@ class Styler(StylerBase):
             print("# vps:", self.n_views)
             assert self.n_views % self.v_batch == 0
         # one loss chain per stylizer: the grey render's, or for 'c' the colour render's around an image loss
-        self.loss = None if self._colour else self._make_loss(rotate=self.rotate)
-        self.colour = self._make_colour_loss() if self._colour else None
+        self.loss = None if (self._colour or self._joint) else self._make_loss(rotate=self.rotate)
+        self.colour = self._make_colour_loss() if (self._colour or self._joint) else None
         self._graph_loss = None                      # engine.GraphedLoss, decided at the first loss call
         self._identity = T.rot_to_device([np.identity(3)], self.device)
         # multi-GPU (set by the driver): ``pg`` = the process group; ``shard_by`` = 'views' (views=sum: the views of every
@@ -105,6 +117,35 @@ class Styler(StylerBase):
         # exchange is the halo of per-frame updates the temporal filter reaches, point-to-point)
         self.pg = None
         self.shard_by = getattr(self, "shard_by", None) or "views"
+
+    @staticmethod
+    def _check_joint(cfg):
+        """the refusals of target_field 'pc', before the base class loads a network: a ValueError naming the flag"""
+        if (getattr(cfg, "colour_render", "") or "") != "liquid":
+            raise ValueError("target_field 'pc': colour_render %r -- the joint variable moves the density, and only the "
+                             "liquid colour render has an adjoint in it: the smoke render's maximum couples every ray "
+                             "(pass --colour_render liquid)" % (getattr(cfg, "colour_render", ""),))
+        if getattr(cfg, "style_mask", False):
+            raise ValueError("target_field 'pc': style_mask -- the mask 1 - t would depend on the variable and the "
+                             "gradient through it is not built (pass --style_mask false)")
+        if getattr(cfg, "render_liquid", False):
+            raise ValueError("target_field 'pc': render_liquid is the grey liquid render and is not built for the colour "
+                             "render (pass --render_liquid false; the liquid colour render is --colour_render liquid)")
+        if getattr(cfg, "ray_mode", ""):
+            raise ValueError("target_field 'pc': ray_mode %r is not built for the colour render (leave --ray_mode empty)"
+                             % (cfg.ray_mode,))
+        if (getattr(cfg, "w_density", 0) or 0) > 0:
+            raise ValueError("target_field 'pc': w_density acts on the density variable (pass --w_density 0)")
+        if getattr(cfg, "style_mask_on_ref", False):
+            raise ValueError("target_field 'pc': style_mask_on_ref is not built for the colour render (pass "
+                             "--style_mask_on_ref false)")
+        if getattr(cfg, "pg", None) is not None:
+            raise ValueError("target_field 'pc' over a process group (pg): sharding the colour path over ranks is not "
+                             "built (run it on one GPU)")
+        scale = getattr(cfg, "colour_lr_scale", 1.0)
+        if not float(1.0 if scale is None else scale) > 0:
+            raise ValueError("--colour_lr_scale %r: the step of a colour relative to a displacement must be positive"
+                             % (scale,))
 
     def _make_colour_loss(self):
         w_layers = list(self.w_style_layer)
@@ -182,6 +223,63 @@ class Styler(StylerBase):
         if not views_only:
             self._cframes = {}
 
+    # ---- the joint path (target_field 'pc'): the geometry moves, nothing but r and the splat cfgs outlives a call ----
+    def _joint_cfgs(self, res):
+        cfgs = self.__dict__.setdefault("_jcfgs", {})
+        key = tuple(res)
+        if key not in cfgs:
+            mk = lambda rho, mode: ops.make_splat_cfg(3, list(res), list(self.domain), self.radius, self.support, rho,
+                                                      self.nsize, self.clip, mode)
+            cfgs[key] = (mk(1.0, 0), mk(self.rest_density, 1))     # (unit rest density: d / rest_density, as _field)
+        return cfgs[key]
+
+    def _joint_forward(self, p, r, var, res):
+        """positions x = p + v in their grid order o, the raw and the smoothed grey volume, the clamped colours in that
+        order and the emission q; var [N,6] = (v, c / colour_lr_scale)"""
+        cfg_d, cfg_q = self._joint_cfgs(res)
+        x = p + var[:, 0:3]
+        order = self._particle_order(p, x.unsqueeze(0))
+        xo = (x if order is None else x[order]).contiguous()
+        ro = (r if order is None else r[order]).reshape(-1).contiguous()
+        c = (var[:, 3:6] * float(self.colour_lr_scale)).contiguous()
+        d_raw = ops.p2g_fwd(xo, cfg_d)[..., 0].contiguous()
+        e = ops.smooth3d_relu_fwd(d_raw, float(self.k) if self.k > 0 else 0.0)
+        cc = ops.colour_clamp_gather(c, order)
+        q = ops.p2g_fwd(xo, cfg_q, attr=cc, pd=ro)
+        return dict(x=x, order=order, xo=xo, ro=ro, c=c, d_raw=d_raw, e=e, cc=cc, q=q, cfg_d=cfg_d, cfg_q=cfg_q)
+
+    def _joint_value_and_grad(self, p, r, var, res, rot):
+        """per-view losses and d loss / d var [N,6] of one frame on the C-ABI operators: splats -> smoothing -> liquid
+        weights -> ColourRenderLoss(absorb=True) -> smoothing adjoint -> the two splat adjoints -> clamp adjoint"""
+        s = float(self.colour_lr_scale)
+        f = self._joint_forward(p, r, var.contiguous(), res)
+        ctx = self.colour.prepare(f["e"], rot)
+        losses, g_q, g_e = self.colour.loss_and_grad(f["q"], ctx, absorb=True)
+        g_raw = ops.smooth3d_relu_bwd(f["e"], g_e.contiguous(), float(self.k) if self.k > 0 else 0.0)
+        if self.w_pressure > 0:
+            # the mean over ALL voxels of (d_raw - 1)^2 where d_raw > 0, as _field forms it (styler_base.py:228-230)
+            d_raw = f["d_raw"]
+            pressure = torch.where(d_raw > 0, d_raw - 1, torch.zeros_like(d_raw))
+            losses = losses + (pressure ** 2).mean() * self.w_pressure / losses.numel()
+            g_raw = g_raw + pressure * (2.0 * self.w_pressure / d_raw.numel())
+        g_x, g_cc, _ = ops.p2g_bwd(f["xo"], f["cfg_q"], g_q.contiguous(), attr=f["cc"], pd=f["ro"], need_p=True,
+                                   need_attr=True)
+        g_xd, _, _ = ops.p2g_bwd(f["xo"], f["cfg_d"], g_raw.unsqueeze(-1).contiguous(), need_p=True)
+        g_x = g_x + g_xd
+        g = torch.empty_like(var)
+        if f["order"] is None:
+            g[:, 0:3] = g_x
+        else:
+            g[f["order"], 0:3] = g_x
+        g_c = ops.colour_clamp_scatter_bwd(g_cc, f["c"], f["order"])
+        g[:, 3:6] = g_c if s == 1.0 else g_c * s
+        return losses, g
+
+    def _joint_d_img(self, p, r, var, res):
+        """the colour image at the identity view, [1,H',W',3] 0..255 (over the background)"""
+        f = self._joint_forward(p, r, var.contiguous(), res)
+        return self.colour.d_img(f["q"], self.colour.prepare(f["e"], self._identity))
+
     # ---- forward graph: variable -> d_out [1,D,H,W,1] (autograd) ---------------------------------
     def _field(self, p, r, var, res):
         """p [N,3], r [N,nk] device tensors; var = the optimised tensor ([N,3] or [N,nk]).
@@ -191,7 +289,7 @@ class Styler(StylerBase):
         extra = None
         p_ = p.unsqueeze(0)
         if "p" in self.target_field:
-            p_ = p_ + var.unsqueeze(0)
+            p_ = p_ + (var[:, 0:3] if self._joint else var).unsqueeze(0)     # ('pc': the displacement columns)
         p_all = p_                                   # ('c': the positions as they came; var is not read)
         # a sequence keeps ONE particle order for all frames (frame 0's: the temporal filter needs particle i to be the
         # same particle everywhere), so by frame 60 of a flowing liquid the neighbours of that order have dispersed and
@@ -257,6 +355,8 @@ class Styler(StylerBase):
         ranks of ``self.pg`` (then only rank 0 adds the view-independent terms)"""
         if self._colour:
             return self._colour_value_and_grad(p, r, var, res, rot if (self.rotate and rot is not None) else self._identity)
+        if self._joint:
+            return self._joint_value_and_grad(p, r, var, res, rot if (self.rotate and rot is not None) else self._identity)
         v = var.detach().clone().requires_grad_(True)
         _, d_out, extra = self._field(p, r, v, res)
         d3 = d_out.detach().reshape(d_out.shape[1:4]).contiguous()
@@ -319,6 +419,14 @@ class Styler(StylerBase):
                 imgs.append(dimg[0].cpu().numpy().astype(np.uint8))
                 self._colour_reset()
                 continue
+            if self._joint:
+                r = torch.full((n, 1), float(self.rest_density), device=self.device)
+                var = torch.zeros(n, 6, device=self.device)
+                var[:, 3:6] = 0.5 / float(self.colour_lr_scale)
+                with torch.no_grad():
+                    dimg = self._joint_d_img(p, r, var, list(self.resolution))
+                imgs.append(dimg[0].cpu().numpy().astype(np.uint8))
+                continue
             r = self._dev(params["r"][t]) if "d" in self.target_field else None
             var = torch.zeros(n, 3 if "p" in self.target_field else self.num_kernels, device=self.device)
             with torch.no_grad():
@@ -329,9 +437,9 @@ class Styler(StylerBase):
 
     # ---- the optimisation loop (styler_3p.py:229-439) ----------------------------------------------
     def run(self, params):
-        if self._colour and self.pg is not None:
-            raise ValueError("target_field 'c' over a process group: sharding the colour path over ranks is not built "
-                             "(run it on one GPU)")
+        if (self._colour or self._joint) and self.pg is not None:
+            raise ValueError("target_field %r over a process group: sharding the colour path over ranks is not built "
+                             "(run it on one GPU)" % (self.target_field,))
         if abs(self.lr_scale - 1) > 1e-7 and not isinstance(self.lr, list):
             self.lr = [self.lr / self.lr_scale ** i for i in range(self.octave_n)]
 
@@ -346,7 +454,7 @@ class Styler(StylerBase):
         p = [self._dev(x) for x in params["p"]]
         r = [self._dev(x) for x in params["r"]] if "d" in self.target_field else [None] * self.num_frames
         c_init = None
-        if self._colour:
+        if self._colour or self._joint:
             # per-particle densities [N,1] (the first kernel's column; rest_density where the frames carry none) and the
             # colour start: noise around the VGG mean / 255 (styler_2p.py:189-192) unless the caller brings one
             if params.get("r") is not None:
@@ -360,7 +468,8 @@ class Styler(StylerBase):
                 c_init = self.rng.uniform(-5, 5, [self.num_frames, p[0].shape[0], 3]).astype(np.float32)
                 c_init += np.array([vggmod._R_MEAN, vggmod._G_MEAN, vggmod._B_MEAN], np.float32)
                 c_init /= 255
-            self._colour_reset()
+            if self._colour:
+                self._colour_reset()
         # Particles in grid-cell order (one permutation for all frames, from the first frame's positions: the temporal
         # filter and the frame interpolation need particle i to be the same particle in every frame).  A block of
         # consecutive particles then touches a small box of cells and the splat accumulates it in LDS
@@ -378,12 +487,17 @@ class Styler(StylerBase):
             for x in p[1:]:                                  # (frame 0 is in its own order already)
                 if x.shape[0] > 1:
                     self._orders[(x.data_ptr(), x.shape[0])] = T.grid_order(x, self.resolution)
-        nvar = 3 if ("p" in self.target_field or self._colour) else self.num_kernels
+        nvar = 6 if self._joint else 3 if ("p" in self.target_field or self._colour) else self.num_kernels
         g_opt = [torch.zeros(p[i].shape[0], nvar, device=self.device) for i in range(self.num_frames)]
         if self._colour:
             g_opt = [self._dev(c_init[i]) for i in range(self.num_frames)]
             if inv is not None:
                 g_opt = [g[perm].contiguous() for g in g_opt]
+        if self._joint:
+            # (v, c / colour_lr_scale): the displacements start at zero, the colours as for 'c'
+            for i in range(self.num_frames):
+                c0 = self._dev(c_init[i])
+                g_opt[i][:, 3:6] = (c0 if inv is None else c0[perm]) / float(self.colour_lr_scale)
         mode = getattr(self, "views_mode", "sequential")
         if getattr(self, "optimizer", "adam") == "lbfgs" and self.rotate and mode == "sequential" \
                 and self.n_views > self.v_batch:
@@ -432,7 +546,7 @@ class Styler(StylerBase):
         for octave in range(self.octave_n):
             loss_history_o, d_intm_o = [], []
             res = [int(v) for v in oct_size[octave]]
-            loss_net = self.colour.image_loss if self._colour else self.loss       # (who holds the image targets)
+            loss_net = self.colour.image_loss if (self._colour or self._joint) else self.loss   # (who holds the image targets)
             if self.style_img is not None:
                 loss_net.set_style_image(self._style_feature(self.style_img, res[1:]))
                 if getattr(self, "w_hist", 0) > 0:                # styler_3p.py:288-293
@@ -499,6 +613,8 @@ class Styler(StylerBase):
                         with torch.no_grad():
                             if self._colour:
                                 dimg = self._colour_d_img(p[t], r[t], var, res)
+                            elif self._joint:
+                                dimg = self._joint_d_img(p[t], r[t], var, res)
                             else:
                                 _, d_out, _ = self._field(p[t], r[t], var, res)
                                 dimg = self.loss_d_img(d_out)
@@ -546,10 +662,12 @@ class Styler(StylerBase):
         for t in range(self.num_frames):
             with torch.no_grad():
                 p_out, d_out, _ = self._field(p[t], r[t], g_opt[t], res)
-                dimg = self._colour_d_img(p[t], r[t], g_opt[t], res) if self._colour else self.loss_d_img(d_out)
+                dimg = self._colour_d_img(p[t], r[t], g_opt[t], res) if self._colour else \
+                    self._joint_d_img(p[t], r[t], g_opt[t], res) if self._joint else self.loss_d_img(d_out)
             p_sty.append((p_out if inv is None else p_out[inv]).cpu().numpy())
             if "p" in self.target_field:
-                v_sty.append((g_opt[t] if inv is None else g_opt[t][inv]).cpu().numpy())
+                v_t = g_opt[t][:, 0:3] if self._joint else g_opt[t]
+                v_sty.append((v_t if inv is None else v_t[inv]).cpu().numpy())
             d_sty.append(torch.abs(d_out[0]).cpu().numpy())      # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
         result["p"] = p_sty
@@ -557,13 +675,19 @@ class Styler(StylerBase):
             result["v"] = v_sty
         result["d"] = np.array(d_sty)
         result["r"] = np.array(r_sty)
+        if self._joint:
+            # 'opt' in natural units: (v, c), the colour columns times colour_lr_scale
+            unit = torch.tensor([1.0] * 3 + [float(self.colour_lr_scale)] * 3, device=self.device)
+            g_opt = [g * unit for g in g_opt]
         result["opt"] = [(g if inv is None else g[inv]).cpu().numpy() for g in g_opt]   # build extension: the variables
-        if self._colour:
+        if self._colour or self._joint:
             # the colours as styler_2p returns them: clipped, and faded by the particle's density (styler_2p.py:297-300)
-            result["c"] = [((torch.clamp(g_opt[t], 0, 1) * torch.clamp(r[t] / self.rest_density, 0, 1))
+            cols = [g[:, 3:6] if self._joint else g for g in g_opt]
+            result["c"] = [((torch.clamp(cols[t], 0, 1) * torch.clamp(r[t] / self.rest_density, 0, 1))
                             [slice(None) if inv is None else inv]).cpu().numpy() for t in range(self.num_frames)]
             result["c_init"] = c_init
-            self._colour_reset()
+            if self._colour:
+                self._colour_reset()
         self._orders, self._order_age = {}, {}   # keyed by device address: the frame tensors die with this call
         return result
 
