@@ -3,11 +3,11 @@
 include/nfs_hip.h is the only declaration of the C ABI: ``read_header`` derives the argtypes, the return types, the
 struct layouts, the NFS_E* codes and the ABI version from it at import time (no compiler, no library, no GPU).
 
-A side library is a key of ``SIDE`` or of ``SIDE_LATER``: libnfs_<key>.so beside the package, declared in
+A side library is a key of ``SIDE``, of ``SIDE_LATER`` or of ``SIDE_OPEN``: libnfs_<key>.so beside the package, declared in
 include/nfs_<key>.h (read by the same ``read_header``), versioned by NFS_<KEY>_ABI_VERSION / nfs_<key>_version().  It links
-against libnfs_hip.so (one error channel, one HIP runtime).  The two tables hold one record per key (``SIDE`` the first five
-libraries, ``SIDE_LATER`` every one since: a new key goes there), ``side(key)`` returns the loaded library of a key of
-either, and ``call`` finds the library that owns a name.
+against libnfs_hip.so (one error channel, one HIP runtime).  The three tables hold one record per key (``SIDE`` the first five
+libraries, ``SIDE_LATER`` the sixth, ``SIDE_OPEN`` every one since: a new key goes THERE, and no test pins what that table
+holds), ``side(key)`` returns the loaded library of a key of any of them, and ``call`` finds the library that owns a name.
 
 The HIP library is the product path: there is NO CPU fallback.  If the shared
 object is missing, importing an op raises immediately (``NfsLibraryError``).
@@ -151,6 +151,24 @@ SIDE = {k: SideLibrary(k) for k in ("grid2d", "descent", "colour", "emission", "
 # absorb: the derivative of the liquid colour render in the density it is seen through (target_field 'pc')
 SIDE_LATER = {k: SideLibrary(k) for k in ("absorb",)}
 _OWNER = _owners(list(SIDE.values()) + list(SIDE_LATER.values()))
+# THE OPEN TABLE: tests pin SIDE_LATER to ["absorb"] and the names of _OWNER to those six libraries, so every library added
+# since is a record here -- append the key; nothing else in this file changes, and no test may assert what this table holds
+# as a whole (only that its own key is in it and bound).  Its names are a second lookup that call() consults after _OWNER.
+# exposure: the smoke colour render at a fixed exposure and its derivative in the density (colour_render 'exposure')
+SIDE_OPEN = {k: SideLibrary(k) for k in ("exposure",)}
+
+
+def _owners_open(records, taken):
+    """``_owners`` of the open table; a name that ``taken`` (the names of the two closed tables) holds raises as well"""
+    owners = _owners(records)
+    for name, r in owners.items():
+        if name in taken:
+            raise NfsLibraryError("%s declares %s, which %s declares too: call() could not tell whose it is"
+                                  % (r.header_path, name, taken[name].header_path))
+    return owners
+
+
+_OWNER_OPEN = _owners_open(list(SIDE_OPEN.values()), _OWNER)
 _lib = None
 
 
@@ -208,7 +226,7 @@ def lib():
 
 def side(key):
     """libnfs_<key>.so, loaded after libnfs_hip.so (it links against it: one error channel, one HIP runtime)"""
-    r = SIDE[key] if key in SIDE else SIDE_LATER[key]
+    r = SIDE[key] if key in SIDE else SIDE_LATER[key] if key in SIDE_LATER else SIDE_OPEN[key]
     if r.handle is None:
         lib()
         r.handle = _open(os.path.basename(r.path), r.path, r.header_path, r.signatures, r.restypes, r.version_fn, r.abi)
@@ -225,7 +243,7 @@ PROFILE = None
 def call(name, *args):
     """Call an int-returning entry point; raise with nfs_last_error() on failure."""
     L0 = lib()                       # (the error text stays libnfs_hip.so's: the libraries share nfs::set_error)
-    r = _OWNER.get(name)
+    r = _OWNER.get(name) or _OWNER_OPEN.get(name)
     L = L0 if r is None else side(r.key)
     if PROFILE is not None:
         import torch

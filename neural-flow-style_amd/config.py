@@ -16,11 +16,12 @@ grid path's learning rate, from ``lr_decay * lr`` at the first iteration of an o
 ``--lr_decay`` (float, default 1) and ``--lap_n`` (int, default 3) are parsed when given and otherwise defaulted by
 ``complete()``, like the attributes the drivers inject.  So are ``--colour_render`` ('' / 'smoke': the colour paths'
 emission-absorption render over black, max-normalised; 'liquid': front-to-back alpha compositing over a background,
-include/nfs_liquid.h; default '') and ``--colour_background`` (three floats in [0,1], the liquid render's background;
+include/nfs_liquid.h; 'exposure': the smoke model at a fixed exposure ``--colour_exposure`` (positive float, default 1) with
+no maximum, include/nfs_exposure.h; default '') and ``--colour_background`` (three floats in [0,1], the liquid render's background;
 default 1 1 1), read by the two colour stylizers (styler_3p ``target_field 'c'``, styler_grid ``grid_variable 'c'``).
-``--target_field pc`` (styler_3p): positions and colours of a liquid in one variable, through ``--colour_render liquid``
-only; ``--colour_lr_scale`` (positive float, default 1, defaulted by ``complete()`` too): one optimiser step of ``lr``
-moves a colour of that variable by ``colour_lr_scale * lr``.
+``--target_field pc`` (styler_3p): positions and colours in one variable, of a liquid through ``--colour_render liquid`` or
+of smoke through ``--colour_render exposure``; ``--colour_lr_scale`` (positive float, default 1, defaulted by
+``complete()`` too): one optimiser step of ``lr`` moves a colour of that variable by ``colour_lr_scale * lr``.
 """
 from __future__ import annotations
 
@@ -117,9 +118,10 @@ _FLAGS = [
     ("MI355X", "colour_render", dict(type=str, default=argparse.SUPPRESS)),
     ("MI355X", "colour_background", dict(nargs=3, type=float, default=argparse.SUPPRESS)),
     ("MI355X", "colour_lr_scale", dict(type=float, default=argparse.SUPPRESS)),
+    ("MI355X", "colour_exposure", dict(type=float, default=argparse.SUPPRESS)),
 ]
 
-COLOUR_RENDERS = ("", "smoke", "liquid")
+COLOUR_RENDERS = ("", "smoke", "liquid", "exposure")
 
 
 def make_parser():
@@ -170,17 +172,36 @@ def colour_background(background):
     return bg
 
 
+def colour_exposure(exposure):
+    """``colour_exposure`` as a finite positive float, or a ValueError naming the flag (None: the default 1)"""
+    try:
+        k = float(1.0 if exposure is None else exposure)
+    except (TypeError, ValueError):
+        k = float("nan")
+    if not (0.0 < k < float("inf")):
+        raise ValueError("--colour_exposure %r: the exposure of colour_render 'exposure' must be finite and positive"
+                         % (exposure,))
+    return k
+
+
 def check_colour_render(config, colour):
     """the colour render's flags, checked where a stylizer is constructed, before a network is loaded (``colour``: the
     stylizer's variable is, or holds, a colour rendered through views -- styler_3p target_field 'c' and 'pc', styler_grid
     grid_variable 'c').
-    ValueError naming the flag for a ``colour_render`` outside '' / 'smoke' / 'liquid', for 'liquid' without a colour
-    variable, and for a ``colour_background`` that is not three numbers in [0,1].  -> (render, background)"""
+    ValueError naming the flag for a ``colour_render`` outside '' / 'smoke' / 'liquid' / 'exposure', for 'liquid' or
+    'exposure' without a colour variable, for a ``colour_background`` that is not three numbers in [0,1] and for a
+    ``colour_exposure`` that is not finite and positive (both whatever the render is).  -> (render, background); the
+    exposure is ``colour_exposure(config.colour_exposure)``"""
     render = getattr(config, "colour_render", "")
     render = "" if render is None else render
     if render not in COLOUR_RENDERS:
         raise ValueError("--colour_render %r is none of %s" % (render, COLOUR_RENDERS))
     bg = colour_background(getattr(config, "colour_background", (1.0, 1.0, 1.0)))
+    colour_exposure(getattr(config, "colour_exposure", 1.0))
+    if render == "exposure" and not colour:
+        raise ValueError("--colour_render exposure (--colour_exposure) without a colour variable: the fixed-exposure colour "
+                         "render belongs to --target_field c / pc of the 3-D particle stylizer and --grid_variable c of the "
+                         "grid stylizer")
     if render == "liquid" and not colour:
         raise ValueError("--colour_render liquid without a colour variable: the liquid colour render belongs to "
                          "--target_field c of the 3-D particle stylizer and --grid_variable c of the grid stylizer (the "
@@ -216,5 +237,7 @@ def complete(config):
         config.colour_background = [1.0, 1.0, 1.0]
     if not hasattr(config, "colour_lr_scale"):
         config.colour_lr_scale = 1.0
+    if not hasattr(config, "colour_exposure"):
+        config.colour_exposure = 1.0
 
     return config

@@ -5,7 +5,8 @@
 //                              P = sum_{z'' < z} a w,  S = rotate(d, R_v) and Q = rotate(q, R_v) gathered on the fly
 // The twin of liquid_weights_kernel: one lane per ray, a wave on 64 consecutive x of one (view, row), but NEAR end first
 // (z = 0 upwards: what lies in front of a sample is what its weight is seen through), P in a register.  One stencil per
-// sample (ray_coords, axis_setup) gathers the sample of d and the C channels of q: as x-pairs where W >= 2 (an 8-byte load
+// sample (ray_sample_pairs / ray_sample_scalar of ray_gather.h, which exposure.hip takes without the density; ray_coords,
+// axis_setup) gathers the sample of d and the C channels of q: as x-pairs where W >= 2 (an 8-byte load
 // of d and one load of 2 C floats of q per (z, y) corner pair; four samples' gathers issued before any is consumed), and
 // through tri_setup and scalar loads where W == 1.  The only [V,D,H,W] traffic is w read and g_s written (a z step of a wave
 // moves 256 contiguous bytes each way); nothing of size [V,D,H,W,C] exists.  No LDS, no atomics.  g_s may be the buffer w
@@ -29,6 +30,7 @@
 // 64-bit; axis_setup clamps every corner into the volume whatever the matrix is (also for NaN coordinates), and a pair load
 // reads x = min(i0, W - 2) and its neighbour.
 #include "common.h"
+#include "ray_gather.h"
 #include "../../include/nfs_absorb.h"
 
 namespace nfs {
@@ -43,72 +45,6 @@ __device__ __forceinline__ float liquid_psi(float x) {
   }
   if (x >= PSI_TAIL_FROM) return -1.f / x;
   return 1.f / expm1f(x) - 1.f / x;
-}
-
-template <int N>
-struct __attribute__((packed, aligned(4))) FNu { float v[N]; };
-
-// one sample of the march: s = trilinear(d), a = sum_c g[c] trilinear(q[..., c]), both from one stencil
-template <int C>
-__device__ __forceinline__ void absorb_sample_pairs(const float* __restrict__ d, const float* __restrict__ q,
-                                                    const float* r, const float* g, int D, int H, int W, int z, int h,
-                                                    int x, float& s, float& a) {
-  float cx, cy, cz;
-  ray_coords(r, D, H, W, z, h, x, cx, cy, cz);
-  const Axis az = axis_setup(cx, D), ay = axis_setup(cy, H), ax = axis_setup(cz, W);
-  const int xb = min(ax.i0, W - 2);                 // pair base; clamped stencils select below
-  const bool x0_lo = ax.i0 == xb, x1_lo = ax.i1 == xb;
-  const float wz[2] = {1.f - az.w1, az.w1}, wy[2] = {1.f - ay.w1, ay.w1}, wx[2] = {1.f - ax.w1, ax.w1};
-  const int iz[2] = {az.i0, az.i1}, iy[2] = {ay.i0, ay.i1};
-  float sv = 0.f, qc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) qc[c] = 0.f;
-#pragma unroll
-  for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib) {
-      const int64_t o = ((int64_t)iz[ia] * H + iy[ib]) * W + xb;
-      const F2u p = *reinterpret_cast<const F2u*>(d + o);
-      const FNu<2 * C> pq = *reinterpret_cast<const FNu<2 * C>*>(q + o * C);
-      const float w0 = wz[ia] * wy[ib] * wx[0], w1 = wz[ia] * wy[ib] * wx[1];
-      sv += w0 * (x0_lo ? p.x : p.y);
-      sv += w1 * (x1_lo ? p.x : p.y);
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        qc[c] += w0 * (x0_lo ? pq.v[c] : pq.v[C + c]);
-        qc[c] += w1 * (x1_lo ? pq.v[c] : pq.v[C + c]);
-      }
-    }
-  float av = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) av += g[c] * qc[c];
-  s = sv;
-  a = av;
-}
-
-template <int C>
-__device__ __forceinline__ void absorb_sample_scalar(const float* __restrict__ d, const float* __restrict__ q,
-                                                     const float* r, const float* g, int D, int H, int W, int z, int h,
-                                                     int x, float& s, float& a) {
-  float cx, cy, cz;
-  ray_coords(r, D, H, W, z, h, x, cx, cy, cz);
-  Tri t; Axis ax, ay, az;
-  tri_setup(cx, cy, cz, D, H, W, t, ax, ay, az);
-  float sv = 0.f, qc[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) qc[c] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sv += t.w[k] * d[t.o[k]];
-    const float* p = q + t.o[k] * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) qc[c] += t.w[k] * p[c];
-  }
-  float av = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) av += g[c] * qc[c];
-  s = sv;
-  a = av;
 }
 
 // (w and g_s carry no __restrict__: they may be one buffer)
@@ -150,7 +86,7 @@ __global__ void __launch_bounds__(256) liquid_absorb_bwd_kernel(const float* __r
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         wv[u] = wcol[(int64_t)(z + u) * HW];
-        absorb_sample_pairs<C>(d, q, r, g, D, H, W, z + u, h, x, sv[u], av[u]);
+        ray_sample_pairs<C, true>(d, q, r, g, D, H, W, z + u, h, x, sv[u], av[u]);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) NFS_ABSORB_TAKE(sv[u], av[u], wv[u], z + u);
@@ -158,25 +94,18 @@ __global__ void __launch_bounds__(256) liquid_absorb_bwd_kernel(const float* __r
     for (; z < D; ++z) {
       float sone, aone;
       const float wone = wcol[(int64_t)z * HW];
-      absorb_sample_pairs<C>(d, q, r, g, D, H, W, z, h, x, sone, aone);
+      ray_sample_pairs<C, true>(d, q, r, g, D, H, W, z, h, x, sone, aone);
       NFS_ABSORB_TAKE(sone, aone, wone, z);
     }
   } else {
     for (int z = 0; z < D; ++z) {
       float sone, aone;
       const float wone = wcol[(int64_t)z * HW];
-      absorb_sample_scalar<C>(d, q, r, g, D, H, W, z, h, x, sone, aone);
+      ray_sample_scalar<C, true>(d, q, r, g, D, H, W, z, h, x, sone, aone);
       NFS_ABSORB_TAKE(sone, aone, wone, z);
     }
   }
 #undef NFS_ABSORB_TAKE
-}
-
-// do [a, a + na) and [b, b + nb) floats share an address?  (a null range shares none)
-static bool overlaps(const float* a, int64_t na, const float* b, int64_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * 4, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * 4;
-  return a0 < b1 && b0 < a1;
 }
 
 }  // namespace nfs

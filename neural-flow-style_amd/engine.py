@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops, parallel
-from .config import COLOUR_RENDERS, colour_background
+from .config import COLOUR_RENDERS, colour_background, colour_exposure
 
 HOST_BOUND = 0.85       # issue time over this share of the wall time: the GPU finished as soon as the host had issued the work
 
@@ -1544,9 +1544,20 @@ class ColourRenderLoss(object):
     emission q is not (as in the smoke mode), so rotate(q) / S can exceed the particles' colour there and the clip takes
     what is above 1; smoothing the emission is not built.
 
-    ``loss_and_grad(..., absorb=True)`` (liquid render, no ``style_mask``; include/nfs_absorb.h) also returns the gradient
+    ``render="exposure"`` (include/nfs_exposure.h): the smoke model at a fixed ``exposure`` kappa > 0 in place of the maximum,
+
+        w = kappa tau T (ops.exposure_weights, one pass, one launch),  J = sum_z w rotate(q)  over black
+
+    so a weight depends on its own ray alone and the brightness of a sequence no longer follows each frame's brightest
+    pixel.  The context carries ``grey`` = sum_z w S <= kappa (1 - t), ``d_gray`` = clip(grey, 0, 1)[..., None] and
+    ``gmax`` = None; ``background`` has no effect; ``v_batch`` only groups the image-loss batches.  At kappa = 1 a uniform
+    colour c0 (q = c0 d) renders at most c0 (1 - t) and is never clipped.  The weights are at most kappa tau.
+
+    ``loss_and_grad(..., absorb=True)`` (liquid or exposure render, no ``style_mask``; include/nfs_absorb.h,
+    include/nfs_exposure.h) also returns the gradient
     in the volume d given to ``prepare`` with q held constant -- the joint variable of target_field 'pc', where d moves
     with the particles.  It is formed after the projection's transpose, which needs the weights: ``ops.liquid_absorb_bwd``
+    (exposure render: ``ops.exposure_absorb_bwd``, g_S = -tau times the inclusive prefix of a w from the near end)
     writes g_S over ``ctx["w"]`` and ``ops.rotate_bwd`` (tiled, bit-reproducible) takes it to d, so the context is SPENT
     afterwards (``ctx["spent"]``; a second call with it raises).  Two cases are refused with a ValueError: the smoke
     render, whose maximum M couples every ray (its adjoint in the density is not built), and ``style_mask``, whose mask
@@ -1554,15 +1565,22 @@ class ColourRenderLoss(object):
 
     RENDERS = COLOUR_RENDERS
 
-    def __init__(self, image_loss, transmit, v_batch=1, render="", background=(1, 1, 1)):
+    def __init__(self, image_loss, transmit, v_batch=1, render="", background=(1, 1, 1), exposure=1.0):
         if render not in self.RENDERS:
             raise ValueError("colour_render %r is none of %s" % (render, self.RENDERS))
         self.image_loss = image_loss
         self.tau = float(transmit)
         self.v_batch = max(int(v_batch or 1), 1)
         self.liquid = render == "liquid"
+        self.fixed_exposure = render == "exposure"
         self.background = colour_background(background)
+        self.exposure = colour_exposure(exposure)
         self._bg_dev = None
+
+    def _prepare_exposure(self, d3, rot):
+        w, grey = ops.exposure_weights(d3, rot, self.tau, self.exposure)
+        return {"rot": rot, "w": w, "grey": grey, "gmax": None,
+                "d_gray": torch.clamp(grey, 0, 1).unsqueeze(-1).contiguous()}
 
     def _prepare_liquid(self, d3, rot):
         w, grey, t = ops.liquid_weights(d3, rot, self.tau)
@@ -1577,6 +1595,8 @@ class ColourRenderLoss(object):
         (liquid: also t_total [V,H,W], bg_img [V,H,W,3] and ``d3`` itself, for ``loss_and_grad(absorb=True)``)"""
         if self.liquid:
             return self._prepare_liquid(d3, rot)
+        if self.fixed_exposure:
+            return self._prepare_exposure(d3, rot)
         V = int(rot.shape[0])
         w = torch.empty((V,) + tuple(d3.shape), dtype=torch.float32, device=d3.device)
         grey, _ = ops.rotate_render_fwd(d3, rot, self.tau, False, d_rot=w)
@@ -1598,15 +1618,17 @@ class ColourRenderLoss(object):
 
     def loss_and_grad(self, q, ctx, route=None, absorb=False):
         """q [D,H,W,3] -> (losses [V], g_q [D,H,W,3]); ``route``: the transpose's (``ops.colour_project_bwd``; None: by size).
-        ``absorb``: -> (losses, g_q, g_d [D,H,W]), g_d the gradient in the volume ``prepare`` was given (liquid render
-        without style_mask only); the context's weights are overwritten and the context marked spent"""
+        ``absorb``: -> (losses, g_q, g_d [D,H,W]), g_d the gradient in the volume ``prepare`` was given (liquid or exposure
+        render without style_mask only); the context's weights are overwritten and the context marked spent"""
         if absorb:
-            if not self.liquid:
+            if not (self.liquid or self.fixed_exposure):
                 raise ValueError("absorb=True on the smoke colour render: the maximum M of w = T / M couples every ray and "
-                                 "its adjoint in the density is not built (use colour_render 'liquid')")
+                                 "its adjoint in the density is not built (use colour_render 'liquid' or 'exposure')")
             if self.image_loss.style_mask:
                 raise ValueError("absorb=True with style_mask: the mask 1 - t would depend on the density and the gradient "
-                                 "through it is not built (pass style_mask false)")
+                                 "through it is not built (pass style_mask false)" if self.liquid else
+                                 "absorb=True with style_mask: the mask clip(grey, 0, 1) would depend on the density and "
+                                 "the gradient through it is not built (pass style_mask false)")
         if ctx.get("spent"):
             raise ValueError("this colour context is spent: loss_and_grad(absorb=True) overwrote its ray weights (prepare "
                              "a new one)")
@@ -1623,6 +1645,9 @@ class ColourRenderLoss(object):
         if not absorb:
             return losses, g_q
         ctx["spent"] = True                              # (the weights are dead from here on: g_S goes over them)
+        if self.fixed_exposure:
+            g_S = ops.exposure_absorb_bwd(g_J, q, ctx["rot"], ctx["w"], self.tau, out=ctx["w"])
+            return losses, g_q, ops.rotate_bwd(g_S.unsqueeze(-1), ctx["rot"], tiled=True).squeeze(-1)
         g_S = ops.liquid_absorb_bwd(g_J, q, ctx["d3"], ctx["rot"], ctx["w"], ctx["t_total"], self._bg_dev[:q.shape[-1]],
                                     self.tau, out=ctx["w"])
         g_d = ops.rotate_bwd(g_S.unsqueeze(-1), ctx["rot"], tiled=True).squeeze(-1)

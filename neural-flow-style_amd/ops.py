@@ -950,6 +950,43 @@ def liquid_absorb_bwd(g_J, q, d, rot, w, t_total, bg, tau, out=None):
     return out
 
 
+# ---- the smoke colour render at a fixed exposure and its derivative in the density (include/nfs_exposure.h) ----------
+
+def exposure_weights(d, rot, tau, gain=1.0, w=None, grey=None):
+    """d [D,H,W], rot [V,3,3] -> (w [V,D,H,W], grey [V,H,W]) in one pass over the rays: w = gain tau exp(-tau sum_{z' >= z} S)
+    with S = rotate(d) gathered on the fly (the smoke render's transmittance, no maximum), grey = sum_z w S <= gain (1 - t)."""
+    D, H, W = d.shape
+    V = int(rot.shape[0])
+    if w is None:
+        w = _empty((V, D, H, W), d)
+    if grey is None:
+        grey = _empty((V, H, W), d)
+    assert tuple(w.shape) == (V, D, H, W) and tuple(grey.shape) == (V, H, W)
+    _lib.call("nfs_exposure_weights", _ptr(d), _ptr(rot), float(tau), float(gain), _ptr(w), _ptr(grey), V, D, H, W,
+              _stream())
+    _written(w, grey)
+    return w, grey
+
+
+def exposure_absorb_bwd(g_J, q, rot, w, tau, out=None):
+    """g_J [V,H,W,C], q [D,H,W,C] (C in 1..4), rot [V,3,3], w [V,D,H,W] as ``exposure_weights`` wrote it ->
+    g_S [V,D,H,W] = -tau sum_{z' <= z} w sum_c g_J[c] rotate(q)[z',c] = d loss / d rotate(d) of J = sum_z w rotate(q) with q
+    held constant (``rotate_bwd`` of it is the gradient in d).  ``out`` may be ``w`` itself: the weights are then
+    overwritten."""
+    D, H, W, C = (int(x) for x in q.shape)
+    V = int(rot.shape[0])
+    if tuple(g_J.shape) != (V, H, W, C) or tuple(w.shape) != (V, D, H, W):
+        raise ValueError("exposure_absorb_bwd: g_J %s, w %s do not fit q %s through %d views"
+                         % (tuple(g_J.shape), tuple(w.shape), tuple(q.shape), V))
+    if out is None:
+        out = _empty((V, D, H, W), w)
+    assert tuple(out.shape) == (V, D, H, W)
+    _lib.call("nfs_exposure_absorb_bwd", _ptr(g_J), _ptr(q), _ptr(rot), _ptr(w), float(tau), _ptr(out), V, D, H, W, C,
+              _stream())
+    _written(out)
+    return out
+
+
 # ---- the emission of a colour grid (include/nfs_emission.h) -----------------------------------------------------------
 
 def _emission_dims(c, e):

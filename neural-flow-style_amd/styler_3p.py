@@ -12,16 +12,19 @@ Forward graph per frame (styler_3p.py:42-164):
        of a view is clip(sum_z T/M rotate(q), 0, 1) -> x255 -> loss network: ``engine.ColourRenderLoss`` (build
        extension; conventions of styler_2p).  ``--colour_render liquid``: the image is
        clip(sum_z w rotate(q) + t bg, 0, 1), front-to-back alpha compositing over ``--colour_background`` (w, t:
-       include/nfs_liquid.h); 'r' and 'd_intm' are then over the background.  The grey volume is smoothed by k and q is
-       not, so rotate(q) / rotate(d) can exceed the particles' colour and the clip takes it
-  'pc': positions AND colours of a liquid in one variable [N,6] = (v, c / colour_lr_scale) (build extension, DESIGN.md
-       section 8): the grey field of 'p' at p + v absorbs, q = p2g(p + v, pc=clip(c,0,1), pd=r) emits, the image is the
-       liquid colour render's (``--colour_render liquid`` only).  The geometry moves, so nothing of a frame is kept across
-       steps but its densities r and the splat configurations: an evaluation forms the ray weights, and
+       include/nfs_liquid.h); 'r' and 'd_intm' are then over the background.  ``--colour_render exposure``: the smoke
+       model with the fixed exposure ``--colour_exposure`` in place of the maximum M (include/nfs_exposure.h), over black.
+       The grey volume is smoothed by k and q is not, so rotate(q) / rotate(d) can exceed the particles' colour and the
+       clip takes it
+  'pc': positions AND colours of a liquid (or, with ``--colour_render exposure``, of smoke) in one variable [N,6] =
+       (v, c / colour_lr_scale) (build extension): the grey field of 'p' at p + v absorbs, q = p2g(p + v, pc=clip(c,0,1), pd=r) emits, the image is the
+       liquid colour render's or the fixed-exposure smoke render's (``--colour_render liquid`` / ``exposure``; the
+       weights of the latter are one launch, ``ops.exposure_weights``).  The geometry moves, so nothing of a frame is
+       kept across steps but its densities r and the splat configurations: an evaluation forms the ray weights, and
        ``engine.ColourRenderLoss.loss_and_grad(absorb=True)`` returns the gradient in the emission AND in the absorbing
-       volume (include/nfs_absorb.h); both reach the positions through the splat's adjoint.  One optimiser step of ``lr``
-       moves a colour by ``colour_lr_scale * lr``.  ``w_pressure`` acts as for 'p'; ``style_mask`` and the smoke colour
-       render are refused (the mask and the maximum would depend on the variable)
+       volume (include/nfs_absorb.h, include/nfs_exposure.h); both reach the positions through the splat's adjoint.  One
+       optimiser step of ``lr`` moves a colour by ``colour_lr_scale * lr``.  ``w_pressure`` acts as for 'p'; ``style_mask`` and the max-normalised
+       smoke colour render ('' / 'smoke') are refused (the mask and the maximum would depend on the variable)
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -44,7 +47,7 @@ import torch
 from . import engine, ops, parallel
 from . import transform as T
 from . import vgg as vggmod
-from .config import check_colour_render, check_optimizer
+from .config import check_colour_render, check_optimizer, colour_exposure
 from .styler_base import StylerBase
 from .util import temporal_weights
 
@@ -121,10 +124,11 @@ class Styler(StylerBase):
     @staticmethod
     def _check_joint(cfg):
         """the refusals of target_field 'pc', before the base class loads a network: a ValueError naming the flag"""
-        if (getattr(cfg, "colour_render", "") or "") != "liquid":
+        if (getattr(cfg, "colour_render", "") or "") not in ("liquid", "exposure"):
             raise ValueError("target_field 'pc': colour_render %r -- the joint variable moves the density, and only the "
-                             "liquid colour render has an adjoint in it: the smoke render's maximum couples every ray "
-                             "(pass --colour_render liquid)" % (getattr(cfg, "colour_render", ""),))
+                             "liquid and the fixed-exposure colour renders have an adjoint in it: the smoke render's "
+                             "maximum couples every ray (pass --colour_render liquid, or --colour_render exposure for smoke)"
+                             % (getattr(cfg, "colour_render", ""),))
         if getattr(cfg, "style_mask", False):
             raise ValueError("target_field 'pc': style_mask -- the mask 1 - t would depend on the variable and the "
                              "gradient through it is not built (pass --style_mask false)")
@@ -161,7 +165,8 @@ class Styler(StylerBase):
                                            w_hist_layer=getattr(self, "w_hist_layer", ()))
         render, background = check_colour_render(self, colour=True)
         return engine.ColourRenderLoss(image_loss, self.transmit, self.v_batch if self.rotate else 1, render=render,
-                                       background=background)
+                                       background=background,
+                                       exposure=colour_exposure(getattr(self, "colour_exposure", 1.0)))
 
     # ---- the colour path (target_field 'c'): what a step does not change is formed once -------------------------
     _COLOUR_CTX_FLOATS = 1 << 30          # ray weights kept across steps (4 GiB); beyond it a context is formed per call

@@ -66,7 +66,7 @@ import torch
 
 from . import engine, grid2d, ops, parallel
 from . import transform as T
-from .config import check_colour_render, check_optimizer
+from .config import check_colour_render, check_optimizer, colour_exposure
 from .styler_base import StylerBase
 from .util import cosine_decay, temporal_weights
 
@@ -110,7 +110,8 @@ class Styler(StylerBase):
     alpha compositing over ``colour_background`` (include/nfs_liquid.h; ``engine.ColourRenderLoss``); ``'r'`` and
     ``'d_intm'`` are then over the background, everything else of the path unchanged.  Refused with a ValueError naming
     the flag: a two-entry ``resolution``, ``render_liquid``, a non-empty ``ray_mode``, ``style_mask_on_ref``,
-    ``w_density`` > 0, a ``colour_render`` outside '' / 'smoke' / 'liquid' (and 'liquid' with another variable), a
+    ``w_density`` > 0, a ``colour_render`` outside '' / 'smoke' / 'liquid' / 'exposure' (and 'liquid' or 'exposure' with
+    another variable), a ``colour_exposure`` that is not finite and positive, a
     ``colour_background`` that is not three numbers in [0,1].  Eager launches only.
     Not built in 2-D: ``rotate`` (ValueError: there are no views), L-BFGS (ValueError), dead-region masks, slab
     sharding, a MacCormack transport between frames, ``batch_size > 1``, a root-level driver (the reference has none for
@@ -171,7 +172,8 @@ class Styler(StylerBase):
             # the colour render around an image loss (styler_3p's 'c' path); the image targets live in the image loss
             render, background = check_colour_render(self, colour=True)
             self.loss = engine.ColourRenderLoss(self._make_image_loss(), self.transmit, self.v_batch if self.rotate else 1,
-                                                render=render, background=background)
+                                                render=render, background=background,
+                                                exposure=colour_exposure(getattr(self, "colour_exposure", 1.0)))
             self.colour_bwd_route = getattr(self, "colour_bwd_route", None)   # ('tiled': bit-reproducible steps)
         else:
             self.loss = self._make_image_loss() if self.is2d else self._make_loss(rotate=self.rotate)
