@@ -155,7 +155,8 @@ _OWNER = _owners(list(SIDE.values()) + list(SIDE_LATER.values()))
 # since is a record here -- append the key; nothing else in this file changes, and no test may assert what this table holds
 # as a whole (only that its own key is in it and bound).  Its names are a second lookup that call() consults after _OWNER.
 # exposure: the smoke colour render at a fixed exposure and its derivative in the density (colour_render 'exposure')
-SIDE_OPEN = {k: SideLibrary(k) for k in ("exposure",)}
+# carrier: particles moved by a displacement field on a coarse grid, and the transpose of that sampling (target_field 'g')
+SIDE_OPEN = {k: SideLibrary(k) for k in ("exposure", "carrier")}
 
 
 def _owners_open(records, taken):

@@ -22,6 +22,9 @@ default 1 1 1), read by the two colour stylizers (styler_3p ``target_field 'c'``
 ``--target_field pc`` (styler_3p): positions and colours in one variable, of a liquid through ``--colour_render liquid`` or
 of smoke through ``--colour_render exposure``; ``--colour_lr_scale`` (positive float, default 1, defaulted by
 ``complete()`` too): one optimiser step of ``lr`` moves a colour of that variable by ``colour_lr_scale * lr``.
+``--target_field g`` (styler_3p): the variable is a displacement field on a coarse carrier grid, sampled at the particles
+(include/nfs_carrier.h); ``--carrier_resolution`` (three ints >= 1; ``complete()`` defaults it to ``max(n // 8, 2)`` per axis
+of ``resolution``) is that grid and ``--carrier_interp`` (``cubic`` / ``linear``, default ``cubic``) the sampling kernel.
 """
 from __future__ import annotations
 
@@ -77,7 +80,7 @@ _FLAGS = [
     ("Render", "n_views", dict(type=int, default=9)),
     ("Render", "sample_type", dict(type=str, default="poisson", choices=["uniform", "poisson", "both"])),
     ("Render", "render_liquid", dict(type=str2bool, default=False)),
-    ("Optimizer", "target_field", dict(type=str, default="p", choices=["d", "p", "c", "pc"])),
+    ("Optimizer", "target_field", dict(type=str, default="p", choices=["d", "p", "c", "pc", "g"])),
     ("Optimizer", "optimizer", dict(type=str, default="adam")),
     ("Optimizer", "iter", dict(type=int, default=20)),
     ("Optimizer", "lr", dict(type=float, default=0.0007)),
@@ -119,9 +122,12 @@ _FLAGS = [
     ("MI355X", "colour_background", dict(nargs=3, type=float, default=argparse.SUPPRESS)),
     ("MI355X", "colour_lr_scale", dict(type=float, default=argparse.SUPPRESS)),
     ("MI355X", "colour_exposure", dict(type=float, default=argparse.SUPPRESS)),
+    ("MI355X", "carrier_resolution", dict(nargs=3, type=int, default=argparse.SUPPRESS)),
+    ("MI355X", "carrier_interp", dict(type=str, default=argparse.SUPPRESS)),
 ]
 
 COLOUR_RENDERS = ("", "smoke", "liquid", "exposure")
+CARRIER_INTERPS = ("cubic", "linear")
 
 
 def make_parser():
@@ -209,6 +215,31 @@ def check_colour_render(config, colour):
     return render, bg
 
 
+def default_carrier_resolution(resolution):
+    """``max(n // 8, 2)`` per axis of ``resolution``"""
+    return [max(int(n) // 8, 2) for n in resolution]
+
+
+def check_carrier(config):
+    """the carrier grid's flags (target_field 'g'), checked where the stylizer is constructed, before a network is loaded:
+    ValueError naming the flag for a ``carrier_resolution`` that is not three ints >= 1 and a ``carrier_interp`` outside
+    'cubic' / 'linear'.  -> (resolution as a tuple of three ints, cubic as a bool)"""
+    res = getattr(config, "carrier_resolution", None)
+    if res is None:
+        res = default_carrier_resolution(getattr(config, "resolution", ()))
+    try:
+        ok = len(res) == 3 and all(float(v) == int(v) and not isinstance(v, bool) and int(v) >= 1 for v in res)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("--carrier_resolution %r: the carrier grid of target_field 'g' is three ints >= 1" % (res,))
+    interp = getattr(config, "carrier_interp", None)
+    interp = "cubic" if interp is None else interp
+    if interp not in CARRIER_INTERPS:
+        raise ValueError("--carrier_interp %r is none of %s" % (interp, CARRIER_INTERPS))
+    return tuple(int(v) for v in res), interp == "cubic"
+
+
 def complete(config):
     """defaults for the attributes the reference drivers inject after parsing"""
     if not hasattr(config, "rng") or config.rng is None:
@@ -239,5 +270,9 @@ def complete(config):
         config.colour_lr_scale = 1.0
     if not hasattr(config, "colour_exposure"):
         config.colour_exposure = 1.0
+    if not hasattr(config, "carrier_resolution"):
+        config.carrier_resolution = default_carrier_resolution(getattr(config, "resolution", ()))
+    if not hasattr(config, "carrier_interp"):
+        config.carrier_interp = "cubic"
 
     return config

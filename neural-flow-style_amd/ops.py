@@ -1527,6 +1527,48 @@ def g2p_fwd(g, p, cubic=True):
     return out
 
 
+# ---- particles moved by a displacement field on a carrier grid, and the transpose (include/nfs_carrier.h) -------------
+
+def _carrier_dims(dims, nd):
+    dims = [int(v) for v in dims]
+    if nd not in (2, 3) or len(dims) != nd:
+        raise ValueError("carrier: a grid of %d axes for positions of %d components (nd is 2 or 3)" % (len(dims), nd))
+    return dims[0], dims[1], dims[2] if nd == 3 else 1
+
+
+def carrier_displace(u, p, cubic=True, want_v=True):
+    """u [X,Y,(Z),nd] cell-centred displacement field in the units of p, p [N,nd] in [0,1] -> (p + v, v) with
+    v = g2p_fwd(u, p) bit for bit, in one launch; v is None unless ``want_v``"""
+    nd = int(p.shape[-1])
+    if u.dim() != nd + 1 or int(u.shape[-1]) != nd:
+        raise ValueError("carrier_displace: u %s is not a field of %d-vectors on a %d-D grid for p %s"
+                         % (tuple(u.shape), nd, nd, tuple(p.shape)))
+    X, Y, Z = _carrier_dims(u.shape[:nd], nd)
+    N = int(p.shape[0])
+    p_out = _empty((N, nd), p)
+    v = _empty((N, nd), p) if want_v else None
+    _lib.call("nfs_carrier_displace", _ptr(u), _ptr(p), _ptr(p_out), _ptr(v), nd, X, Y, Z, N, int(bool(cubic)), _stream())
+    return p_out, v
+
+
+def carrier_bwd(g_v, p, dims, cubic=True, route=0, count=False):
+    """g_v [N,C], p [N,nd] -> g_u [*dims,C]: the transpose of ``g2p_fwd`` in the grid, g_u[cell,c] = sum over the taps that
+    land on the cell of w g_v[i,c].  Any particle order is correct; grid order (transform.grid_order) is fast: a block of
+    256 consecutive particles sums the box of cells it touches in LDS and adds each once.  ``route`` 1: every block issues
+    one global atomic per tap instead.  ``count``: also the number of blocks that took the box route (an int32 device
+    tensor of one element)"""
+    nd = int(p.shape[-1])
+    X, Y, Z = _carrier_dims(dims, nd)
+    N, Cn = int(p.shape[0]), int(g_v.shape[-1])
+    if tuple(g_v.shape) != (N, Cn):
+        raise ValueError("carrier_bwd: g_v %s is not [N,C] for p %s" % (tuple(g_v.shape), tuple(p.shape)))
+    g_u = _empty(tuple(int(v) for v in dims) + (Cn,), p)
+    n_box = torch.empty(1, dtype=torch.int32, device=p.device) if count else None
+    _lib.call("nfs_carrier_bwd", _ptr(g_v), _ptr(p), _ptr(g_u), None if n_box is None else n_box.data_ptr(), nd, X, Y, Z, Cn,
+              N, int(bool(cubic)), int(route), _stream())
+    return (g_u, n_box) if count else g_u
+
+
 
 # ---- SURVEY 8(f)-3: node types of the Inception-v1 loss network ------------------------------------------------------
 # Operands are channel RANGES of contiguous [B,H,W,ld] buffers: (tensor, first channel, channels).

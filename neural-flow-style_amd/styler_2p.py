@@ -28,6 +28,9 @@ class Styler(StylerBase):
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
         check_colour_render(self_dict, colour=False)     # (a 2-D colour image has no rays: 'liquid' is refused here)
+        if getattr(self_dict, "target_field", "") == "g":
+            raise ValueError("target_field 'g' is 3-D only: the carrier grid (--carrier_resolution) is wired into the 3-D "
+                             "particle stylizer (styler_3p); the kernels of include/nfs_carrier.h take nd = 2 as well")
         StylerBase.__init__(self, self_dict)
         self.batch_size = max(int(self.batch_size), 1)
         if self.batch_size > 1 and getattr(self, "w_hist", 0):

@@ -25,6 +25,19 @@ Forward graph per frame (styler_3p.py:42-164):
        volume (include/nfs_absorb.h, include/nfs_exposure.h); both reach the positions through the splat's adjoint.  One
        optimiser step of ``lr`` moves a colour by ``colour_lr_scale * lr``.  ``w_pressure`` acts as for 'p'; ``style_mask`` and the max-normalised
        smoke colour render ('' / 'smoke') are refused (the mask and the maximum would depend on the variable)
+  'g': the 'p' path with the displacement sampled from a CARRIER GRID (build extension; the reference
+       has no such path): the variable of a key frame is u [Gd,Gh,Gw,3] (``--carrier_resolution``), a displacement field
+       in the units of p, cell-centred over the whole domain, starting at zero or at ``params['u_init'][t]``;
+       p' = p + g2p(u, p) (``--carrier_interp`` cubic / linear, one launch: ``ops.carrier_displace``), then splat, smooth,
+       views, render, loss network and ``w_pressure`` exactly as for 'p'.  The gradient in the displacements reaches u
+       through the transpose of the sampling (``ops.carrier_bwd``, include/nfs_carrier.h).  The variable has one shape
+       whatever a frame holds, so the frames of a sequence may hold DIFFERENT particle sets (each in its own grid order,
+       returned in the caller's), the sampling kernel ties neighbouring particles together, and the result moves any
+       particle set (``Styler.apply_carrier``).  Temporal smoothing, ``interp`` and ``frames_per_opt`` act on the grids
+       in place: there is NO transport between frames (particle ``params`` carry no grid velocity), a frame's field is
+       filtered with its neighbours' cell by cell.  The carrier resolution is the same at every octave and u is in domain
+       units, so it carries over unchanged.  ``result['opt']`` are the fields, ``result['v']`` the sampled per-particle
+       displacements, ``result['p']`` = p + v.  ``w_density`` and a process group are refused
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -47,7 +60,7 @@ import torch
 from . import engine, ops, parallel
 from . import transform as T
 from . import vgg as vggmod
-from .config import check_colour_render, check_optimizer, colour_exposure
+from .config import check_carrier, check_colour_render, check_optimizer, colour_exposure
 from .styler_base import StylerBase
 from .util import temporal_weights
 
@@ -73,12 +86,15 @@ class _SmoothRelu(torch.autograd.Function):
 class Styler(StylerBase):
     _colour = False                                  # target_field 'c' (set by the constructor)
     _joint = False                                   # target_field 'pc' (set by the constructor)
+    _carrier = False                                 # target_field 'g' (set by the constructor)
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
         check_colour_render(self_dict, colour=getattr(self_dict, "target_field", "") in ("c", "pc"))
         if getattr(self_dict, "target_field", "") == "pc":
             self._check_joint(self_dict)
+        if getattr(self_dict, "target_field", "") == "g":
+            self._check_carrier(self_dict)
         if getattr(self_dict, "target_field", "") == "c":
             # the colour path renders by emission-absorption only and has no auxiliary field terms (refused before the
             # base class loads a network)
@@ -101,6 +117,9 @@ class Styler(StylerBase):
         assert self.batch_size == 1, "batch_size > 1 is not supported (see module docstring)"
         self._colour = self.target_field == "c"
         self._joint = self.target_field == "pc"
+        self._carrier = self.target_field == "g"
+        if self._carrier:
+            self.carrier_resolution, self._carrier_cubic = check_carrier(self)
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -150,6 +169,33 @@ class Styler(StylerBase):
         if not float(1.0 if scale is None else scale) > 0:
             raise ValueError("--colour_lr_scale %r: the step of a colour relative to a displacement must be positive"
                              % (scale,))
+
+    @staticmethod
+    def _check_carrier(cfg):
+        """the refusals of target_field 'g', before the base class loads a network: a ValueError naming the flag"""
+        check_carrier(cfg)
+        if (getattr(cfg, "w_density", 0) or 0) > 0:
+            raise ValueError("target_field 'g': w_density acts on the density variable (pass --w_density 0)")
+        if getattr(cfg, "pg", None) is not None:
+            raise ValueError("target_field 'g' over a process group (pg): sharding the carrier grid over ranks is not "
+                             "built (run it on one GPU)")
+
+    @property
+    def _moves(self):
+        """the variable moves the positions: 'p', 'pc' (its displacement columns) and 'g' (the carrier grid sampled at
+        the particles)"""
+        return "p" in self.target_field or self._carrier
+
+    def apply_carrier(self, u, p):
+        """a result of target_field 'g' applied to ANY particle set: u [Gd,Gh,Gw,3] (an entry of result['opt']), p [N,3]
+        in the normalised domain, array order -> p + g2p(u, p) with this stylizer's ``carrier_interp``; numpy in, numpy
+        out (device tensors stay on the device).  That is how a field stylised on a low-resolution set reaches a
+        resampled one"""
+        cubic = check_carrier(self)[1]
+        as_np = not torch.is_tensor(p)
+        u_, p_ = (x.to(self.device).float().contiguous() if torch.is_tensor(x) else self._dev(x) for x in (u, p))
+        out = ops.carrier_displace(u_, p_, cubic=cubic, want_v=False)[0]
+        return out.cpu().numpy() if as_np else out
 
     def _make_colour_loss(self):
         w_layers = list(self.w_style_layer)
@@ -293,7 +339,11 @@ class Styler(StylerBase):
         pressure = None
         extra = None
         p_ = p.unsqueeze(0)
-        if "p" in self.target_field:
+        if self._carrier:
+            # ('g': the carrier grid sampled at the frame's constant positions; autograd carries the positions' gradient
+            # into the grid through the transpose, ops.carrier_bwd)
+            p_ = T.carrier_displace(var, p, self._carrier_cubic).unsqueeze(0)
+        elif self._moves:
             p_ = p_ + (var[:, 0:3] if self._joint else var).unsqueeze(0)     # ('pc': the displacement columns)
         p_all = p_                                   # ('c': the positions as they came; var is not read)
         # a sequence keeps ONE particle order for all frames (frame 0's: the temporal filter needs particle i to be the
@@ -345,7 +395,7 @@ class Styler(StylerBase):
         orders = self.__dict__.setdefault("_orders", {})
         key = (p.data_ptr(), p.shape[0])
         every = int(getattr(self, "reorder_every", 10) or 0)
-        if "p" not in self.target_field or every <= 0 or not getattr(self, "sort_particles", True) or p.shape[0] < 2:
+        if not self._moves or every <= 0 or not getattr(self, "sort_particles", True) or p.shape[0] < 2:
             return orders.get(key)
         ages = self.__dict__.setdefault("_order_age", {})
         age = ages.get(key, 0) + 1
@@ -410,6 +460,12 @@ class Styler(StylerBase):
     def _dev(self, a):
         return torch.as_tensor(np.asarray(a, np.float32)).to(self.device).contiguous()
 
+    def _var_shape(self, n):
+        """the shape of a frame's variable: the carrier grid's for 'g', per particle otherwise"""
+        if self._carrier:
+            return tuple(self.carrier_resolution) + (3,)
+        return (n, 6 if self._joint else 3 if (self._moves or self._colour) else self.num_kernels)
+
     # ---- debug helper: rendered images of the un-stylised input ------------------------------------
     def render_test(self, params):
         imgs = []
@@ -433,7 +489,7 @@ class Styler(StylerBase):
                 imgs.append(dimg[0].cpu().numpy().astype(np.uint8))
                 continue
             r = self._dev(params["r"][t]) if "d" in self.target_field else None
-            var = torch.zeros(n, 3 if "p" in self.target_field else self.num_kernels, device=self.device)
+            var = torch.zeros(*self._var_shape(n), device=self.device)
             with torch.no_grad():
                 _, d_out, _ = self._field(p, r, var, list(self.resolution))
                 dimg = self.loss.d_img(d_out.reshape(d_out.shape[1:4]).contiguous(), self._identity)
@@ -445,6 +501,9 @@ class Styler(StylerBase):
         if (self._colour or self._joint) and self.pg is not None:
             raise ValueError("target_field %r over a process group: sharding the colour path over ranks is not built "
                              "(run it on one GPU)" % (self.target_field,))
+        if self._carrier and self.pg is not None:
+            raise ValueError("target_field 'g' over a process group (pg): sharding the carrier grid over ranks is not built "
+                             "(run it on one GPU)")
         if abs(self.lr_scale - 1) > 1e-7 and not isinstance(self.lr, list):
             self.lr = [self.lr / self.lr_scale ** i for i in range(self.octave_n)]
 
@@ -481,19 +540,34 @@ class Styler(StylerBase):
         # (5e5 particles on 200^3: 0.69 ms unordered, 0.37 ordered with global atomics, 0.16 in LDS); the outputs are
         # returned in the caller's order.
         inv = None
-        if getattr(self, "sort_particles", True) and len(set(int(x.shape[0]) for x in p)) == 1 and p[0].shape[0] > 1:
+        invs = None
+        if self._carrier:
+            # 'g': the variable has one shape whatever a frame holds, so the frames may hold different particles: each is
+            # put into its OWN grid order (what the splat and the transpose of the sampling are fast in) and comes back
+            # through its own inverse permutation
+            invs = [None] * self.num_frames
+            if getattr(self, "sort_particles", True):
+                for t, x in enumerate(p):
+                    if x.shape[0] > 1:
+                        perm = T.grid_order(x, self.resolution)
+                        invs[t] = torch.empty_like(perm)
+                        invs[t][perm] = torch.arange(perm.numel(), device=self.device)
+                        p[t] = x[perm].contiguous()
+        elif getattr(self, "sort_particles", True) and len(set(int(x.shape[0]) for x in p)) == 1 and p[0].shape[0] > 1:
             perm = T.grid_order(p[0], self.resolution)
             inv = torch.empty_like(perm)
             inv[perm] = torch.arange(perm.numel(), device=self.device)
             p = [x[perm].contiguous() for x in p]
             r = [x[perm].contiguous() if x is not None else None for x in r]
         self._orders, self._order_age = {}, {}
-        if getattr(self, "sort_particles", True) and self.num_frames > 1:
+        if getattr(self, "sort_particles", True) and self.num_frames > 1 and not self._carrier:
             for x in p[1:]:                                  # (frame 0 is in its own order already)
                 if x.shape[0] > 1:
                     self._orders[(x.data_ptr(), x.shape[0])] = T.grid_order(x, self.resolution)
-        nvar = 6 if self._joint else 3 if ("p" in self.target_field or self._colour) else self.num_kernels
-        g_opt = [torch.zeros(p[i].shape[0], nvar, device=self.device) for i in range(self.num_frames)]
+        g_opt = [torch.zeros(*self._var_shape(p[i].shape[0]), device=self.device) for i in range(self.num_frames)]
+        if self._carrier and params.get("u_init") is not None:
+            g_opt = [self._dev(params["u_init"][i]) for i in range(self.num_frames)]
+            assert all(tuple(g.shape) == self._var_shape(0) for g in g_opt), "params['u_init'][t] is [Gd,Gh,Gw,3]"
         if self._colour:
             g_opt = [self._dev(c_init[i]) for i in range(self.num_frames)]
             if inv is not None:
@@ -526,7 +600,7 @@ class Styler(StylerBase):
         # by tests/golden/util_reference.npz): evaluated on the device, and -- frames sharded -- only the frames inside a
         # rank's filter window travel (point-to-point halo, parallel.exchange_frames)
         Wt = temporal_weights(len(keys), self.window_sigma) if (self.window_sigma > 0 and len(keys) > 1) else None
-        if Wt is not None:
+        if Wt is not None and not self._carrier:
             assert len(set(int(x.shape[0]) for x in p)) == 1, "temporal smoothing needs the same particles in every frame"
         need_by_rank = []
         for rk in range(world):
@@ -535,7 +609,7 @@ class Styler(StylerBase):
                 for t in list(nd):
                     nd |= set(keys[jj] for jj in np.nonzero(Wt[keys.index(t)])[0])
             need_by_rank.append(nd)
-        like = torch.zeros(p[0].shape[0], nvar, device=self.device)
+        like = torch.zeros(*self._var_shape(p[0].shape[0]), device=self.device)
 
         def sync_all(g):
             """every rank receives every key frame's variable (octave ends, final inference: a few MB per frame)"""
@@ -669,6 +743,11 @@ class Styler(StylerBase):
                 p_out, d_out, _ = self._field(p[t], r[t], g_opt[t], res)
                 dimg = self._colour_d_img(p[t], r[t], g_opt[t], res) if self._colour else \
                     self._joint_d_img(p[t], r[t], g_opt[t], res) if self._joint else self.loss_d_img(d_out)
+            if self._carrier:
+                # (the sampled displacements beside the positions they make: p + v is result['p'], float for float)
+                inv = invs[t]
+                p_out, v_t = ops.carrier_displace(g_opt[t].contiguous(), p[t], cubic=self._carrier_cubic)
+                v_sty.append((v_t if inv is None else v_t[inv]).cpu().numpy())
             p_sty.append((p_out if inv is None else p_out[inv]).cpu().numpy())
             if "p" in self.target_field:
                 v_t = g_opt[t][:, 0:3] if self._joint else g_opt[t]
@@ -676,7 +755,7 @@ class Styler(StylerBase):
             d_sty.append(torch.abs(d_out[0]).cpu().numpy())      # abs(): drop the sign-bit mask of -0.0
             r_sty.append(dimg[0].cpu().numpy().astype(np.uint8))
         result["p"] = p_sty
-        if "p" in self.target_field:
+        if self._moves:
             result["v"] = v_sty
         result["d"] = np.array(d_sty)
         result["r"] = np.array(r_sty)
@@ -684,6 +763,9 @@ class Styler(StylerBase):
             # 'opt' in natural units: (v, c), the colour columns times colour_lr_scale
             unit = torch.tensor([1.0] * 3 + [float(self.colour_lr_scale)] * 3, device=self.device)
             g_opt = [g * unit for g in g_opt]
+        if self._carrier:
+            inv = None                                       # (the fields have no particle axis)
+            result["carrier_resolution"] = list(self.carrier_resolution)
         result["opt"] = [(g if inv is None else g[inv]).cpu().numpy() for g in g_opt]   # build extension: the variables
         if self._colour or self._joint:
             # the colours as styler_2p returns them: clipped, and faded by the particle's density (styler_2p.py:297-300)

@@ -434,3 +434,27 @@ def g2p_cubic(g, p, is_2d=True):
 def g2p_linear(g, p, is_2d=True):
     """the (bi/tri)linear branch under its own name (transform.py:1110)"""
     return g2p(g, p, is_2d=is_2d, is_linear=True)
+
+
+class _CarrierDisplace(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, p, cubic):
+        u2, p2 = u.detach().contiguous(), p.detach().contiguous()
+        ctx.cubic, ctx.dims = bool(cubic), tuple(u2.shape[:-1])
+        ctx.save_for_backward(p2)
+        return ops.carrier_displace(u2, p2, cubic=cubic, want_v=False)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (p2,) = ctx.saved_tensors
+        g_u = ops.carrier_bwd(g.contiguous(), p2, ctx.dims, cubic=ctx.cubic) if ctx.needs_input_grad[0] else None
+        return g_u, None, None
+
+
+def carrier_displace(u, p, cubic=True):
+    """particles moved by a displacement field on a carrier grid (build extension, include/nfs_carrier.h):
+    u [X,Y,(Z),nd] cell-centred over the whole domain, in the units of p; p [N,nd] in [0,1], array order -> p + g2p(u, p)
+    [N,nd] (Catmull-Rom unless ``cubic`` is false).  Differentiable in u ONLY: the gradient in u is the transpose of the
+    sampling (``ops.carrier_bwd``; fast with p in ``grid_order``), the gradient in p is None -- the stylizer samples the
+    field at a frame's constant positions, and d p_out / d p = 1 + grad u is not built."""
+    return _CarrierDisplace.apply(u, p, cubic)
