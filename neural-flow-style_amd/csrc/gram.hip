@@ -423,10 +423,11 @@ static void gram_plan(GramArgs& a, int cus) {
   // few images / few tile pairs: shorter slabs until the grid covers the chip twice (not below 4 chunks)
   while (cps > 4 && pairs * ((total_chunks + cps - 1) / cps) < 2 * (int64_t)cus) cps >>= 1;
   if (cps > total_chunks) cps = total_chunks;
-  if ((total_chunks + cps - 1) / cps > 256) cps = (total_chunks + 255) / 256;   // bound the reduce fan-in
   // many tile pairs, few pixels (relu4_1, relu5_1 at 8 views): one slab -- the tile kernel then writes G itself
   if (pairs >= cus && total_chunks <= 32) cps = total_chunks;
   if (env_cps > 0) cps = env_cps < total_chunks ? env_cps : total_chunks;
+  // bound the reduce fan-in -- last, so that it also holds for a slab length from the environment
+  if ((total_chunks + cps - 1) / cps > 256) cps = (total_chunks + 255) / 256;
   a.cps = cps;
   a.nslab = (total_chunks + cps - 1) / cps;
 }

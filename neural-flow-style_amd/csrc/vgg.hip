@@ -37,7 +37,8 @@ int winograd_conv(const float* x, const float* U, const float* aux0, const float
 // layers with >= 64 channels on both sides take the Winograd path (F(4x4,3x3): 4x fewer MFMA flops); only the
 // 3-channel conv1_1 stays direct.  NFS_WINOGRAD_MIN_CH raises the threshold (timing comparisons).
 static inline bool winograd_eligible(int K, int N) {
-  static const int min_ch = [] { const char* e = getenv("NFS_WINOGRAD_MIN_CH"); return e ? atoi(e) : 64; }();
+  // (never below 64: the Winograd kernels take no narrower layer)
+  static const int min_ch = [] { const char* e = getenv("NFS_WINOGRAD_MIN_CH"); const int v = e ? atoi(e) : 64; return v < 64 ? 64 : v; }();
   return K >= min_ch && N >= min_ch && K % 32 == 0 && N % 64 == 0;
 }
 
@@ -636,6 +637,7 @@ struct C3Grid { int tiles_x, tiles_y; int64_t ntiles; unsigned blocks; };
 static C3Grid c3_grid(int B, int H, int W, int tw, int th, int per_cu) {
   C3Grid g{(W + tw - 1) / tw, (H + th - 1) / th, 0, 0};
   g.ntiles = (int64_t)B * g.tiles_x * g.tiles_y;
+  if (per_cu < 0) per_cu = 0;                                       // (a negative NFS_C3*_BLOCKS: one block per tile)
   const int64_t cap = 256 * (int64_t)per_cu;
   g.blocks = (unsigned)(per_cu > 0 && g.ntiles > cap ? cap : g.ntiles);
   return g;

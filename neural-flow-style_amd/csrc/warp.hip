@@ -1228,7 +1228,8 @@ static void rotate_bwd_tiled_launch(const float* src, const float* rot, float* g
   // raises it for any view whose matrix is no rotation: rotate_view_extra_weight)
   const int nmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
   const float bound_factor = 4.f * (float)nmax * (float)V + 8.f;
-  static const int order = [] { const char* e = getenv("NFS_RT_XCD"); return e ? atoi(e) : 0; }();
+  // (0, 1 or 2; anything else is the default order, not a third decomposition the kernel does not have)
+  static const int order = [] { const char* e = getenv("NFS_RT_XCD"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 ? v : 0; }();
   const int grid = (live || order == 0) ? tz * ty * tx : 8 * ((tz * ty + 7) / 8) * tx;
   if (live) {
     hipLaunchKernelGGL(rotate_live_boxes_kernel, dim3((tz * ty * tx + LB_WAVES - 1) / LB_WAVES), dim3(LB_THREADS), 0, s,

@@ -1,7 +1,7 @@
 """The VGG 3x3 convolution chain restated in float64 numpy (no torch, no tiles): the SAME stride-1 convolution, its data
 gradient, the layer rules of include/nfs_hip.h around them, the two Winograd algorithms the kernels run (restated in
-float64 to prove the matrices and in float32 to measure what float32 rounding alone does), and a worst-case float32
-bound for every output element.  Layout NHWC, filters HWIO [3,3,Ci,Co].
+float64 to prove the matrices and in float32 to measure what float32 rounding alone does), the F(2x2) algorithm that
+NFS_WINOGRAD_TILE=2 selects, restated the same two ways, and a worst-case float32 bound for every output element.  Layout NHWC, filters HWIO [3,3,Ci,Co].
 
 Exact inputs.  With integer x, w, gy (|.| <= 3) and integer bias / addend every product and every partial sum of the
 DIRECT kernels is an integer below 2^24 (``exact_units`` asserts it through loss_ref.units), so float32 holds each of
@@ -32,6 +32,20 @@ Bounds (u = 2^-24, one float32 rounding; K input channels of the kernel's GEMM):
                     39, rounded up to c = 40; the factor 1.01 covers the second-order terms ((K + c) u < 4e-5).
                     F(4x4) needs less at every stage; one constant serves both families.
 
+  F(2x2) Winograd   1.01 (K + c2) u AW2 + u |y|,  c2 = 12  (NFS_WINOGRAD_TILE=2: winograd_pack_kernel, winograd_input_kernel,
+                    winograd_output_kernel).  The same argument with the F(2x2) matrices, which hold only 0, +-1 and 1/2:
+                      filter passes (G, twice)          <= 2 each: the rows 1/2 (g0 +- g1 + g2) are two adds, the product by
+                                                        1/2 is exact                                                      4
+                      input passes (B^T, twice)         1 each: every row is one difference or one sum                   2
+                      the K sum                         K, as above (the f32-input MFMA of the batched GEMM; there is no
+                                                        split into K parts on this path)                                 K
+                      output passes (A^T, twice)        2 each: three terms, two adds, no product                        4
+                      the bias, the addend                                                                               2
+                    12 = c2.  AW2 is built from |G2|, |B2^T|, |A2^T|; the rows of |B2^T| and |A2^T| sum to at most 2 and 3
+                    where F(4x4)'s sum to 10 and 19, so on the same input the F(2x2) bound is several times tighter
+                    (tests/test_conv_ref_cpu.py prints the ratio): the F(4x4) bound would let a wrong F(2x2) transform
+                    row through and is not borrowed.
+
   pooled output     the mean of the four bounds + 3 u y_pool  (three adds; the factor 1/4 is exact)
 
 The bound is loose against rounding (float32 Winograd sits at a thousandth of it) and tight against structure: a dropped
@@ -43,6 +57,7 @@ import numpy as np
 from tests.loss_ref import LIMIT, U, avgpool2, avgpool2_bwd, err_ratio, f64, units  # noqa: F401  (re-exported)
 
 C_WINO = 40
+C_WINO2 = 12
 C_DIRECT = 20
 
 
@@ -115,7 +130,11 @@ BT5 = np.array([[-2, 4, 2.5, -5, -0.5, 1, 0], [0, 2, -2, -4.5, 0.5, 1, 0], [0, -
                 [0, -2, 4, 2.5, -5, -0.5, 1]])
 AT5 = np.array([[1, 1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 1 / 2, 0], [0, 1, 1, 4, 4, 1 / 4, 0], [0, 1, -1, 8, -8, 1 / 8, 0],
                 [0, 1, 1, 16, 16, 1 / 16, 1]])
-MATS = {4: (G4, BT4, AT4), 5: (G5, BT5, AT5)}
+# F(2x2, 3x3): points 0, +-1, inf (winograd.hip: winograd_pack_kernel, winograd_input_kernel, winograd_output_kernel)
+G2 = np.array([[1, 0, 0], [1 / 2, 1 / 2, 1 / 2], [1 / 2, -1 / 2, 1 / 2], [0, 0, 1]])
+BT2 = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64)
+AT2 = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=np.float64)
+MATS = {2: (G2, BT2, AT2), 4: (G4, BT4, AT4), 5: (G5, BT5, AT5)}
 
 
 def patches(x, m):
@@ -138,7 +157,7 @@ def untile(Y, H, W):
 
 
 def winograd64(x, w, m, absolute=False):
-    """the convolution through F(m x m, 3x3) in float64 (m = 4 | 5): A^T ( sum_k (G g G^T) (.) (B^T d B) ) A per tile.
+    """the convolution through F(m x m, 3x3) in float64 (m = 2 | 4 | 5): A^T ( sum_k (G g G^T) (.) (B^T d B) ) A per tile.
     ``absolute``: every matrix and operand by its absolute value -- AW of the bound"""
     x, w = f64(x), f64(w)
     G, BT, AT = MATS[m]
@@ -160,7 +179,7 @@ def wino_bound(x, w, m, y):
     """the float32 bound of every element of y (the FINAL stored value: after bias, ReLU, mask, addend) computed through
     F(m x m) from x and w"""
     K = np.shape(x)[-1]
-    return 1.01 * (K + C_WINO) * U * winograd64(x, w, m, absolute=True) + U * np.abs(f64(y))
+    return 1.01 * (K + (C_WINO2 if m == 2 else C_WINO)) * U * winograd64(x, w, m, absolute=True) + U * np.abs(f64(y))
 
 
 def direct_bound(S, K, y):
@@ -176,7 +195,9 @@ _f = np.float32
 
 
 def _g32(g0, g1, g2, m):
-    """wg_g<6> / wg_g<7>: the kernels' expressions, every operation rounded to float32"""
+    """wg_g<6> / wg_g<7> / winograd_pack_kernel: the kernels' expressions, every operation rounded to float32"""
+    if m == 2:
+        return [g0, _f(0.5) * (g0 + g1 + g2), _f(0.5) * (g0 - g1 + g2), g2]
     if m == 4:
         return [_f(0.25) * g0, _f(-1 / 6) * (g0 + g1 + g2), _f(-1 / 6) * (g0 - g1 + g2),
                 _f(1 / 24) * g0 + _f(1 / 12) * g1 + _f(1 / 6) * g2, _f(1 / 24) * g0 - _f(1 / 12) * g1 + _f(1 / 6) * g2, g2]
@@ -186,7 +207,9 @@ def _g32(g0, g1, g2, m):
 
 
 def _bt32(d, m):
-    """wg4_bt / w5_bt"""
+    """wg4_bt / w5_bt / winograd_input_kernel"""
+    if m == 2:
+        return [d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]]
     if m == 4:
         p, q = _f(-4) * d[2] + d[4], _f(-4) * d[1] + d[3]
         e, f = -d[2] + d[4], _f(-2) * d[1] + _f(2) * d[3]
@@ -201,7 +224,9 @@ def _bt32(d, m):
 
 
 def _at32(v, m):
-    """wg4_at / w5_at"""
+    """wg4_at / w5_at / winograd_output_kernel"""
+    if m == 2:
+        return [v[0] + v[1] + v[2], v[1] - v[2] - v[3]]
     s12, d12, s34, d34 = v[1] + v[2], v[1] - v[2], v[3] + v[4], v[3] - v[4]
     if m == 4:
         return [v[0] + s12 + s34, d12 + _f(2) * d34, s12 + _f(4) * s34, d12 + _f(8) * d34 + v[5]]
