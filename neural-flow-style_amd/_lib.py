@@ -156,7 +156,9 @@ _OWNER = _owners(list(SIDE.values()) + list(SIDE_LATER.values()))
 # as a whole (only that its own key is in it and bound).  Its names are a second lookup that call() consults after _OWNER.
 # exposure: the smoke colour render at a fixed exposure and its derivative in the density (colour_render 'exposure')
 # carrier: particles moved by a displacement field on a coarse grid, and the transpose of that sampling (target_field 'g')
-SIDE_OPEN = {k: SideLibrary(k) for k in ("exposure", "carrier")}
+# flow: particles carried along a flow of the carrier field in K Euler steps, and the sweep back along the path
+# (--carrier_steps of target_field 'g')
+SIDE_OPEN = {k: SideLibrary(k) for k in ("exposure", "carrier", "flow")}
 
 
 def _owners_open(records, taken):

@@ -25,6 +25,9 @@ of smoke through ``--colour_render exposure``; ``--colour_lr_scale`` (positive f
 ``--target_field g`` (styler_3p): the variable is a displacement field on a coarse carrier grid, sampled at the particles
 (include/nfs_carrier.h); ``--carrier_resolution`` (three ints >= 1; ``complete()`` defaults it to ``max(n // 8, 2)`` per axis
 of ``resolution``) is that grid and ``--carrier_interp`` (``cubic`` / ``linear``, default ``cubic``) the sampling kernel.
+``--carrier_steps`` (int >= 1, default 1): the field is a velocity over one unit of pseudo-time and the particles are carried
+through it in that many explicit Euler steps (include/nfs_flow.h); 1 is the one-sample displacement p + g2p(u, p).  A field
+stylised at K steps must be applied at the same K.
 """
 from __future__ import annotations
 
@@ -124,6 +127,7 @@ _FLAGS = [
     ("MI355X", "colour_exposure", dict(type=float, default=argparse.SUPPRESS)),
     ("MI355X", "carrier_resolution", dict(nargs=3, type=int, default=argparse.SUPPRESS)),
     ("MI355X", "carrier_interp", dict(type=str, default=argparse.SUPPRESS)),
+    ("MI355X", "carrier_steps", dict(type=int, default=argparse.SUPPRESS)),
 ]
 
 COLOUR_RENDERS = ("", "smoke", "liquid", "exposure")
@@ -240,6 +244,20 @@ def check_carrier(config):
     return tuple(int(v) for v in res), interp == "cubic"
 
 
+def check_carrier_steps(config):
+    """``carrier_steps`` (target_field 'g') as an int >= 1, or a ValueError naming the flag (absent or None: 1)"""
+    steps = getattr(config, "carrier_steps", None)
+    steps = 1 if steps is None else steps
+    try:
+        ok = not isinstance(steps, bool) and float(steps) == int(steps) and int(steps) >= 1
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("--carrier_steps %r: the number of Euler steps of the carrier flow is an int >= 1 (1 = the "
+                         "one-sample displacement)" % (steps,))
+    return int(steps)
+
+
 def complete(config):
     """defaults for the attributes the reference drivers inject after parsing"""
     if not hasattr(config, "rng") or config.rng is None:
@@ -274,5 +292,7 @@ def complete(config):
         config.carrier_resolution = default_carrier_resolution(getattr(config, "resolution", ()))
     if not hasattr(config, "carrier_interp"):
         config.carrier_interp = "cubic"
+    if not hasattr(config, "carrier_steps"):
+        config.carrier_steps = 1
 
     return config

@@ -1,6 +1,7 @@
 // The axis rule of the cell-centred grid <-> particle links, written once: nfs_g2p_fwd (splat.hip, libnfs_hip.so) and the
 // carrier kernels (carrier.hip, libnfs_carrier.so: the same sampling and its transpose in the grid) include this file, so
-// both libraries form indices and weights with the same text.
+// both libraries form indices and weights with the same text.  So does flow.hip (libnfs_flow.so), which also needs the
+// weights' derivatives: g2p_axis_d below.
 // g [X,Y,(Z),C] cell-centred, p [N,nd] in [0,1] (axis order = array order): x = p * n, base = floor(x - 0.5).
 // linear: cells (base, base+1) clipped to [0,n-1], weight dx = x - (clipped base + 0.5) (so outside the centre
 // lattice both cells coincide and the value is the border cell's); cubic: cells base-1..base+2 clipped,
@@ -30,6 +31,22 @@ __device__ __forceinline__ void g2p_axis(float x, int n, int cubic, int* idx, fl
   w[1] = 1.5f * t3 - 2.5f * t2 + 1.f;
   w[2] = -1.5f * t3 + 2.f * t2 + 0.5f * t;
   w[3] = 0.5f * t3 - 0.5f * t2;
+}
+
+// the derivatives of g2p_axis's weights in x, from the indices g2p_axis returned for the same x (flow.hip,
+// libnfs_flow.so): the clipped index does not move with x, so d/dx = d/dt (cubic: t formed as above) or d/ddx (linear:
+// constants; where both taps were clipped onto one cell the two terms cancel in the sum over the taps)
+__device__ __forceinline__ void g2p_axis_d(float x, int cubic, const int* idx, float* dw) {
+  if (!cubic) {
+    dw[0] = -1.f; dw[1] = 1.f;
+    return;
+  }
+  const float t = x - ((float)idx[1] + 0.5f);
+  const float t2 = t * t;
+  dw[0] = -1.5f * t2 + 2.f * t - 0.5f;
+  dw[1] = 4.5f * t2 - 5.f * t;
+  dw[2] = -4.5f * t2 + 4.f * t + 0.5f;
+  dw[3] = 1.5f * t2 - t;
 }
 
 // the stencil of particle i: per axis d < nd the taps' cells ix[d][.] and weights wx[d][.]; an axis beyond nd is the one

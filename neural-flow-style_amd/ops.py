@@ -1569,6 +1569,53 @@ def carrier_bwd(g_v, p, dims, cubic=True, route=0, count=False):
     return (g_u, n_box) if count else g_u
 
 
+# ---- particles carried along a flow of the carrier field, and the sweep back along the path (include/nfs_flow.h) --------
+
+def _flow_dims(who, u, nd):
+    if u.dim() != nd + 1 or int(u.shape[-1]) != nd:
+        raise ValueError("%s: u %s is not a field of %d-vectors on a %d-D grid" % (who, tuple(u.shape), nd, nd))
+    return _carrier_dims(u.shape[:nd], nd)
+
+
+def flow_fwd(u, p, steps, cubic=True):
+    """u [X,Y,(Z),nd] a velocity over one unit of pseudo-time on the carrier grid, p [N,nd] -> path [steps+1,N,nd]:
+    path[0] = p, path[k+1] = path[k] + h g2p_fwd(u, path[k]) with h = 1 / steps, in one launch.  Bit for bit those
+    operators (the float32 product h v, then the float32 sum); ``steps`` 1 gives ``carrier_displace``'s p_out as path[1]"""
+    nd, K = int(p.shape[-1]), int(steps)
+    X, Y, Z = _flow_dims("flow_fwd", u, nd)
+    N = int(p.shape[0])
+    path = _empty((max(K, 0) + 1, N, nd), p)
+    _lib.call("nfs_flow_fwd", _ptr(u), _ptr(p), _ptr(path), nd, X, Y, Z, N, K, int(bool(cubic)), _stream())
+    return path
+
+
+def flow_bwd(u, path, g_out, cubic=True):
+    """u, path [K+1,N,nd] of ``flow_fwd``, g_out [N,nd] the gradient in path[K] -> lam [K+1,N,nd]: lam[K] = g_out,
+    lam[k] = lam[k+1] + h J(path[k])^T lam[k+1], one launch, a pure gather.  lam[0] is the gradient in p"""
+    if path.dim() != 3 or int(path.shape[0]) < 2 or tuple(g_out.shape) != tuple(path.shape[1:]):
+        raise ValueError("flow_bwd: path %s is not [K+1,N,nd] with K >= 1 for g_out %s [N,nd]"
+                         % (tuple(path.shape), tuple(g_out.shape)))
+    K, N, nd = (int(v) for v in path.shape)
+    K -= 1
+    X, Y, Z = _flow_dims("flow_bwd", u, nd)
+    lam = _empty((K + 1, N, nd), path)
+    _lib.call("nfs_flow_bwd", _ptr(u), _ptr(path), _ptr(g_out), _ptr(lam), nd, X, Y, Z, N, K, int(bool(cubic)), _stream())
+    return lam
+
+
+def flow_grad(u, path, g_out, cubic=True, route=0):
+    """the gradients of a flow in its field and in its starting positions -> (g_u [like u], g_p [N,nd]): the sweep
+    (``flow_bwd``), then g_u = h sum_k g2p^T(lam[k+1]; path[k]) as ONE ``carrier_bwd`` over the K N positions path[0:K]
+    with the gradients lam[1:K+1] (contiguous slices; ``route`` is that call's) and one scale of the grid by h"""
+    lam = flow_bwd(u, path, g_out, cubic=cubic)
+    K, N, nd = int(path.shape[0]) - 1, int(path.shape[1]), int(path.shape[2])
+    g_u = carrier_bwd(lam[1:].reshape(K * N, nd), path[:K].reshape(K * N, nd), tuple(u.shape[:nd]), cubic=cubic,
+                      route=route)
+    if K > 1:
+        g_u.mul_(1.0 / K)
+    return g_u, lam[0]
+
+
 
 # ---- SURVEY 8(f)-3: node types of the Inception-v1 loss network ------------------------------------------------------
 # Operands are channel RANGES of contiguous [B,H,W,ld] buffers: (tensor, first channel, channels).

@@ -37,7 +37,16 @@ Forward graph per frame (styler_3p.py:42-164):
        in place: there is NO transport between frames (particle ``params`` carry no grid velocity), a frame's field is
        filtered with its neighbours' cell by cell.  The carrier resolution is the same at every octave and u is in domain
        units, so it carries over unchanged.  ``result['opt']`` are the fields, ``result['v']`` the sampled per-particle
-       displacements, ``result['p']`` = p + v.  ``w_density`` and a process group are refused
+       displacements, ``result['p']`` = p + v.  ``w_density`` and a process group are refused.
+       ``--carrier_steps`` K > 1 (include/nfs_flow.h): the one-sample map folds once grad u reaches about 1 per unit of p
+       (particles cross, pile up and leave holes), so u becomes a VELOCITY over one unit of pseudo-time and the particles
+       are carried through it in K explicit Euler steps of 1 / K, path[k+1] = path[k] + g2p(u, path[k]) / K
+       (``T.carrier_flow``, one launch: ``ops.flow_fwd``); the gradient sweeps the stored path back
+       (``ops.flow_bwd``: lam[k] = lam[k+1] + J(path[k])^T lam[k+1] / K, the Jacobian of the sampling in the position)
+       and reaches u through ONE transpose over the K N positions of the path (``ops.flow_grad``).  ``result['p']`` =
+       path[K], ``result['v']`` = path[K] - p, ``apply_carrier`` integrates with the same K: a field stylised at K must
+       be applied at that K, and K = 1 is the displacement above, launch for launch.  Euler steps only; with another
+       ``target_field`` K > 1 is refused
   -> 3x3x3 smoothing conv -> max(.,0) = d_out -> [rotate] -> render -> max-normalise
   -> x255, grey->3ch = d_img -> VGG-19 -> Gram style loss (+TV).
 The particle side runs through ``torch.autograd`` (custom Functions wrapping the splat
@@ -60,7 +69,7 @@ import torch
 from . import engine, ops, parallel
 from . import transform as T
 from . import vgg as vggmod
-from .config import check_carrier, check_colour_render, check_optimizer, colour_exposure
+from .config import check_carrier, check_carrier_steps, check_colour_render, check_optimizer, colour_exposure
 from .styler_base import StylerBase
 from .util import temporal_weights
 
@@ -87,6 +96,7 @@ class Styler(StylerBase):
     _colour = False                                  # target_field 'c' (set by the constructor)
     _joint = False                                   # target_field 'pc' (set by the constructor)
     _carrier = False                                 # target_field 'g' (set by the constructor)
+    _carrier_steps = 1                               # carrier_steps of 'g' (set by the constructor)
 
     def __init__(self, self_dict):
         check_optimizer(self_dict, grid=False)
@@ -95,6 +105,11 @@ class Styler(StylerBase):
             self._check_joint(self_dict)
         if getattr(self_dict, "target_field", "") == "g":
             self._check_carrier(self_dict)
+        steps = check_carrier_steps(self_dict)
+        if steps > 1 and getattr(self_dict, "target_field", "") != "g":
+            raise ValueError("--carrier_steps %d with target_field %r: the steps are those of the carrier flow, which "
+                             "belongs to --target_field g (pass --carrier_steps 1)"
+                             % (steps, getattr(self_dict, "target_field", "")))
         if getattr(self_dict, "target_field", "") == "c":
             # the colour path renders by emission-absorption only and has no auxiliary field terms (refused before the
             # base class loads a network)
@@ -120,6 +135,7 @@ class Styler(StylerBase):
         self._carrier = self.target_field == "g"
         if self._carrier:
             self.carrier_resolution, self._carrier_cubic = check_carrier(self)
+            self._carrier_steps = steps
         if self.rotate:
             self.rot_mat_, self.views = T.rot_mat(self.phi0, self.phi1, self.phi_unit, self.theta0, self.theta1,
                                                   self.theta_unit, sample_type=self.sample_type, rng=self.rng,
@@ -188,13 +204,17 @@ class Styler(StylerBase):
 
     def apply_carrier(self, u, p):
         """a result of target_field 'g' applied to ANY particle set: u [Gd,Gh,Gw,3] (an entry of result['opt']), p [N,3]
-        in the normalised domain, array order -> p + g2p(u, p) with this stylizer's ``carrier_interp``; numpy in, numpy
-        out (device tensors stay on the device).  That is how a field stylised on a low-resolution set reaches a
-        resampled one"""
-        cubic = check_carrier(self)[1]
+        in the normalised domain, array order -> p + g2p(u, p) with this stylizer's ``carrier_interp``, or with
+        ``carrier_steps`` K > 1 the end of the K-step flow through u (``ops.flow_fwd``) -- a field stylised at K means
+        that map and no other; numpy in, numpy out (device tensors stay on the device).  That is how a field stylised on
+        a low-resolution set reaches a resampled one"""
+        cubic, steps = check_carrier(self)[1], check_carrier_steps(self)
         as_np = not torch.is_tensor(p)
         u_, p_ = (x.to(self.device).float().contiguous() if torch.is_tensor(x) else self._dev(x) for x in (u, p))
-        out = ops.carrier_displace(u_, p_, cubic=cubic, want_v=False)[0]
+        if steps == 1:
+            out = ops.carrier_displace(u_, p_, cubic=cubic, want_v=False)[0]
+        else:
+            out = ops.flow_fwd(u_, p_, steps, cubic=cubic)[steps]
         return out.cpu().numpy() if as_np else out
 
     def _make_colour_loss(self):
@@ -342,7 +362,9 @@ class Styler(StylerBase):
         if self._carrier:
             # ('g': the carrier grid sampled at the frame's constant positions; autograd carries the positions' gradient
             # into the grid through the transpose, ops.carrier_bwd)
-            p_ = T.carrier_displace(var, p, self._carrier_cubic).unsqueeze(0)
+            # (carrier_steps K > 1: var is a velocity and the positions are the end of its K-step flow, T.carrier_flow)
+            p_ = (T.carrier_displace(var, p, self._carrier_cubic) if self._carrier_steps == 1 else
+                  T.carrier_flow(var, p, self._carrier_steps, self._carrier_cubic)).unsqueeze(0)
         elif self._moves:
             p_ = p_ + (var[:, 0:3] if self._joint else var).unsqueeze(0)     # ('pc': the displacement columns)
         p_all = p_                                   # ('c': the positions as they came; var is not read)
@@ -746,7 +768,13 @@ class Styler(StylerBase):
             if self._carrier:
                 # (the sampled displacements beside the positions they make: p + v is result['p'], float for float)
                 inv = invs[t]
-                p_out, v_t = ops.carrier_displace(g_opt[t].contiguous(), p[t], cubic=self._carrier_cubic)
+                if self._carrier_steps == 1:
+                    p_out, v_t = ops.carrier_displace(g_opt[t].contiguous(), p[t], cubic=self._carrier_cubic)
+                else:
+                    # (the end of the flow, float for float what apply_carrier returns, and the displacement it amounts to)
+                    p_out = ops.flow_fwd(g_opt[t].contiguous(), p[t], self._carrier_steps,
+                                         cubic=self._carrier_cubic)[self._carrier_steps]
+                    v_t = p_out - p[t]
                 v_sty.append((v_t if inv is None else v_t[inv]).cpu().numpy())
             p_sty.append((p_out if inv is None else p_out[inv]).cpu().numpy())
             if "p" in self.target_field:

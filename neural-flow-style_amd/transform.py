@@ -458,3 +458,33 @@ def carrier_displace(u, p, cubic=True):
     sampling (``ops.carrier_bwd``; fast with p in ``grid_order``), the gradient in p is None -- the stylizer samples the
     field at a frame's constant positions, and d p_out / d p = 1 + grad u is not built."""
     return _CarrierDisplace.apply(u, p, cubic)
+
+
+class _CarrierFlow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, p, steps, cubic):
+        u2, p2 = u.detach().contiguous(), p.detach().contiguous()
+        path = ops.flow_fwd(u2, p2, steps, cubic=cubic)
+        ctx.cubic = bool(cubic)
+        ctx.save_for_backward(u2, path)
+        return path[-1].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        u2, path = ctx.saved_tensors
+        need_u, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_u:
+            g_u, g_p = ops.flow_grad(u2, path, g.contiguous(), cubic=ctx.cubic)
+        else:
+            g_u, g_p = None, ops.flow_bwd(u2, path, g.contiguous(), cubic=ctx.cubic)[0] if need_p else None
+        return g_u, (g_p if need_p else None), None, None
+
+
+def carrier_flow(u, p, steps, cubic=True):
+    """particles carried along a flow of the carrier field (build extension, include/nfs_flow.h): u [X,Y,(Z),nd] is a
+    velocity over one unit of pseudo-time, p [N,nd] in [0,1], array order -> path[steps], where path[0] = p and
+    path[k+1] = path[k] + g2p(u, path[k]) / steps (explicit Euler; ``steps`` 1 is ``carrier_displace``'s map).
+    Differentiable in u AND in p: the backward pass sweeps the stored path (``ops.flow_bwd``: lam[k] = (1 + h J^T) lam[k+1],
+    the Jacobian 1 + h grad u that ``carrier_displace`` does not build) and adds the transposes of all steps in one
+    ``ops.carrier_bwd`` (``ops.flow_grad``).  The path, (steps + 1) N nd floats, is kept for the backward pass."""
+    return _CarrierFlow.apply(u, p, steps, cubic)
